@@ -82,7 +82,21 @@ def parse():
     p.add_argument("--dry-run", action="store_true",
                    help="launch plumbing only (ranks, rendezvous, barrier, max-over-ranks timing of empty steps): "
                         "no GPU is touched; the JSON line says dry_run")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="everything beyond the headline: stream ceilings, prefill batch time, TTFT, serving legs, roofline / "
+                        "null-step / ragged / 64-row objects, prefill attention, CPU baseline + parity probe, the 13B leg, "
+                        "multi-GPU migration and E/P/D legs, and the headline as the median of several timed regions.  "
+                        "Without it a run sets up, warms up, times --steps steps once and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    if not args.full:      # a plain run: nothing but the headline
+        for flag in ("no_cpu_baseline", "no_ttft", "no_serving", "no_serving_64", "no_disaggregated", "no_migration",
+                     "no_13b", "no_tune", "no_ragged", "no_null_step"):
+            setattr(args, flag, True)
+    return args
 
 
 def launch_ranks_if_needed(args):
@@ -121,6 +135,22 @@ def timed_contexts(prompt_len, n_generate, steps):
     stride = (hi - lo) // (steps - 1)
     first = lo + ((hi - lo) - stride * (steps - 1)) // 2
     return [first + k * stride for k in range(steps)]
+
+
+def timed_passes(prompt_len, n_generate, steps):
+    """The contexts of exactly `steps` timed decode steps, as passes over the generation (the decode state is rewound to
+    the pass's first context in front of each).  Up to the generation's 255 decode steps: one pass, `timed_contexts`.
+    More: whole passes over 705..959 and a last pass of the remaining steps at consecutive contexts, centred in the same
+    range — every pass has stride 1, so one captured step serves them all."""
+    lo, hi = prompt_len + 1, prompt_len + n_generate - 1
+    n = hi - lo + 1
+    if steps <= n:
+        return [timed_contexts(prompt_len, n_generate, steps)]
+    passes = [list(range(lo, hi + 1))] * (steps // n)
+    if steps % n:
+        first = lo + (n - steps % n) // 2
+        passes.append(list(range(first, first + steps % n)))
+    return passes
 
 
 def dry_run(args):
@@ -1061,16 +1091,19 @@ def parity_probe(dtype, dev, executor, steps=4):
 TIMED_REGIONS = 3
 
 
-def decode_leg(ctx, model, runner, ctxs, warmup, prompt_len, regions=TIMED_REGIONS):
+def decode_leg(ctx, model, runner, passes, warmup, prompt_len, regions=TIMED_REGIONS):
     """Warm-up, then the timed region of the contract: barrier + synchronize on both sides, exactly
-    len(ctxs) decode steps, MAX over ranks.  The contexts are equally spaced: the step's own device-side advance
-    moves the decode state from one to the next (stride 1 = the generation itself), so the timed region is
-    nothing but the K steps.
+    sum(len(p) for p in passes) decode steps, MAX over ranks.  Within a pass the contexts are equally spaced: the step's
+    own device-side advance moves the decode state from one to the next (stride 1 = the generation itself), so the timed
+    region is nothing but the K steps; between passes (more steps than the generation has: `timed_passes`) the clock
+    stops while the state is rewound.
     The region is run `regions` times behind the one warm-up (state rewound in between, outside the clocks), each bracketed
     as the contract says; the line reports the MEDIAN region (round-5 review: one 0.1-s region at a threshold with +-1 %
     box-to-box spread is a coin flip) and carries the fastest and slowest beside it.  Returns (median elapsed s, all)."""
+    ctxs = passes[0]
     stride = ctxs[1] - ctxs[0] if len(ctxs) > 1 else 1
-    assert all(b - a == stride for a, b in zip(ctxs, ctxs[1:])), "timed contexts must be equally spaced"
+    assert all(b - a == stride for p in passes for a, b in zip(p, p[1:])), "timed contexts must be equally spaced"
+    assert len(passes) == 1 or stride == 1, "several passes walk consecutive contexts"
     runner.cfg.advance_stride = stride
     ids = runner.input_ids.clone()
     if runner.cfg.use_graph:
@@ -1081,21 +1114,50 @@ def decode_leg(ctx, model, runner, ctxs, warmup, prompt_len, regions=TIMED_REGIO
         runner.step(record=False)
     all_elapsed = []
     for _ in range(max(1, regions)):
-        runner.set_state(ctxs[0] - stride, ids)      # the first step's advance makes it ctxs[0]
+        elapsed = 0.0
+        for i, p in enumerate(passes):
+            runner.set_state(p[0] - stride, ids)      # the first step's advance makes it p[0]
+            if i == 0:
+                ctx.barrier()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in p:
+                runner.step(record=False)
+            torch.cuda.synchronize()
+            elapsed += time.perf_counter() - t0
+            assert int(runner.kv_lens[0]) == p[-1], "the timed steps did not walk the announced contexts"
+        all_elapsed.append(ctx.max_over_ranks(elapsed, runner.dev))
         ctx.barrier(); torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in ctxs:
-            runner.step(record=False)
-        torch.cuda.synchronize()
-        all_elapsed.append(ctx.max_over_ranks(time.perf_counter() - t0, runner.dev))
-        ctx.barrier(); torch.cuda.synchronize()
-        assert int(runner.kv_lens[0]) == ctxs[-1], "the timed steps did not walk the announced contexts"
     # an in-kernel hand-over that gave up waiting leaves an error word: not a measurement
     if model.handover_failed():
         print("bench.py: a norm-fused launch gave up waiting for its producer workgroups",
               file=sys.stderr, flush=True)
         sys.exit(4)
     return sorted(all_elapsed)[len(all_elapsed) // 2], all_elapsed
+
+
+DUMP_BYTES_PER_ARRAY = 48 << 20
+
+
+def dump_outputs(runner, out_dir, max_bytes=DUMP_BYTES_PER_ARRAY):
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy — the token each sequence sampled
+    (float64, exact) and the K / V rows the step appended to every layer's cache ([layers, k|v, sequence, kv head,
+    head_dim], float32).  An array larger than `max_bytes` is written as a fixed sample of its flattened elements: the
+    first max_bytes / 4 of torch.randperm(size, generator=torch.Generator().manual_seed(0)), in ascending order."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize(runner.dev)
+    bs = runner.cfg.block_size
+    slots = runner.slots.long()          # the cache slots the last step wrote
+    arrays = {"next_token_ids": runner.input_ids.to(torch.float64),
+              "kv_appended": runner.pool[:, :, slots // bs, slots % bs].float()}
+    for name, t in arrays.items():
+        a = t.cpu().numpy()
+        if a.nbytes > max_bytes:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randperm(a.size, generator=g)[: max_bytes // a.itemsize].sort().values.numpy()
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def region_spread(all_elapsed, n_steps):
@@ -1118,7 +1180,7 @@ def leg_64_rows(ctx, model, args, dev, prompt_len, n_generate, steps=20):
     runner = DecodeRunner(model, cfg, seed=7)
     runner.input_ids.copy_(torch.randint(1000, 30000, (B,), device=dev))
     ctxs = timed_contexts(prompt_len, n_generate, steps)
-    elapsed, all_elapsed = decode_leg(ctx, model, runner, ctxs, 3, prompt_len)
+    elapsed, all_elapsed = decode_leg(ctx, model, runner, [ctxs], 3, prompt_len)
     ms = elapsed / len(ctxs) * 1e3
     step_bytes = sum(runner.step_bytes(c * B) for c in ctxs) / len(ctxs)
     gbs = step_bytes / (ms * 1e-3) / 1e9
@@ -1410,7 +1472,10 @@ def null_step_object(model, runner, ctxs, ms_per_step, reps=5, grid_wgs=256):
                     "the 5-launch structure's ceiling the built step reaches on this GPU in this run"}
 
 
-def ctx_label(ctxs):
+def ctx_label(ctxs, passes=None):
+    if passes is not None and len(passes) > 1:
+        return (f"{len(ctxs)} steps in {len(passes)} passes of consecutive contexts (the generation's 705..959, the last pass "
+                f"ctx {passes[-1][0]}..{passes[-1][-1]}), the state rewound between passes outside the clock")
     if len(ctxs) > 1 and ctxs[1] - ctxs[0] == 1:
         return f"ctx {ctxs[0]}..{ctxs[-1]} (consecutive steps of the generation)"
     return (f"ctx {ctxs[0]}..{ctxs[-1]} in {len(ctxs)} steps {ctxs[1] - ctxs[0] if len(ctxs) > 1 else 0} apart (mean "
@@ -1435,7 +1500,7 @@ def leg_13b(ctx, args, dtype, dev, rank):
     img = (torch.randn((args.batch, 576, shape.hidden_size), generator=g, device=dev) * 0.02).to(dtype)
     runner.prefill(prompts, img, image_token_id(shape.vocab_size))
     ctxs = timed_contexts(prompt_len, n_generate, min(args.steps_13b, n_generate - 1))
-    elapsed, all_elapsed = decode_leg(ctx, model, runner, ctxs, args.warmup, prompt_len)
+    elapsed, all_elapsed = decode_leg(ctx, model, runner, [ctxs], args.warmup, prompt_len)
     ms = elapsed / len(ctxs) * 1e3
     roofline, roofline_gemm, whole = roofline_objects(model, runner, ctxs, ms, args, name)
     if not args.no_null_step:
@@ -1468,7 +1533,7 @@ def leg_13b_child(args):
     model from start-up, so the fresh process is the case to quote.  The child is spawned, never exec'd."""
     cmd = [sys.executable, os.path.abspath(__file__), "--model", "13b", "--as-13b-leg", "--gpus", "1",
            "--steps", str(args.steps_13b), "--warmup", str(args.warmup), "--batch", str(args.batch), "--dtype", args.dtype,
-           "--executor", args.executor, "--no-cpu-baseline", "--no-serving", "--no-ttft", "--no-ragged"]
+           "--executor", args.executor, "--full", "--no-cpu-baseline", "--no-serving", "--no-ttft", "--no-ragged"]
     for flag in ("no_graph", "lib_gemm", "no_fused_attention", "no_ranked", "no_null_step", "no_serving_64"):
         if getattr(args, flag):
             cmd.append("--" + flag.replace("_", "-"))
@@ -1514,13 +1579,14 @@ def main():
     shape, model_name = model_shape(args.model)
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float16
     prompt_len, n_generate = 704, 256
-    steps = min(args.steps, n_generate - 1)
-    ctxs = timed_contexts(prompt_len, n_generate, steps)
+    steps = args.steps
+    passes = timed_passes(prompt_len, n_generate, steps)
+    ctxs = [c for p in passes for c in p]
     cfg = RunnerConfig(batch=args.batch, prompt_len=prompt_len, n_generate=n_generate,
                        use_graph=not args.no_graph, executor=args.executor)
     # the GPU's streaming rates, measured FIRST: at the end of a run the heap is fragmented and a fresh 1 GiB buffer reads
     # 20 % slower than the decode step itself streams (5.3 against 6.6-6.7 TB/s at the start: profiles/r5_kv_pool_placement.md)
-    stream_rates = (round(read_stream_ceiling_gbs(dev), 1), round(copy_ceiling_gbs(dev), 1))
+    stream_rates = (round(read_stream_ceiling_gbs(dev), 1), round(copy_ceiling_gbs(dev), 1)) if args.full else None
     model = LlamaForCausalLM.random_init(shape, dtype, dev, seed=0)
     model.use_hip_gemm = not args.lib_gemm
     if args.no_fused_attention:
@@ -1586,17 +1652,51 @@ def main():
         g = torch.Generator(device=dev).manual_seed(100 + rank)
         img = (torch.randn((args.batch, 576, shape.hidden_size), generator=g, device=dev) * 0.02).to(dtype)
         runner.prefill(prompts, img, image_token_id(shape.vocab_size))   # also warms every kernel / GEMM heuristic
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        runner.prefill(prompts, img, image_token_id(shape.vocab_size))
-        torch.cuda.synchronize()
-        ttft_ms = (time.perf_counter() - t0) * 1e3   # prefill of the whole 32-request batch
+        if args.full:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            runner.prefill(prompts, img, image_token_id(shape.vocab_size))
+            torch.cuda.synchronize()
+            ttft_ms = (time.perf_counter() - t0) * 1e3   # prefill of the whole 32-request batch
 
     # ---- warmup (untimed: graph capture + W steps, state rewound) and the timed region
-    elapsed, all_elapsed = decode_leg(ctx, model, runner, ctxs, args.warmup, prompt_len)
+    elapsed, all_elapsed = decode_leg(ctx, model, runner, passes, args.warmup, prompt_len,
+                                      regions=TIMED_REGIONS if args.full else 1)
     ms_per_step = elapsed / steps * 1e3
     tokens = args.batch * steps * n_gpus
     value = tokens / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(runner, args.dump_outputs)
+    configs_i = {"7b": "configs[1]: LLaVA-1.5-7B bf16, collocated prefill+decode on 1 MI355X",
+                 "13b": "configs[2]: LLaVA-1.5-13B, batch 32, decode HBM-roofline run"}.get(args.model, "smoke shape")
+    headline = {
+        "metric": "decode output tokens/s, LLaVA-1.5-7B image+text requests (576 image + 128 text "
+                  "prompt, 256 generated), batch 32 per GPU" if args.model == "7b" else
+                  f"decode output tokens/s, {model_name}, batch {args.batch} per GPU",
+        "value": round(value, 2), "unit": "tokens/s", "n_gpus": n_gpus, "steps": steps,
+        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), **region_spread(all_elapsed, steps),
+        "timing": (f"{len(all_elapsed)} timed regions of exactly {steps} steps each behind one warm-up, every one bracketed by "
+                   "barrier + synchronize and reduced with MAX over ranks; value and ms_per_step are the MEDIAN region's"
+                   if len(all_elapsed) > 1 else
+                   f"one timed region of exactly {steps} steps behind the warm-up, bracketed by barrier + synchronize and "
+                   "reduced with MAX over ranks"),
+        "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+        "config": {"workload": f"{model_name}-shaped random weights, batch {args.batch} "
+                               f"decode, paged KV block_size=16, {ctx_label(ctxs, passes)} (BASELINE {configs_i})",
+                   "global_batch": args.batch * n_gpus, "prompt_tokens": prompt_len,
+                   "generated_tokens": n_generate,
+                   "hip_graph": cfg.use_graph and runner.executor_used == "graph",
+                   # the executor that REALLY replayed the step (a plan falls back to the hipGraph when the step
+                   # holds torch ops, e.g. --lib-gemm: launch_plan.PlanNotRecordable)
+                   "step_executor": runner.executor_used if cfg.use_graph else "eager",
+                   "parallelism": f"replicas x{n_gpus} (independent requests, no data-path collective)"},
+    }
+    if not args.full:      # a plain run ends with its headline
+        if rank == 0:
+            print(json.dumps(headline), flush=True)
+        ctx.shutdown()
+        return
 
     # The prefill side of the TTFT and serving legs is library GEMM (82 % of a single request's TTFT, 24 of the 29 ms of a
     # 2048-token chunk): an engine tunes the four projections for its configured prompt length and chunk budget ONCE at
@@ -1663,27 +1763,8 @@ def main():
                 whole_ragged = {"error": repr(e)[:300]}
         roofline["measured_read_stream_ceiling_GBps"] = stream_rates[0]      # (measured before the model was built)
         roofline["measured_copy_GBps"] = stream_rates[1]     # torch copy_ (read + write): NOT a ceiling
-        configs_i = {"7b": "configs[1]: LLaVA-1.5-7B bf16, collocated prefill+decode on 1 MI355X",
-                     "13b": "configs[2]: LLaVA-1.5-13B, batch 32, decode HBM-roofline run"}.get(args.model, "smoke shape")
         out = {
-            "metric": "decode output tokens/s, LLaVA-1.5-7B image+text requests (576 image + 128 text "
-                      "prompt, 256 generated), batch 32 per GPU" if args.model == "7b" else
-                      f"decode output tokens/s, {model_name}, batch {args.batch} per GPU",
-            "value": round(value, 2), "unit": "tokens/s", "n_gpus": n_gpus, "steps": steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), **region_spread(all_elapsed, steps),
-            "timing": f"{TIMED_REGIONS} timed regions of exactly {steps} steps each behind one warm-up, every one bracketed by barrier + "
-                      "synchronize and reduced with MAX over ranks; value and ms_per_step are the MEDIAN region's",
-            "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-            "config": {"workload": f"{model_name}-shaped random weights, batch {args.batch} "
-                                   f"decode, paged KV block_size=16, {ctx_label(ctxs)} (BASELINE {configs_i})",
-                       "global_batch": args.batch * n_gpus, "prompt_tokens": prompt_len,
-                       "generated_tokens": n_generate,
-                       "hip_graph": cfg.use_graph and runner.executor_used == "graph",
-                       # the executor that REALLY replayed the step (a plan falls back to the hipGraph when the step
-                       # holds torch ops, e.g. --lib-gemm: launch_plan.PlanNotRecordable)
-                       "step_executor": runner.executor_used if cfg.use_graph else "eager",
-                       "parallelism": f"replicas x{n_gpus} (independent requests, no data-path collective)"},
+            **headline,
             "roofline": roofline,
             "roofline_gemm": roofline_gemm,
             "roofline_prefill_attention": None if args.skip_prefill else prefill_attention_object(shape, dtype, dev),

@@ -109,7 +109,7 @@ def test_bench_two_ranks_on_two_devices_over_rccl():
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "HX_SINGLE_DEVICE", "HX_DIST_BACKEND")}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--model", "tiny", "--batch", "8",
-                        "--steps", "8", "--warmup", "2", "--rate", "40", "--no-cpu-baseline", "--no-13b"],
+                        "--steps", "8", "--warmup", "2", "--rate", "40", "--full", "--no-cpu-baseline", "--no-13b"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

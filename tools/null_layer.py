@@ -31,7 +31,7 @@ ctx = parallel.init_from_env()
 runner.input_ids.copy_(torch.randint(1000, 30000, (32,), device=dev))
 built, null, best = [], [], []
 for r in range(a.rounds):
-    el = bench.decode_leg(ctx, model, runner, ctxs, 2, 704)
+    el, _ = bench.decode_leg(ctx, model, runner, [ctxs], 2, 704)
     ms = el / len(ctxs) * 1e3
     o = bench.null_step_object(model, runner, ctxs, ms, reps=3)
     built.append(ms); null.append(o["ms_per_step"]); best.append(o["null_step_best_grid_ms"])

@@ -3,7 +3,7 @@
 VAR=$1; A=$2; B=$3; REPS=${4:-4}; shift 4 || true
 for rep in $(seq $REPS); do
 for val in $A $B; do
-  env $VAR=$val python bench.py --steps 20 --warmup 5 --no-ttft --no-cpu-baseline --no-serving --no-null-step "$@" 2>/dev/null | python -c "
+  env $VAR=$val python bench.py --full --steps 20 --warmup 5 --no-ttft --no-cpu-baseline --no-serving --no-null-step "$@" 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); l=d.get('llava_13b') or {'ms_per_step':0,'whole_step_64':{'ms_per_step':0}}
 print('$VAR[$val]', d['ms_per_step'], d['whole_step_64']['ms_per_step'], d['whole_step_64']['launches_per_layer'], l['ms_per_step'], l['whole_step_64']['ms_per_step'])"
 done

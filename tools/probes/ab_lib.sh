@@ -4,7 +4,7 @@ REPS=${1:-4}; shift || true
 for rep in $(seq $REPS); do
 for which in before after; do
   if [ $which = before ]; then export HX_LIB_PATH=$PWD/build/lib_before/libhydra_hip.so; else unset HX_LIB_PATH; fi
-  python bench.py --steps 20 --warmup 5 --no-ttft --no-cpu-baseline --no-serving --no-null-step "$@" 2>/dev/null | python -c "
+  python bench.py --full --steps 20 --warmup 5 --no-ttft --no-cpu-baseline --no-serving --no-null-step "$@" 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); l=d.get('llava_13b') or {'ms_per_step':0,'whole_step_64':{'ms_per_step':0}}
 print('LIB[$which]', d['ms_per_step'], d['whole_step_64']['ms_per_step'], l['ms_per_step'], l['whole_step_64']['ms_per_step'])"
 done

@@ -4,7 +4,7 @@ OPT=$1; REPS=${2:-4}; shift; shift || true
 for rep in $(seq $REPS); do
 for which in off on; do
   if [ $which = on ]; then export HX_DEBUG_OPTIONS=$OPT; else unset HX_DEBUG_OPTIONS; fi
-  python bench.py --steps 20 --warmup 5 --no-ttft --no-cpu-baseline --no-serving --no-null-step "$@" 2>/dev/null | python -c "
+  python bench.py --full --steps 20 --warmup 5 --no-ttft --no-cpu-baseline --no-serving --no-null-step "$@" 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); l=d.get('llava_13b') or {'ms_per_step':0,'whole_step_64':{'ms_per_step':0}}
 print('OPT[$which]', d['ms_per_step'], d['whole_step_64']['ms_per_step'], l['ms_per_step'], l['whole_step_64']['ms_per_step'], d['roofline']['avg_launch_us'])"
 done

@@ -4,7 +4,7 @@
 REPS=${1:-4}; shift || true
 for rep in $(seq $REPS); do
 for skew in 0 256 768 4352; do
-  HX_KV_POOL_SKEW=$skew python bench.py --steps 20 --warmup 5 --no-ttft --no-cpu-baseline --no-serving --no-null-step "$@" 2>/dev/null | python -c "
+  HX_KV_POOL_SKEW=$skew python bench.py --full --steps 20 --warmup 5 --no-ttft --no-cpu-baseline --no-serving --no-null-step "$@" 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); l=d.get('llava_13b') or {'ms_per_step':0,'whole_step_64':{'ms_per_step':0}}
 print('SKEW[$skew]', d['ms_per_step'], d['whole_step_64']['ms_per_step'], l['ms_per_step'], l['whole_step_64']['ms_per_step'])"
 done

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:?set GRAFT_REPO_ROOT (gpurun exports it)}
 OUT=$R/gpurun_out/${ROUND:-r6}
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-F="--steps 20 --no-cpu-baseline --no-serving --no-ttft --no-null-step --no-ragged"
+F="--full --steps 20 --no-cpu-baseline --no-serving --no-ttft --no-null-step --no-ragged"
 rm -rf /tmp/p13a /tmp/p13b
 rocprofv3 --kernel-trace --output-format csv -d /tmp/p13a -- python3 "$R/bench.py" $F --model 13b > "$OUT/13b_alone.json" 2>/dev/null
 rocprofv3 --kernel-trace --output-format csv -d /tmp/p13b -- python3 "$R/bench.py" $F > "$OUT/13b_after7b.json" 2>/dev/null

@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 D=/tmp/prof_$TAG
 rm -rf "$D"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$D" -- python3 "$R/bench.py" --steps 64 --warmup 3 \
+rocprofv3 --kernel-trace --stats --output-format csv -d "$D" -- python3 "$R/bench.py" --full --steps 64 --warmup 3 \
     --no-cpu-baseline --no-serving --no-ttft --no-13b "$@" > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err" || { tail -5 "$OUT/${TAG}_bench.err"; exit 1; }
 python3 "$R/tools/layer_timeline.py" "$D" "$OUT/${TAG}_timeline.md" "$OUT/${TAG}_in_step.json" > /dev/null
 cp "$(find "$D" -name '*kernel_stats.csv' | head -1)" "$OUT/${TAG}_kernel_stats.csv"
