@@ -25,7 +25,7 @@ def mha_varlen_fwd(out: Tensor, q: Tensor, k: Tensor, v: Tensor, cu_seqlens_q: T
                    cu_block_lens: Optional[Tensor], alibi_slopes: Optional[Tensor],
                    max_seqlen_q: int, max_seqlen_k: int, softmax_scale: float, softcap: float,
                    window_size_left: int, window_size_right: int, num_splits: int) -> None:
-    _lib.require_gpu(out, q, k, v, cu_seqlens_q, cu_seqlens_k, block_table_, cu_block_lens)
+    _lib.require_gpu(out, q, k, v, cu_seqlens_q, cu_seqlens_k, block_table_, cu_block_lens, alibi_slopes)
     if q.dtype not in (torch.float16, torch.bfloat16):
         raise _lib.HydraHipError("FlashAttention only support fp16 and bf16 data type")
     if k.dtype != q.dtype or v.dtype != q.dtype or out.dtype != q.dtype:
@@ -39,8 +39,13 @@ def mha_varlen_fwd(out: Tensor, q: Tensor, k: Tensor, v: Tensor, cu_seqlens_q: T
         raise _lib.HydraHipError("q/out must be [n_tokens, n_heads, head_dim]")
     if q.stride(1) != q.size(2) or out.stride(1) != out.size(2):
         raise _lib.HydraHipError("q/out heads must be contiguous")
-    if alibi_slopes is not None:
-        raise _lib.HydraHipError("alibi_slopes is not supported by the MI355X implementation")
+    if alibi_slopes is not None:      # flash_api.cpp:197-214
+        if alibi_slopes.dtype != torch.float32:
+            raise _lib.HydraHipError("ALiBi slopes must have dtype fp32")
+        if alibi_slopes.device != q.device:
+            raise _lib.HydraHipError("ALiBi slopes must be on the same device as q")
+        if alibi_slopes.dim() not in (1, 2) or alibi_slopes.stride(-1) != 1:
+            raise _lib.HydraHipError("ALiBi slopes must have contiguous last dimension")
     if softcap < 0:
         raise _lib.HydraHipError("softcap must be >= 0")
     # flash_api.cpp:99-107: causal iff window (-1, 0); full iff (-1, -1); anything else is local
@@ -103,6 +108,12 @@ def mha_varlen_fwd(out: Tensor, q: Tensor, k: Tensor, v: Tensor, cu_seqlens_q: T
     a.window_left = int(window_size_left) if local else -1
     a.window_right = int(window_size_right) if local else -1
     a.flags = _lib.HX_ATTN_LOCAL_WINDOW if local else 0
+    if alibi_slopes is not None:
+        if tuple(alibi_slopes.shape) not in ((n_heads,), (batch, n_heads)):
+            raise _lib.HydraHipError(f"ALiBi slopes must have shape [{n_heads}] or [{batch}, {n_heads}]")
+        a.alibi_slopes = alibi_slopes.data_ptr()
+        a.alibi_batch_stride = alibi_slopes.stride(0) if alibi_slopes.dim() == 2 else 0
+        a.flags |= _lib.HX_ATTN_ALIBI
 
     l = _lib.lib()
     need = l.hx_mha_varlen_fwd_workspace_bytes(ctypes.byref(a))

@@ -20,6 +20,7 @@ HX_F32, HX_F16, HX_BF16 = 0, 1, 2
 HX_IPC_HANDLE_BYTES = 64
 HX_ABI_VERSION = 3            # include/hydra_hip.h
 HX_ATTN_LOCAL_WINDOW = 1
+HX_ATTN_ALIBI = 2
 
 _DTYPE = {torch.float32: HX_F32, torch.float16: HX_F16, torch.bfloat16: HX_BF16}
 
@@ -43,6 +44,7 @@ class hx_attn_args(ctypes.Structure):
         ("softmax_scale", c_float), ("causal", c_int32), ("dtype", c_int32),
         ("num_splits", c_int32), ("workspace", c_void_p), ("workspace_bytes", c_int64),
         ("softcap", c_float), ("window_left", c_int32), ("window_right", c_int32), ("flags", c_int32),
+        ("alibi_slopes", c_void_p), ("alibi_batch_stride", c_int64),
     ]
 
 

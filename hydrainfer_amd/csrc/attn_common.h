@@ -90,6 +90,16 @@ struct AttnParams {
   int64_t qkv_slab_stride;  // batch * row length
   int64_t qkv_row;          // (n_heads + 2*n_kv_heads) * D
   const int32_t* rank_desc; // decode kernel, RANKED form: [0] ragged?, [1 + r] the sequence with the r-th most keys (null: static grid)
+  // ALiBi (appended last: the offsets of everything above are what they were).  score(i, j) -= slope[b, h] * |i + lk - lq - j|,
+  // added after the soft cap, before the masks; read only by attn_decode_alibi_kernel, attn_decode_gqa_alibi_kernel and
+  // attn_fwd_kernel
+  const float* alibi;       // fp32 [n_heads] or [batch, n_heads] on the device; null = off
+  int64_t alibi_batch_stride;   // elements between two sequences' slope vectors; 0 = one vector for all
 };
+
+// ALiBi slope of (sequence b, head h) in the log2 domain of the kernels' exponentials: one scalar load per workgroup
+__device__ __forceinline__ float alibi_slope_log2(const AttnParams& p, int b, int h) {
+  return p.alibi[(int64_t)b * p.alibi_batch_stride + h] * 1.4426950408889634f;
+}
 
 }  // namespace hx

@@ -221,7 +221,18 @@ static int attn_dispatch(const hx_attn_args* a, const hx_fused_decode_args* fuse
 #endif
   p.scale_log2 = a->softmax_scale * 1.4426950408889634f;
   // flash_api.cpp:93-111
-  if (a->flags & ~HX_ATTN_LOCAL_WINDOW) return HX_ERR_UNSUPPORTED;
+  if (a->flags & ~(HX_ATTN_LOCAL_WINDOW | HX_ATTN_ALIBI)) return HX_ERR_UNSUPPORTED;
+  // ALiBi (flash_api.cpp:197-214): fp32 slopes [n_heads] or [batch, n_heads]; the tail fields count only with the flag
+  p.alibi = nullptr;
+  p.alibi_batch_stride = 0;
+  if (a->flags & HX_ATTN_ALIBI) {
+    if (fused) return HX_ERR_UNSUPPORTED;      // that entry fuses RoPE, and ALiBi models have none
+    if (!a->alibi_slopes) return HX_ERR_NULL;
+    if (reinterpret_cast<uintptr_t>(a->alibi_slopes) & 3u) return HX_ERR_STRIDE;
+    if (a->alibi_batch_stride < 0 || !(a->softmax_scale > 0.f)) return HX_ERR_SHAPE;
+    p.alibi = a->alibi_slopes;
+    p.alibi_batch_stride = a->alibi_batch_stride;
+  }
   const bool local = is_local(a);
   p.window_left = local ? a->window_left : -1;
   p.window_right = local ? a->window_right : -1;
@@ -287,8 +298,8 @@ static int attn_dispatch(const hx_attn_args* a, const hx_fused_decode_args* fuse
     p.n_splits = splits;
     if (gqa) return launch_attn_decode_gqa(p, a->batch, a->head_dim, a->dtype, s);
 #if HX_EXPERIMENTS
-    // four heads per workgroup (1 KiB contiguous per key row) when the grid still fills the chip
-    if (decode4_applies(p, a->batch, a->head_dim, device_cus())) return launch_attn_decode4(p, a->batch, a->dtype, s);
+    // four heads per workgroup (1 KiB contiguous per key row) when the grid still fills the chip; never for an ALiBi call
+    if (!p.alibi && decode4_applies(p, a->batch, a->head_dim, device_cus())) return launch_attn_decode4(p, a->batch, a->dtype, s);
 #endif
     return launch_attn_decode(p, a->batch, a->head_dim, a->dtype, s);
   }

@@ -124,6 +124,9 @@ class CausalGroupedQueryPageAttentionConfig:
     n_qo_heads: int
     n_kv_heads: int
     head_dim: int
+    # ALiBi (BLOOM / MPT / Baichuan-13B: no rotary embedding): fp32 device tensor [n_qo_heads] or [batch, n_qo_heads]
+    # (hydrainfer_amd.layer.alibi.alibi_slopes); None = no bias
+    alibi_slopes: Optional[Tensor] = None
 
 
 @dataclass
@@ -138,6 +141,7 @@ class CausalGroupedQueryPageAttention(nn.Module):
         self.n_qo_heads = config.n_qo_heads
         self.n_kv_heads = config.n_kv_heads
         self.head_dim = config.head_dim
+        self.alibi_slopes = config.alibi_slopes
 
     def forward(self, query: Tensor, key: Tensor, value: Tensor,
                 attention_params: AttentionParameters) -> CausalGroupedQueryPageAttentionOutput:
@@ -153,6 +157,6 @@ class CausalGroupedQueryPageAttention(nn.Module):
                              device=query.device)
         mha_varlen_fwd(output, query, key_cache, value_cache, attention_params.q_cu_seq_lens,
                        attention_params.kv_cu_seq_lens, attention_params.block_tables,
-                       attention_params.cu_blocks_lens, None, attention_params.q_max_seq_len,
+                       attention_params.cu_blocks_lens, self.alibi_slopes, attention_params.q_max_seq_len,
                        attention_params.kv_max_seq_len, 1.0 / math.sqrt(self.head_dim), 0, -1, 0, 0)
         return CausalGroupedQueryPageAttentionOutput(o=output.view(n_tokens, self.n_qo_heads * self.head_dim))

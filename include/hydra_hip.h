@@ -337,8 +337,8 @@ int hx_silu_and_mul_slabs_ex(void* out, const float* partial, int32_t n_splits, 
  * cu_seqlens_q / cu_seqlens_k: int32 [batch+1] (device).
  * causal != 0: key j visible to query i iff j <= i + (kv_len - q_len)
  *          (bottom-right aligned; reference mask.h:173-193, window (-1,0)).
- * softcap and local windows: see the tail of hx_attn_args (flags & HX_ATTN_LOCAL_WINDOW).
- * Unsupported reference feature (HX_ERR_UNSUPPORTED): alibi slopes.
+ * softcap, local windows and ALiBi slopes: see the tail of hx_attn_args (flags & HX_ATTN_LOCAL_WINDOW,
+ *          flags & HX_ATTN_ALIBI).
  * workspace: device scratch of at least hx_mha_varlen_fwd_workspace_bytes() bytes
  * (used for split-KV partials; may be NULL when that returns 0).
  * ---------------------------------------------------------------------- */
@@ -379,8 +379,22 @@ typedef struct hx_attn_args {
   int32_t window_left;
   int32_t window_right;
   int32_t flags;         /* HX_ATTN_* bits; unknown bits -> HX_ERR_UNSUPPORTED */
+  /* ALiBi (flash_api.cpp:197-214), read only when flags & HX_ATTN_ALIBI: fp32 slopes on the device, [n_heads]
+   * (alibi_batch_stride = 0) or [batch, n_heads] (alibi_batch_stride = elements between two sequences' vectors,
+   * >= 0); the pointer must be 4-byte aligned and softmax_scale > 0.  Sequence b, head h, query row i (of q_len rows)
+   * and key j (of kv_len keys):
+   *   score(i, j) = f(q_i.k_j * softmax_scale) - alibi_slopes[b * alibi_batch_stride + h] * |i + kv_len - q_len - j|
+   * with f the soft cap above (or the identity): the bias is added after the cap and before the masks.  Under a
+   * causal mask the reference adds slope * j instead (mask.h:157-158), a constant per row apart: the same softmax.
+   * hx_decode_attention_fused answers the flag with HX_ERR_UNSUPPORTED (it fuses RoPE; ALiBi models have none).
+   * These two fields were appended WITHOUT raising HX_ABI_VERSION (still 3): a zero-filled tail keeps meaning "off",
+   * and a caller detects the feature by the flag itself — a library built before it answers the unknown flag bit
+   * with HX_ERR_UNSUPPORTED and never reads past `flags`. */
+  const float* alibi_slopes;
+  int64_t alibi_batch_stride;
 } hx_attn_args;
 #define HX_ATTN_LOCAL_WINDOW 1
+#define HX_ATTN_ALIBI 2
 
 int64_t hx_mha_varlen_fwd_workspace_bytes(const hx_attn_args* args);
 int hx_mha_varlen_fwd(const hx_attn_args* args, hx_stream stream);
