@@ -21,6 +21,7 @@ HX_IPC_HANDLE_BYTES = 64
 HX_ABI_VERSION = 3            # include/hydra_hip.h
 HX_ATTN_LOCAL_WINDOW = 1
 HX_ATTN_ALIBI = 2
+HX_FOCAL_RANK, HX_FOCAL_ROW = 0, 1
 
 _DTYPE = {torch.float32: HX_F32, torch.float16: HX_F16, torch.bfloat16: HX_BF16}
 
@@ -165,6 +166,10 @@ _SIGNATURES = {
     "hx_measure_read_stream": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "hx_measure_read_grid": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "hx_measure_paged_read": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int64, c_int64, c_int, c_void_p, c_void_p]),
+    "hx_focal_significance_workspace_bytes": (c_int64, [c_int64] * 3),
+    "hx_focal_significance": (c_int, [c_void_p] * 4 + [c_int64] * 7 + [c_float, c_void_p, c_int64, c_int, c_void_p]),
+    "hx_focal_select": (c_int, [c_void_p] * 4 + [c_int64] * 2 + [c_int, c_void_p]),
+    "hx_focal_gather": (c_int, [c_void_p] * 4 + [c_int64] * 5 + [c_int, c_void_p]),
 }
 
 # Only in a library built with `make EXPERIMENTS=1` (include/hydra_hip_experimental.h): rejected experiments and

@@ -7,7 +7,7 @@ from hydrainfer_amd.engine.isa import (EmptyInstruction, EPMigrate, Fill, ImageE
                                        MigrateRequest, PDMigrate, PullCache, TextFill)
 from hydrainfer_amd.engine.rcb import (BatchRequest, LogOutputTokenProcessor, OutputTokenProcessor,
                                        RequestControlBlock, RequestMetaData, RequestMetric,
-                                       SamplingParameters, ScenarioClassifier, ScenarioType)
+                                       SamplingParameters, ScenarioClassifier, ScenarioType, TokenParameters)
 from hydrainfer_amd.engine.scheduler import (BatchScheduler, BatchSchedulerConfig, BatchSchedulerContext,
                                              BatchSchedulerMetrics)
 from hydrainfer_amd.engine.request_processor import InstructionCreator, TokenRequest

@@ -347,27 +347,34 @@ class BatchImageEmbedExecutor:
         self.n_qo_heads, self.head_dim = n_qo_heads, head_dim
         self.dtype, self.device = dtype, device
         self.use_graphs = use_graphs and device.type == "cuda"
-        self.graphs = {}       # n_images -> (graph, static pixel buffer, static output)
+        self.graphs = {}       # n_images (or (n_images, strategy) for the pruning forward) -> (graph, static inputs, static output)
         self._stages = {}      # (n_images, shape, dtype) -> [(pinned staging buffer, event behind its last copy), ...]
 
-    def _encode(self, pixels: torch.Tensor) -> torch.Tensor:
+    def _encode(self, pixels: torch.Tensor, n_keep: Optional[torch.Tensor] = None, strategy: str = "rank") -> torch.Tensor:
+        """n_keep: None, or the per-image kept counts (int32, on the device): the pruning forward, whose graph takes the
+        counts as a second static input — one graph per image count serves every mix of counts."""
+        extra = () if n_keep is None else (n_keep, strategy)
         if not self.use_graphs or torch.cuda.is_current_stream_capturing():
-            return self.vision_model.forward(pixels)
+            return self.vision_model.forward(pixels, *extra)
         n = pixels.shape[0]
-        entry = self.graphs.get(n)
+        key = n if n_keep is None else (n, strategy)
+        entry = self.graphs.get(key)
         if entry is None:
             static_in = pixels.clone()
+            static_extra = () if n_keep is None else (n_keep.clone(), strategy)
             side = torch.cuda.Stream(device=self.device)
             side.wait_stream(torch.cuda.current_stream(self.device))
             with torch.cuda.stream(side):
-                self.vision_model.forward(static_in)          # warm-up outside capture
+                self.vision_model.forward(static_in, *static_extra)          # warm-up outside capture
             torch.cuda.current_stream(self.device).wait_stream(side)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                static_out = self.vision_model.forward(static_in)
-            entry = self.graphs[n] = (graph, static_in, static_out)
-        graph, static_in, static_out = entry
-        static_in.copy_(pixels)
+                static_out = self.vision_model.forward(static_in, *static_extra)
+            entry = self.graphs[key] = (graph, (static_in,) + static_extra[:1], static_out)
+        graph, static_ins, static_out = entry
+        static_ins[0].copy_(pixels)
+        if n_keep is not None:
+            static_ins[1].copy_(n_keep)
         graph.replay()
         return static_out          # consumed (scattered into the image cache) before the next replay: same stream
 
@@ -414,15 +421,39 @@ class BatchImageEmbedExecutor:
             return
         slots: List[int] = []
         pixels = []
+        counts: List[Optional[int]] = []
+        strategies = set()
         for rcb, inst in batch:
             pixels.append(inst.pixel_values)
             inst.pixel_values = None
             slots += self.manager.v2p(rcb.virtual_image_cache, inst.cache_ids)
-        feats = self._encode(self._upload(pixels))                      # (n_img, 576, hidden)
-        tokens = feats.reshape(-1, self.n_qo_heads, self.head_dim)
-        slot_t = torch.tensor(slots, dtype=torch.int32)
+            n_keep = getattr(inst, "n_keep", None)
+            counts += [n_keep] * pixels[-1].shape[0]
+            if n_keep is not None:
+                strategies.add(inst.strategy)
+        if not strategies:
+            feats = self._encode(self._upload(pixels))                      # (n_img, 576, hidden)
+            tokens = feats.reshape(-1, self.n_qo_heads, self.head_dim)
+            ints = slots
+        else:
+            # focal token pruning (layer/token_prunning.py): an image that keeps every token rides along with n = all of
+            # them (the identity selection), so one forward serves the mixed batch.  Only the kept rows — the first n of
+            # each image's block of the padded output — go to the image cache, into the first n slots of its block.
+            if len(strategies) > 1:
+                raise ValueError(f"one image-embed batch mixes pruning strategies {sorted(strategies)}")
+            n_patches = (self.vision_model.shape.image_size // self.vision_model.shape.patch_size) ** 2
+            counts = [n_patches if c is None else c for c in counts]
+            rows = [b * n_patches + r for b, c in enumerate(counts) for r in range(c)]
+            assert len(rows) == len(slots), "kept image tokens and image cache slots differ"
+            ints = slots + rows + counts
+        slot_t = torch.tensor(ints, dtype=torch.int32)
         if self.device.type == "cuda":
             slot_t = slot_t.pin_memory().to(self.device, non_blocking=True)
+        if strategies:
+            n_rows = len(slots)
+            slot_t, row_t, keep_t = slot_t[:n_rows], slot_t[n_rows:2 * n_rows], slot_t[2 * n_rows:]
+            feats = self._encode(self._upload(pixels), keep_t.contiguous(), strategies.pop())
+            tokens = feats.reshape(-1, feats.shape[-1]).index_select(0, row_t).reshape(-1, self.n_qo_heads, self.head_dim)
         self.manager.get_layer_cache(layer_id=0).set_caches(slot_t, [tokens])
         batch.step()
 

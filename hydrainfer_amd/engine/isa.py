@@ -92,11 +92,15 @@ class ImageEmbedFill(Fill):
 
 class ImageEmbed(Instruction):
     def __init__(self, pixel_values, cache_ids: List[int], images_size: List[Tuple[int, int]],
-                 hashes: Optional[List[int]]):
+                 hashes: Optional[List[int]], n_keep: Optional[int] = None, strategy: str = "rank"):
         self.pixel_values = pixel_values
         self.cache_ids = cache_ids
         self.images_size = images_size
         self.hashes = hashes
+        # focal token pruning (layer/token_prunning.py): the image yields n_keep == len(cache_ids) embeddings instead of
+        # one per patch; None = every patch token
+        self.n_keep = n_keep
+        self.strategy = strategy
 
     def __repr__(self):
         return "IE"

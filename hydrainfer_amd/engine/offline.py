@@ -8,7 +8,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from hydrainfer_amd.engine.node import LocalCluster
-from hydrainfer_amd.engine.rcb import SamplingParameters
+from hydrainfer_amd.engine.rcb import SamplingParameters, TokenParameters
 from hydrainfer_amd.engine.request_processor import InstructionCreator, TokenRequest
 from hydrainfer_amd.engine.scheduler import BatchSchedulerConfig
 from hydrainfer_amd.engine.serve import build_node, quiet_gc, warm_library_gemms
@@ -32,6 +32,7 @@ class OfflineRequest:
     image: object = None          # PIL image or None
     max_tokens: int = 50
     eos_token_ids: Sequence[int] = ()
+    token_params: Optional[TokenParameters] = None     # token_pruning_policy='focal': the image as n_embed_output_tokens tokens
 
 
 class OfflineInferenceEngine:
@@ -76,7 +77,8 @@ class OfflineInferenceEngine:
                 req = TokenRequest(request_id=i, token_ids=list(r.token_ids), pixel_values=pixels,
                                    image_size=(r.image.size[1], r.image.size[0]) if r.image is not None else (0, 0),
                                    image_hash=compute_image_hash(r.image) if r.image is not None else 0,
-                                   sampling_params=SamplingParameters(r.max_tokens, list(r.eos_token_ids)))
+                                   sampling_params=SamplingParameters(r.max_tokens, list(r.eos_token_ids)),
+                                   token_params=r.token_params)
                 rcb = self.creator.process(req)
                 rcb.metric.arrival_time = time.perf_counter()
                 rcbs.append(rcb)

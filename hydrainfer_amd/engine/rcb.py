@@ -16,6 +16,18 @@ class SamplingParameters:
 
 
 @dataclass
+class TokenParameters:
+    """hydrainfer/request/request.py:13-18, field for field.  Implemented: token_pruning_policy = 'focal' (the request's
+    image enters the prompt as n_embed_output_tokens tokens chosen by layer/token_prunning.py instead of all of them).
+    Declared only: the KV-cache eviction policies — InstructionCreator.process refuses anything but None."""
+    kv_cache_eviction_policy: Optional[str] = None     # None | 'random' | 'streamingllm'
+    window_size: int = 28
+    attention_sink_size: int = 4
+    token_pruning_policy: Optional[str] = None         # None | 'focal'
+    n_embed_output_tokens: int = 64
+
+
+@dataclass
 class RequestMetaData:
     n_images: int
     n_prompt_tokens: int

@@ -2,12 +2,14 @@
 (InstructionCreator) without the tokenizer / image processor (the caller passes token ids and
 pre-processed pixel values; there are no checkpoints or tokenizers offline)."""
 from dataclasses import dataclass
-from typing import List, Tuple
+from typing import List, Optional, Tuple
+
+import xxhash
 
 from hydrainfer_amd.engine.isa import (EPMigrate, ImageEmbed, ImageEmbedFill, InstructionListBuilder,
                                        PDMigrate, PullCache, TextFill)
 from hydrainfer_amd.engine.rcb import (RequestControlBlock, RequestMetaData, SamplingParameters,
-                                       ScenarioClassifier)
+                                       ScenarioClassifier, TokenParameters)
 from hydrainfer_amd.memory.shared_cache import compute_hash
 
 
@@ -20,12 +22,27 @@ class TokenRequest:
     image_size: Tuple[int, int] = (336, 336)   # (height, width) of the original image
     image_hash: int = 0
     sampling_params: SamplingParameters = None
+    token_params: Optional[TokenParameters] = None     # None: every image token, no pruning
+
+
+def pruned_image_hash(image_hash: int, n_tokens: int, strategy: str) -> int:
+    """What stands in for a PRUNED image in the prefix-cache block hashes and in ImageEmbed.hashes: a function of (image
+    hash, kept count, strategy).  The KV of a block of image placeholders depends on which tokens were kept, so it must
+    not share a hash with the unpruned prompt of the same image (whose stand-in stays the image hash itself).  63 bits:
+    exact as an int64 beside the token ids."""
+    h = xxhash.xxh64()
+    h.update(b"focal")
+    h.update(int(image_hash).to_bytes(16, "little", signed=True))
+    h.update(int(n_tokens).to_bytes(8, "little"))
+    h.update(strategy.encode())
+    return h.intdigest() >> 1
 
 
 class InstructionCreator:
     def __init__(self, image_token_id: int = 32000, n_image_tokens_per_image: int = 576,
                  block_size: int = 16, ignore_eos: bool = True, eos_token_id: int = 2,
-                 max_position_embeddings: int = 4096):
+                 max_position_embeddings: int = 4096, pruning_strategy: str = "rank"):
+        self.pruning_strategy = pruning_strategy       # 'rank' | 'row' (layer/token_prunning.py) for 'focal' requests
         self.max_position_embeddings = max_position_embeddings
         self.image_token_id = image_token_id
         self.n_image_tokens_per_image = n_image_tokens_per_image
@@ -33,15 +50,38 @@ class InstructionCreator:
         self.ignore_eos, self.eos_token_id = ignore_eos, eos_token_id
         self.scenario_classifier = ScenarioClassifier()
 
-    def _insert_image_tokens(self, token_ids: List[int], image_hashes: List[int]):
+    def _pruned_count(self, request: TokenRequest) -> Optional[int]:
+        """The request's image-token count under its token_params, None = unpruned.  What the reference declares and
+        this engine does not implement is refused here, not ignored."""
+        tp = request.token_params
+        if tp is None:
+            return None
+        if tp.kv_cache_eviction_policy is not None:
+            raise ValueError(f"request {request.request_id}: kv_cache_eviction_policy {tp.kv_cache_eviction_policy!r} is "
+                             "declared by the request type but not implemented (only None)")
+        if tp.token_pruning_policy is None:
+            return None
+        if tp.token_pruning_policy != "focal":
+            raise ValueError(f"request {request.request_id}: unknown token_pruning_policy {tp.token_pruning_policy!r} "
+                             "(None or 'focal')")
+        n, full = tp.n_embed_output_tokens, self.n_image_tokens_per_image
+        if not isinstance(n, int) or not 1 <= n <= full:
+            raise ValueError(f"request {request.request_id}: n_embed_output_tokens {n!r} outside 1..{full}")
+        if request.pixel_values is not None:
+            from hydrainfer_amd.layer.token_prunning import check_counts
+            check_counts([n], full, self.pruning_strategy)
+        return n
+
+    def _insert_image_tokens(self, token_ids: List[int], image_hashes: List[int], n_per_image: Optional[int] = None):
         """Each image placeholder becomes n_image_tokens placeholders; the prefix hashes are taken
         over the prompt with the image's content hash standing in for the inserted placeholders
-        (request_processor.py:64-81: the LAST placeholder keeps the token id itself)."""
+        (request_processor.py:64-81: the LAST placeholder keeps the token id itself).  n_per_image: a pruned
+        image's count; image_hashes then already are the pruned stand-ins."""
         out, to_hash, image_id, total = [], [], -1, 0
         for t in token_ids:
             if t == self.image_token_id:
                 image_id += 1
-                n = self.n_image_tokens_per_image
+                n = self.n_image_tokens_per_image if n_per_image is None else n_per_image
                 total += n
                 out.extend([self.image_token_id] * (n - 1))
                 to_hash.extend([image_hashes[image_id]] * (n - 1))
@@ -58,9 +98,14 @@ class InstructionCreator:
             rcb.sampling_params.eos_token_ids.append(self.eos_token_id)
 
         has_image = request.pixel_values is not None
+        n_keep = self._pruned_count(request)
+        if not has_image:
+            n_keep = None
         image_hashes = [request.image_hash] if has_image else []
+        if n_keep is not None:
+            image_hashes = [pruned_image_hash(h, n_keep, self.pruning_strategy) for h in image_hashes]
         n_images = request.token_ids.count(self.image_token_id)
-        hashes, token_ids, n_image_tokens = self._insert_image_tokens(request.token_ids, image_hashes)
+        hashes, token_ids, n_image_tokens = self._insert_image_tokens(request.token_ids, image_hashes, n_keep)
         n_prompt = len(token_ids)
         # position ids run to n_prompt + max_tokens - 2; the rotary table (cos_sin) has
         # max_position_embeddings rows and the kernels index it unchecked
@@ -75,7 +120,8 @@ class InstructionCreator:
         b = InstructionListBuilder()
         if has_image:
             image_cache_ids = list(range(n_image_tokens))
-            b.append(ImageEmbed(request.pixel_values, image_cache_ids, [request.image_size], image_hashes))
+            b.append(ImageEmbed(request.pixel_values, image_cache_ids, [request.image_size], image_hashes,
+                                n_keep=n_keep, strategy=self.pruning_strategy))
             b.append(EPMigrate())
             b.append(PullCache())
             prefill = ImageEmbedFill(image_cache_ids, mask[:n_prompt], token_ids[:n_prompt], ids[:n_prompt],

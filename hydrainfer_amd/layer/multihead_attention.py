@@ -37,8 +37,6 @@ class MultiHeadAttention(nn.Module):
 
     def forward(self, query: Tensor, key: Tensor, value: Tensor,
                 params: MultiHeadAttentionParameters) -> MultiHeadAttentionOutput:
-        if params.return_scores:
-            raise NotImplementedError("attention scores are not materialised by the fused HIP kernel")
         batch_size, seq_len, hidden_size = query.shape
         q = query.reshape(batch_size * seq_len, self.n_heads, self.head_dim)
         k = key.reshape(batch_size * seq_len, self.n_heads, self.head_dim)
@@ -55,4 +53,13 @@ class MultiHeadAttention(nn.Module):
                 self._cu[key_cu] = cu
         mha_varlen_fwd(o, q, k, v, cu, cu, None, None, None, seq_len, seq_len,
                        1.0 / math.sqrt(self.head_dim), 0, -1, -1, 0)
-        return MultiHeadAttentionOutput(o=o.view(batch_size, seq_len, hidden_size), attention_scores=None)
+        scores = None
+        if params.return_scores:
+            # the compatibility / debugging surface, not the hot path: what the reference's fallback handler returns
+            # (multihead_attention.py:59-62: the fp32 PRE-softmax scaled logits, a view taken before the softmax), by a
+            # library bmm on the device.  `o` above is the HIP kernel's, unchanged.  Pruning does not need this tensor:
+            # layer/token_prunning.py::focal_prunning_qk.
+            qs = q.view(batch_size, seq_len, self.n_heads, self.head_dim).transpose(1, 2).float() * (1.0 / math.sqrt(self.head_dim))
+            ks = k.view(batch_size, seq_len, self.n_heads, self.head_dim).transpose(1, 2).float()
+            scores = torch.matmul(qs, ks.transpose(-1, -2))
+        return MultiHeadAttentionOutput(o=o.view(batch_size, seq_len, hidden_size), attention_scores=scores)

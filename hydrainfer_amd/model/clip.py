@@ -8,7 +8,7 @@ GEMMs (q, k, v as ONE product over the three weights laid side by side); on the 
 and the quick-GELU run as one hand-written launch each (hx_add_layer_norm, hx_quick_gelu): 8 launches per encoder
 layer instead of 16 at a size (577 x 1024) where every launch is ~5 us whatever it does."""
 from dataclasses import dataclass
-from typing import Dict
+from typing import Dict, Optional
 
 import torch
 import torch.nn.functional as F
@@ -79,15 +79,18 @@ class LlavaVisionModel:
             hit = self._qkv[l] = (w, b)
         return hit
 
-    def _layer(self, l: int, h: Tensor, x: Tensor):
+    def _layer(self, l: int, h: Tensor, x: Tensor, qk_out: Optional[list] = None):
         """h: the residual stream; x = layer_norm1(h) (computed by the previous layer's last launch).  Returns the new
-        (h, x) — x is layer_norm1 of the NEXT layer, or None after the last layer that runs."""
+        (h, x) — x is layer_norm1 of the NEXT layer, or None after the last layer that runs.  qk_out: a list that
+        receives this layer's q and k views (the last executed layer's rank the image tokens for pruning)."""
         s, sh = self.state, self.shape
         p = f"vision_tower.vision_model.encoder.layers.{l}."
         hid = sh.hidden_size
         wqkv, bqkv = self._fused_qkv(l)
         qkv = F.linear(x, wqkv, bqkv)
         q, k, v = qkv[..., :hid], qkv[..., hid:2 * hid], qkv[..., 2 * hid:]       # views: the kernel takes the row stride
+        if qk_out is not None:
+            qk_out += [q, k]
         o = self.attn(q, k, v, MultiHeadAttentionParameters()).o
         y = F.linear(o, s[p + "self_attn.out_proj.weight"], s[p + "self_attn.out_proj.bias"])
         x = torch.empty_like(h)
@@ -101,8 +104,14 @@ class LlavaVisionModel:
         add_layer_norm(x, h, m, s[pn + "layer_norm1.weight"], s[pn + "layer_norm1.bias"], sh.layer_norm_eps)     # h += m
         return h, x
 
-    def forward(self, pixel_values: Tensor) -> Tensor:
-        """pixel_values (n_images, C, H, W) -> image_features (n_images, n_patches, lm_hidden)."""
+    def forward(self, pixel_values: Tensor, n_keep=None, strategy: str = "rank") -> Tensor:
+        """pixel_values (n_images, C, H, W) -> image_features (n_images, n_patches, lm_hidden).
+        n_keep (an int, a per-image list, or an int32 device tensor [n_images]; None = no pruning, the path above
+        untouched): focal token pruning (layer/token_prunning.py) — the q and k of the last executed layer rank the patch
+        tokens (the CLS token takes no part), and image b's n_keep[b] kept rows of the PROJECTOR OUTPUT come first in its
+        block, in ascending token order: forward(px, n)[b, :n_b] == forward(px)[b, ids[b, :n_b]] bit for bit; the rows
+        behind them are unwritten.  Three more launches, no host synchronisation: with n_keep on the device one captured
+        graph per image count serves every mix of counts.  `last_kept_ids` holds the id tensor of the last pruned call."""
         s, sh = self.state, self.shape
         pre = "vision_tower.vision_model."
         n = pixel_values.shape[0]
@@ -119,12 +128,21 @@ class LlavaVisionModel:
                          sh.layer_norm_eps)
         p0 = pre + "encoder.layers.0."
         x = F.layer_norm(h, (sh.hidden_size,), s[p0 + "layer_norm1.weight"], s[p0 + "layer_norm1.bias"], sh.layer_norm_eps)
+        qk = [] if n_keep is not None else None
         for l in range(self.n_run):
-            h, x = self._layer(l, h, x)
+            h, x = self._layer(l, h, x, qk if l + 1 == self.n_run else None)
         feat = h[:, 1:]                                        # drop CLS (llava.py:104)
         x = F.linear(feat, s["multi_modal_projector.linear_1.weight"], s["multi_modal_projector.linear_1.bias"])
         x = F.gelu(x)
-        return F.linear(x, s["multi_modal_projector.linear_2.weight"], s["multi_modal_projector.linear_2.bias"])
+        feats = F.linear(x, s["multi_modal_projector.linear_2.weight"], s["multi_modal_projector.linear_2.bias"])
+        if n_keep is None:
+            return feats
+        # (pruning in front of the projector would save its GEMM rows but change which library GEMM runs, and with it
+        #  the bits of the kept rows)
+        from hydrainfer_amd.layer.token_prunning import focal_prunning_qk
+        pruned, self.last_kept_ids = focal_prunning_qk(feats, qk[0], qk[1], n_keep, strategy, skip_leading=1,
+                                                       n_heads=sh.num_attention_heads)
+        return pruned
 
     __call__ = forward
 

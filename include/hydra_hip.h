@@ -658,6 +658,44 @@ int hx_moe_unpermute(const void* permuted, void* out, const int32_t* row_id_map,
 int hx_moe_sum_out(const void* in, void* out, int64_t n_tokens, int64_t topk, int64_t dim,
                    int dtype, hx_stream stream);
 
+/* ------------------------------------------------------------------------
+ * Focal image-token pruning without a score tensor (csrc/focal_prune.hip).
+ * replaces: hydrainfer/layer/token_prunning.py:5-37 (focal_prunning) fed with the pre-softmax scaled logits of
+ *           hydrainfer/layer/multihead_attention.py:59-62 (`attention_scores`, a view of `score` taken before the softmax)
+ * Per image, N = tokens_per_image - skip_leading tokens, H heads, head dim D:
+ *   S_h[i, j] = (q[i,h,:] * scale) . k[j,h,:];  A = mean_h S_h;  s1[j] = mean_i A[i, j];  s2[i] = mean_j A[i, j]
+ *   sig = var(s1) > var(s2) ? s1 : s2  (unbiased variance);  'rank': keep the n tokens of largest sig;  'row': g = sqrt(N),
+ *   keep all tokens of the n / g grid rows with the largest sum of sig;  ties go to the lower index;  ids ascending.
+ * Every reduction is linear in S, so s1 / s2 come from q and k directly (column sums, then one dot product per token):
+ * no N x N tensor, no host synchronisation.  All three are deterministic (no floating-point atomics, fixed summation
+ * order), record into launch plans and capture into hipGraphs.
+ *
+ * hx_focal_significance (token_prunning.py:17-21 over multihead_attention.py:59-62): q, k [n_images * tokens_per_image,
+ *   n_heads, head_dim] f16 / bf16, heads contiguous, row strides in elements (multiples of 8, 16-byte aligned bases);
+ *   the first skip_leading tokens of every image (CLIP's CLS: 1) take no part, neither as query nor as key.  s1, s2: fp32
+ *   [n_images, N].  head_dim % 8 == 0, n_heads * head_dim <= 8192, N <= 4096.  workspace: at least
+ *   hx_focal_significance_workspace_bytes(n_images, n_heads, head_dim) bytes, 4-byte aligned.
+ * hx_focal_select (token_prunning.py:22-35): n_keep int32 [n_images] ON THE DEVICE (clamped to 0 .. N); ids_out int32
+ *   [n_images, N]: the first n_keep[b] entries of row b are the kept ids in ascending order, the rest -1.  strategy
+ *   HX_FOCAL_ROW needs a square N (HX_ERR_SHAPE) and keeps n_keep[b] / g whole rows (the caller, who knows the counts,
+ *   refuses n % g != 0).  Variances in fp32, two passes; var(s1) == var(s2) or NaN -> s2.
+ * hx_focal_gather (token_prunning.py:36): out[b, r, :] = tokens[b, ids[b, r], :] for r < n_keep[b], bit-exact 16-byte
+ *   copies; rows r >= n_keep[b] (and ids outside 0 .. N-1) are not written.  tokens and out hold N rows per image at
+ *   row strides token_row_stride / out_row_stride elements; hidden * itemsize and both strides multiples of 16 bytes.
+ * ---------------------------------------------------------------------- */
+#define HX_FOCAL_RANK 0
+#define HX_FOCAL_ROW 1
+int64_t hx_focal_significance_workspace_bytes(int64_t n_images, int64_t n_heads, int64_t head_dim);
+int hx_focal_significance(float* s1, float* s2, const void* q, const void* k, int64_t n_images,
+                          int64_t tokens_per_image, int64_t skip_leading, int64_t n_heads, int64_t head_dim,
+                          int64_t q_row_stride, int64_t k_row_stride, float scale, void* workspace,
+                          int64_t workspace_bytes, int dtype, hx_stream stream);
+int hx_focal_select(int32_t* ids_out, const float* s1, const float* s2, const int32_t* n_keep,
+                    int64_t n_images, int64_t N, int strategy, hx_stream stream);
+int hx_focal_gather(void* out, const void* tokens, const int32_t* ids, const int32_t* n_keep,
+                    int64_t n_images, int64_t N, int64_t hidden, int64_t token_row_stride,
+                    int64_t out_row_stride, int dtype, hx_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
