@@ -218,10 +218,14 @@
     }
   }
   auto patch = [&](KVTile<D>& buf, int t) {
+    // The new token's row AND the rows behind it: load_tile_b clamps rows past the last key to the last valid row, which
+    // here is the slot this launch appends to — the cache may still hold what the allocator left there (NaN bit patterns
+    // included), and a masked row's p = 0 times a NaN value is NaN.  With the new token in those rows the tile is what
+    // the unfused sequence (append, then attend) loads: same bits.
     if (FUSE && t == t_new) {     // wave-uniform
 #pragma unroll
       for (int i = 0; i < KPL; ++i)
-        if (KPL * g + i == r_new) {
+        if (KPL * g + i >= r_new) {
 #pragma unroll
           for (int n = 0; n < VRow<D>::NV; ++n) {
             buf.k[i][n] = knr[n];
