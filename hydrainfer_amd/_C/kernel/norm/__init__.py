@@ -189,3 +189,54 @@ def argmax_rows(logits: Tensor, out: Optional[Tensor] = None) -> Tensor:
     _lib.check(_lib.lib().hx_argmax_rows(out.data_ptr(), logits.data_ptr(), logits.shape[0], logits.shape[1],
                                          logits.stride(0), _lib.dtype_code(logits), _lib.current_stream()), "argmax_rows")
     return out
+
+
+LOGPROB_MAX_TOP_K = 20      # OpenAI's limit for top_logprobs
+
+
+def logprob_rows_bytes(rows: int, top_k: int) -> int:
+    """Size of the packed result of logprob_rows: [ids int64 x rows | logprobs fp32 x rows | top_ids int32 x rows*K |
+    top_logprobs fp32 x rows*K], one uint8 allocation — a step's scores reach the host in ONE copy."""
+    return rows * (12 + 8 * top_k)
+
+
+def logprob_rows_views(packed: Tensor, rows: int, top_k: int):
+    """The four results inside a packed buffer (device or host): (ids, logprobs, top_ids, top_logprobs)."""
+    if packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous() or packed.numel() != logprob_rows_bytes(rows, top_k):
+        raise _lib.HydraHipError(f"logprob_rows: packed buffer must be contiguous uint8 [{logprob_rows_bytes(rows, top_k)}]")
+    a, b, c = 8 * rows, 12 * rows, 12 * rows + 4 * rows * top_k
+    return (packed[:a].view(torch.int64), packed[a:b].view(torch.float32),
+            packed[b:c].view(torch.int32).view(rows, top_k), packed[c:].view(torch.float32).view(rows, top_k))
+
+
+def logprob_rows_packed(ids: Tensor, top_k: int) -> Tensor:
+    """The packed buffer behind the results of logprob_rows, from its first result: what one copy brings to the host
+    (`logprob_rows_views(logprob_rows_packed(ids, k).cpu(), rows, k)`)."""
+    n = logprob_rows_bytes(ids.shape[0], top_k)
+    return torch.empty(0, dtype=torch.uint8, device=ids.device).set_(ids.untyped_storage(), ids.storage_offset() * 8, (n,))
+
+
+def logprob_rows(logits: Tensor, top_k: int = 0, out: Optional[Tensor] = None):
+    """Extension: the greedy id of every row of fp16 / bf16 logits [rows, n], its log-softmax value and the top_k
+    (0..20) most likely entries, one launch (hx_logprob_rows: fp32 arithmetic, the row read once) — instead of
+    torch.log_softmax(logits.float(), -1) + torch.topk.  Returns (ids int64 [rows] — equal to argmax_rows(logits) —,
+    logprobs fp32 [rows], top_ids int32 [rows, K], top_logprobs fp32 [rows, K]), K entries ordered by value descending,
+    then index ascending; past the row's width: id -1, logprob -inf.  The four are views of one uint8 buffer (`out`, or a
+    new one: logprob_rows_bytes / logprob_rows_views), which goes to the host in one copy (logprob_rows_packed)."""
+    _lib.require_gpu(logits, out)
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.dtype not in (torch.float16, torch.bfloat16) \
+            or logits.shape[0] < 1 or logits.shape[1] < 1 or logits.stride(0) < logits.shape[1]:
+        raise _lib.HydraHipError("logprob_rows: logits must be fp16 / bf16 [rows, n] (rows, n >= 1) with contiguous rows")
+    if not isinstance(top_k, int) or isinstance(top_k, bool) or not 0 <= top_k <= LOGPROB_MAX_TOP_K:
+        raise _lib.HydraHipError(f"logprob_rows: top_k {top_k!r} outside 0..{LOGPROB_MAX_TOP_K}")
+    rows = logits.shape[0]
+    if out is None:
+        out = torch.empty(logprob_rows_bytes(rows, top_k), dtype=torch.uint8, device=logits.device)
+    elif out.device != logits.device or out.data_ptr() % 8:
+        raise _lib.HydraHipError("logprob_rows: out must be an 8-byte aligned buffer on the logits' device")
+    ids, lp, top_ids, top_lp = logprob_rows_views(out, rows, top_k)
+    _lib.check(_lib.lib().hx_logprob_rows(ids.data_ptr(), lp.data_ptr(), top_ids.data_ptr() if top_k else None,
+                                          top_lp.data_ptr() if top_k else None, logits.data_ptr(), rows, logits.shape[1],
+                                          logits.stride(0), top_k, _lib.dtype_code(logits), _lib.current_stream()),
+               "logprob_rows")
+    return ids, lp, top_ids, top_lp

@@ -1,0 +1,237 @@
+// logprobs.hip — per-token log-probabilities of a decode step (include/hydra_hip.h: hx_logprob_rows): the greedy id of
+// hydrainfer/model/llama.py:99-104 together with its log-softmax value and the K most likely alternatives, what
+// torch.log_softmax(logits.float(), -1) + torch.topk would give in three more passes and an fp32 copy of the logits.
+//
+// One workgroup per row.  The row is read from HBM once into LDS (a 32064-wide 16-bit row is 63 KiB of the CU's 160);
+// everything after that — the fp32 sum of exponentials and the K selection rounds — reads LDS.  Rows wider than
+// LP_LDS_ELEMS stay in global memory (L2) and run the same code from there.
+//
+// Order.  "a before b" is arg_better of norm_rope_act.hip: a NaN first, then the larger value, then the lower index — a
+// total order, so the first element is hx_argmax_rows' answer whatever the reduction order, and the top-K list (the
+// first K elements) has one defined answer even in rows full of exact 16-bit ties.
+// Selection.  Each thread owns a fixed subset of the row and keeps its best not-yet-taken element as its candidate.  A
+// round is one workgroup reduction over the candidates; only the winner's owner needs a new one (its best element after
+// the winner), which its wave finds together.  K rounds cost K reductions, not K passes over the row.
+#include <math.h>
+
+#include "hx_common.h"
+
+namespace hx {
+
+#define LP_THREADS 1024
+#define LP_MAX_K 20
+#define LP_LDS_ELEMS 65536          // 128 KiB of LDS for the row; wider rows are read from global memory
+#define LP_NONE 0x7fffffff          // index of "no element": loses to every real element
+
+// (the rule of arg_better, norm_rope_act.hip)
+__device__ __forceinline__ bool lp_before(float a, int ia, float b, int ib) {
+  const bool an = a != a, bn = b != b;
+  if (an != bn) return an;
+  if (!an && a != b) return a > b;
+  return ia < ib;
+}
+
+// f(value, index) for every element this thread owns.  vec: the row is read in 16-byte pieces, thread t owns the pieces
+// t, t + 1024, ... and the element nvec * 8 + t of the n % 8 tail; otherwise it owns the elements t, t + 1024, ...
+template <typename T, typename F>
+__device__ __forceinline__ void lp_for_own(const u16* src, int n, bool vec, F f) {
+  if (vec) {
+    const int nvec = n >> 3;
+    for (int i = threadIdx.x; i < nvec; i += LP_THREADS) {
+      const u16x8 v = *reinterpret_cast<const u16x8*>(src + (int64_t)i * 8);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) f(T::to_float(v[e]), i * 8 + e);
+    }
+    const int i = nvec * 8 + (int)threadIdx.x;
+    if (i < n) f(T::to_float(src[i]), i);
+  } else {
+    for (int i = threadIdx.x; i < n; i += LP_THREADS) f(T::to_float(src[i]), i);
+  }
+}
+
+// this thread's first element (in the order above) that comes after (wv, wi); (NaN, -1) comes before every element
+template <typename T>
+__device__ __forceinline__ void lp_candidate(const u16* src, int n, bool vec, float wv, int wi, float& cv, int& ci) {
+  float bv = -INFINITY;
+  int bi = LP_NONE;
+  lp_for_own<T>(src, n, vec, [&](float v, int i) {
+    if (lp_before(wv, wi, v, i) && lp_before(v, i, bv, bi)) { bv = v; bi = i; }
+  });
+  cv = bv;
+  ci = bi;
+}
+
+// The same for the elements of thread `owner`, by the 64 lanes of a wave together: lane l takes the owner's element
+// l % 8 of its pieces l / 8, l / 8 + 8, ... (one element per lane for rows that fit in LDS), lane 0 its tail element;
+// every lane returns the owner's first element after (wv, wi).
+template <typename T>
+__device__ __forceinline__ void lp_candidate_of(const u16* src, int n, bool vec, int owner, float wv, int wi, float& cv,
+                                                int& ci) {
+  const int lane = threadIdx.x & 63;
+  float bv = -INFINITY;
+  int bi = LP_NONE;
+  auto take = [&](int i) {
+    const float v = T::to_float(src[i]);
+    if (lp_before(wv, wi, v, i) && lp_before(v, i, bv, bi)) { bv = v; bi = i; }
+  };
+  if (vec) {
+    const int nvec = n >> 3;
+    for (int j = owner + LP_THREADS * (lane >> 3); j < nvec; j += 8 * LP_THREADS) take(j * 8 + (lane & 7));
+    if (lane == 0 && nvec * 8 + owner < n) take(nvec * 8 + owner);
+  } else {
+    for (int i = owner + LP_THREADS * lane; i < n; i += 64 * LP_THREADS) take(i);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const float ov = __shfl_xor(bv, off, 64);
+    const int oi = __shfl_xor(bi, off, 64);
+    if (lp_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+  }
+  cv = bv;
+  ci = bi;
+}
+
+// the first of all threads' (v, i), in every thread.  part: 16 floats + 16 ints of LDS, not in use by a reduction that
+// other waves may still be reading (the callers alternate two).
+__device__ __forceinline__ void lp_block_first(float& v, int& i, float* part_v, int* part_i) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const float ov = __shfl_xor(v, off, 64);
+    const int oi = __shfl_xor(i, off, 64);
+    if (lp_before(ov, oi, v, i)) { v = ov; i = oi; }
+  }
+  if ((threadIdx.x & 63) == 0) { part_v[threadIdx.x >> 6] = v; part_i[threadIdx.x >> 6] = i; }
+  __syncthreads();
+  v = part_v[0];
+  i = part_i[0];
+#pragma unroll
+  for (int k = 1; k < LP_THREADS / 64; ++k) {
+    const float ov = part_v[k];
+    const int oi = part_i[k];
+    if (lp_before(ov, oi, v, i)) { v = ov; i = oi; }
+  }
+}
+
+template <typename T, bool LDS>
+__global__ __launch_bounds__(LP_THREADS) void logprob_rows_kernel(int64_t* __restrict__ ids, float* __restrict__ logprobs,
+                                                                  int32_t* __restrict__ top_ids,
+                                                                  float* __restrict__ top_logprobs,
+                                                                  const u16* __restrict__ logits, int32_t n, int64_t ld,
+                                                                  int32_t top_k) {
+  extern __shared__ __attribute__((aligned(16))) u16 staged[];      // LDS: the row, n elements (rounded up to 8)
+  __shared__ float part_v[2][LP_THREADS / 64];
+  __shared__ int part_i[2][LP_THREADS / 64];
+  __shared__ float part_s[LP_THREADS / 64];
+  const int64_t row = blockIdx.x;
+  const u16* p = logits + row * ld;
+  const bool gvec = (ld % 8 == 0) && ((reinterpret_cast<uintptr_t>(logits) & 15) == 0);
+
+  const u16* src = p;
+  bool vec = gvec;
+  if (LDS) {
+    if (gvec) {
+      const int nvec = n >> 3;
+      // four independent 16-byte loads per thread in flight, like argmax_rows_kernel: one memory round trip for a
+      // 32064-wide row
+      for (int i0 = threadIdx.x; i0 < nvec; i0 += 4 * LP_THREADS) {
+        u16x8 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const u16x8*>(p + (int64_t)min(i0 + LP_THREADS * u, nvec - 1) * 8);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int i = i0 + LP_THREADS * u;
+          if (i < nvec) *reinterpret_cast<u16x8*>(staged + i * 8) = v[u];
+        }
+      }
+      for (int i = nvec * 8 + threadIdx.x; i < n; i += LP_THREADS) staged[i] = p[i];
+    } else {
+      for (int i = threadIdx.x; i < n; i += LP_THREADS) staged[i] = p[i];
+    }
+    __syncthreads();
+    src = staged;
+    vec = true;
+  }
+
+  // round 0: the greedy id
+  float cv;
+  int ci;
+  lp_candidate<T>(src, n, vec, __builtin_nanf(""), -1, cv, ci);
+  float best = cv;
+  int bi = ci;
+  lp_block_first(best, bi, part_v[0], part_i[0]);
+
+  // log(sum exp(x - best)): per-thread partial sums, a wave tree, sixteen partials in order — every thread holds the
+  // same bits.  A NaN in the row makes best, and with it every term, NaN.
+  float s = 0.f;
+  lp_for_own<T>(src, n, vec, [&](float v, int) { s += expf(v - best); });
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) part_s[threadIdx.x >> 6] = s;
+  __syncthreads();
+  s = part_s[0];
+#pragma unroll
+  for (int k = 1; k < LP_THREADS / 64; ++k) s += part_s[k];
+  const float log_sum = logf(s);
+
+  if (threadIdx.x == 0) {
+    ids[row] = bi;
+    logprobs[row] = (best - best) - log_sum;
+  }
+  float wv = best;
+  int wi = bi;
+  for (int r = 0; r < top_k; ++r) {
+    if (r > 0) {
+      // the previous winner's owner needs its next candidate: its wave finds it together (alone, the owner would walk
+      // its 32 elements one after the other while 1023 threads wait: 7 us a round, measured)
+      const int nvec8 = (n >> 3) * 8;
+      const int owner = vec ? (wi < nvec8 ? (wi >> 3) & (LP_THREADS - 1) : wi - nvec8) : wi & (LP_THREADS - 1);
+      if (wi != LP_NONE && (owner >> 6) == (int)(threadIdx.x >> 6)) {
+        float nv;
+        int ni;
+        lp_candidate_of<T>(src, n, vec, owner, wv, wi, nv, ni);
+        if ((int)threadIdx.x == owner) { cv = nv; ci = ni; }
+      }
+      wv = cv;
+      wi = ci;
+      lp_block_first(wv, wi, part_v[r & 1], part_i[r & 1]);
+    }
+    if (threadIdx.x == 0) {
+      const bool none = wi == LP_NONE;                                    // K > n: the row is used up
+      top_ids[row * top_k + r] = none ? -1 : wi;
+      top_logprobs[row * top_k + r] = none ? -INFINITY : (wv - best) - log_sum;
+    }
+  }
+}
+
+}  // namespace hx
+
+using namespace hx;
+
+template <typename T>
+static int launch_logprob_rows(int64_t* ids, float* logprobs, int32_t* top_ids, float* top_logprobs, const void* logits,
+                               int64_t rows, int64_t n, int64_t ld, int top_k, hipStream_t s) {
+  if (n <= LP_LDS_ELEMS) {
+    const size_t lds = (size_t)((n + 7) / 8 * 8) * sizeof(u16);
+    if (lds > 48 * 1024) {
+      hipError_t e = hipFuncSetAttribute((const void*)logprob_rows_kernel<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int)lds);
+      if (e != hipSuccess) return hip_rc(e);
+    }
+    hx::launcher(logprob_rows_kernel<T, true>, (unsigned)rows, LP_THREADS, lds, s)(ids, logprobs, top_ids, top_logprobs,
+                                                                                 (const u16*)logits, (int32_t)n, ld, top_k);
+  } else {
+    hx::launcher(logprob_rows_kernel<T, false>, (unsigned)rows, LP_THREADS, 0, s)(ids, logprobs, top_ids, top_logprobs,
+                                                                                (const u16*)logits, (int32_t)n, ld, top_k);
+  }
+  return check_launch();
+}
+
+extern "C" int hx_logprob_rows(int64_t* ids, float* logprobs, int32_t* top_ids, float* top_logprobs, const void* logits,
+                               int64_t rows, int64_t n, int64_t ld, int top_k, int dtype, hx_stream stream) {
+  if (rows < 1 || n < 1 || ld < n || n > 0x7ffffff0 || rows > 0x7fffffff) return HX_ERR_SHAPE;
+  if (top_k < 0 || top_k > LP_MAX_K) return HX_ERR_SHAPE;
+  if (dtype != HX_F16 && dtype != HX_BF16) return HX_ERR_DTYPE;
+  if (!ids || !logprobs || !logits || (top_k > 0 && (!top_ids || !top_logprobs))) return HX_ERR_NULL;
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == HX_F16) return launch_logprob_rows<F16>(ids, logprobs, top_ids, top_logprobs, logits, rows, n, ld, top_k, s);
+  return launch_logprob_rows<BF16>(ids, logprobs, top_ids, top_logprobs, logits, rows, n, ld, top_k, s);
+}

@@ -35,6 +35,16 @@ def _cache_from_wire(d) -> Optional[VirtualTokenCache]:
     return None if d is None else VirtualTokenCache(**d)
 
 
+def refuse_logprobs(request) -> None:
+    """One-process-per-GPU serving does not carry log-probabilities: the rank protocol (rcb_to_wire, the token messages)
+    has no field for them, and dropping the request's wish silently would hand the client a stream without the scores
+    it asked for.  Single-process serving (entrypoint/api_server.EngineFrontend, engine/offline.py) has them."""
+    sp = getattr(request, "sampling_params", None)
+    if sp is not None and (sp.logprobs or sp.top_logprobs):
+        raise ValueError(f"request {request.request_id}: logprobs are not available in multi-process serving "
+                         "(one engine process per GPU); use the single-process server or the offline engine")
+
+
 def rcb_to_wire(rcb: RequestControlBlock) -> dict:
     """Everything the next stage needs: the instructions from the current one on (a flat list —
     the linked chain would pickle recursively), the block tables + IPC handles of the caches, the
@@ -284,6 +294,7 @@ class RankEngine:
         """Front-end side: start `request` on the rank cluster.py:178-184 picks (image requests round-robin over the E
         ranks, text-only ones over the P ranks — two balancers, each with its own cursor); its tokens — sampled on
         whichever ranks run its prefill and decode — are delivered to `processor` on THIS rank."""
+        refuse_logprobs(request)
         self.token_handlers[request.request_id] = processor
         has_image = request.pixel_values is not None
         dst = entry_rank(self._n_submitted[has_image], self.roles, has_image, self.dead)

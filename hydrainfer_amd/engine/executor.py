@@ -12,12 +12,13 @@ from typing import List, Optional
 import numpy as np
 import torch
 
+from hydrainfer_amd._C.kernel.norm import logprob_rows_packed, logprob_rows_views
 from hydrainfer_amd._lib import HydraHipError
 
 from hydrainfer_amd.engine import rcb as rcb_module
 from hydrainfer_amd.engine.isa import Fill, TextFill
 from hydrainfer_amd.engine.parameters_builder import LanguageModelParametersBuilder
-from hydrainfer_amd.engine.rcb import BatchRequest
+from hydrainfer_amd.engine.rcb import BatchRequest, TokenLogprob
 from hydrainfer_amd.model.llama import LanguageModelParameters
 
 
@@ -85,8 +86,8 @@ class BatchFillExecutor:
         bs = self.kv_manager.block_size
         pending_launch = self.pending[0] if self.pending is not None else None
         for rcb, inst in batch:
-            if len(inst.token_ids) != 1 or not inst.sample:
-                return None
+            if len(inst.token_ids) != 1 or not inst.sample or rcb.sampling_params.logprobs:
+                return None                    # (a request that wants log-probabilities decodes eagerly: execute())
             token = inst.token_ids[0]
             if isinstance(token, PendingToken):
                 if token.launch != pending_launch:
@@ -264,7 +265,8 @@ class BatchFillExecutor:
             pending, self.pending = self.pending, None
             self._resolve(pending)
 
-    def _deliver(self, batch: BatchRequest, sampled: List[int]) -> None:
+    def _deliver(self, batch: BatchRequest, sampled: List[int], scores=None) -> None:
+        """scores: None, or the step's (logprobs, top_ids, top_logprobs) as host lists, one entry per sampled row."""
         now = time.perf_counter()
         i = 0
         for rcb, inst in batch:
@@ -274,16 +276,37 @@ class BatchFillExecutor:
             i += 1
             if rcb.eos_hit:
                 continue                       # already ended by a token that was read back late
+            entry = None
             if not inst.is_chunked:
                 rcb.metric.token_times.append(now)
                 rcb.output_token_ids.append(token)
+                if scores is not None and rcb.sampling_params.logprobs:
+                    k = rcb.sampling_params.top_logprobs        # this request's own count out of the batch's largest
+                    entry = TokenLogprob(token, scores[0][i - 1], list(zip(scores[1][i - 1][:k], scores[2][i - 1][:k])))
+                    rcb.output_logprobs.append(entry)
             if inst.sample_dst is not None:
                 inst.sample_dst.token_ids = [token]
             if not inst.is_chunked:
                 last = rcb.is_finished()
                 for p in rcb.output_token_processors:
+                    if entry is not None:
+                        p.append_logprobs(entry)
                     p.append_token_id(token, last)
         batch.step()
+
+    def _sample_with_logprobs(self, inputs, params, top_k: int):
+        """The eager step of a batch in which some request asked for log-probabilities: the same logits, ids by the same
+        rule, and the scores beside them — one launch (hx_logprob_rows), one packed buffer, ONE device-to-host copy."""
+        ids = self.language_model.forward_logprobs(inputs.input_ids, inputs.image_features, inputs.position_ids,
+                                                   params, top_k)[0]
+        rows = ids.shape[0]
+        host = logprob_rows_packed(ids, top_k).cpu()                                   # the step's only device sync
+        ids, lp, top_ids, top_lp = logprob_rows_views(host, rows, top_k)
+        sampled, scores = ids.tolist(), (lp.tolist(), top_ids.tolist(), top_lp.tolist())
+        if inputs.all_sequences_decode and rows != len(inputs.selected_token_ids):
+            sel = inputs.selected_token_ids
+            sampled, scores = [sampled[j] for j in sel], tuple([col[j] for j in sel] for col in scores)
+        return sampled, scores
 
     def _publish_prefix_blocks(self, batch: BatchRequest) -> None:
         """A block's hash enters the prefix cache in the step that computes its last token
@@ -325,6 +348,11 @@ class BatchFillExecutor:
                 self.language_model.embed(inputs.input_ids, inputs.image_features, inputs.image_row_index),
                 inputs.position_ids, params)
             batch.step()
+            return
+        asking = [rcb.sampling_params.top_logprobs for rcb, inst in batch
+                  if rcb.sampling_params.logprobs and isinstance(inst, Fill) and inst.sample and not inst.is_chunked]
+        if asking:
+            self._deliver(batch, *self._sample_with_logprobs(inputs, params, max(asking)))
             return
         sampled = self.language_model.forward(inputs.input_ids, inputs.image_features, inputs.position_ids,
                                               params)

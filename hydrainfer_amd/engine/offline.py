@@ -8,7 +8,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from hydrainfer_amd.engine.node import LocalCluster
-from hydrainfer_amd.engine.rcb import SamplingParameters, TokenParameters
+from hydrainfer_amd.engine.rcb import SamplingParameters, TokenLogprob, TokenParameters
 from hydrainfer_amd.engine.request_processor import InstructionCreator, TokenRequest
 from hydrainfer_amd.engine.scheduler import BatchSchedulerConfig
 from hydrainfer_amd.engine.serve import build_node, quiet_gc, warm_library_gemms
@@ -24,6 +24,7 @@ class OfflineInferenceOutput:
     token_times: List[float] = field(default_factory=list)
     ttft: float = -1.0
     tpot: List[float] = field(default_factory=list)
+    output_logprobs: List[TokenLogprob] = field(default_factory=list)    # one per output token if the request asked, else empty
 
 
 @dataclass
@@ -33,6 +34,8 @@ class OfflineRequest:
     max_tokens: int = 50
     eos_token_ids: Sequence[int] = ()
     token_params: Optional[TokenParameters] = None     # token_pruning_policy='focal': the image as n_embed_output_tokens tokens
+    logprobs: bool = False        # the log-probability of every generated token (such a request decodes eagerly)
+    top_logprobs: int = 0         # and of its 0..20 most likely alternatives
 
 
 class OfflineInferenceEngine:
@@ -77,7 +80,8 @@ class OfflineInferenceEngine:
                 req = TokenRequest(request_id=i, token_ids=list(r.token_ids), pixel_values=pixels,
                                    image_size=(r.image.size[1], r.image.size[0]) if r.image is not None else (0, 0),
                                    image_hash=compute_image_hash(r.image) if r.image is not None else 0,
-                                   sampling_params=SamplingParameters(r.max_tokens, list(r.eos_token_ids)),
+                                   sampling_params=SamplingParameters(r.max_tokens, list(r.eos_token_ids), r.logprobs,
+                                                                      r.top_logprobs),
                                    token_params=r.token_params)
                 rcb = self.creator.process(req)
                 rcb.metric.arrival_time = time.perf_counter()
@@ -94,5 +98,5 @@ class OfflineInferenceEngine:
                 output_token_ids=list(rcb.output_token_ids), arrival_time=rcb.metric.arrival_time,
                 finished_time=rcb.metric.finished_time, token_times=list(t),
                 ttft=t[0] - rcb.metric.arrival_time if t else -1.0,
-                tpot=[b - a for a, b in zip(t, t[1:])]))
+                tpot=[b - a for a, b in zip(t, t[1:])], output_logprobs=list(rcb.output_logprobs)))
         return outs

@@ -13,6 +13,20 @@ from hydrainfer_amd.memory.token_cache import VirtualTokenCache
 class SamplingParameters:
     max_tokens: int = 50
     eos_token_ids: List[int] = field(default_factory=list)
+    logprobs: bool = False      # a TokenLogprob per generated token (OpenAI's `logprobs`); such a request decodes eagerly
+    top_logprobs: int = 0       # 0..20 most likely alternatives in each of them; needs logprobs
+
+
+MAX_TOP_LOGPROBS = 20
+
+
+@dataclass
+class TokenLogprob:
+    """One generated token's score: its log-probability under the model's softmax (fp32, hx_logprob_rows) and the
+    request's top_logprobs most likely (token id, log-probability) pairs, most likely first (ties: lower id first)."""
+    token_id: int
+    logprob: float
+    top: List[Tuple[int, float]] = field(default_factory=list)
 
 
 @dataclass
@@ -72,6 +86,10 @@ class OutputTokenProcessor:
     def append_token_id(self, token_id: int, is_last_token: bool = False) -> None:
         raise NotImplementedError
 
+    def append_logprobs(self, entry: "TokenLogprob") -> None:
+        """The score of the token the next append_token_id call delivers (only for requests with
+        sampling_params.logprobs).  Processors that do not care ignore it."""
+
     def fail(self, exc: BaseException) -> None:
         """The request was terminated by the engine (a migration that failed twice, a node that died): the reference
         pushes a None token to the stream (hydrainfer/cluster/epdnode.py:440-442, `(request_id, None)`)."""
@@ -97,6 +115,7 @@ class RequestControlBlock:
         self.sid: int = -1
         self.output_token_processors: List[OutputTokenProcessor] = []
         self.output_token_ids: List[int] = []
+        self.output_logprobs: List[TokenLogprob] = []     # parallel to output_token_ids when sampling_params.logprobs, else empty
         self.scenario_type: Optional[ScenarioType] = None
         self.metric = RequestMetric()
         self.eos_hit = False      # set when a token read back late (decode look-ahead) was end-of-sequence

@@ -8,7 +8,7 @@ import xxhash
 
 from hydrainfer_amd.engine.isa import (EPMigrate, ImageEmbed, ImageEmbedFill, InstructionListBuilder,
                                        PDMigrate, PullCache, TextFill)
-from hydrainfer_amd.engine.rcb import (RequestControlBlock, RequestMetaData, SamplingParameters,
+from hydrainfer_amd.engine.rcb import (MAX_TOP_LOGPROBS, RequestControlBlock, RequestMetaData, SamplingParameters,
                                        ScenarioClassifier, TokenParameters)
 from hydrainfer_amd.memory.shared_cache import compute_hash
 
@@ -93,7 +93,14 @@ class InstructionCreator:
         rcb = RequestControlBlock()
         rcb.request_id = request.request_id
         sp = request.sampling_params or SamplingParameters()
-        rcb.sampling_params = SamplingParameters(sp.max_tokens, list(sp.eos_token_ids))
+        top = sp.top_logprobs
+        if not isinstance(sp.logprobs, bool):
+            raise ValueError(f"request {request.request_id}: logprobs {sp.logprobs!r} must be a bool")
+        if not isinstance(top, int) or isinstance(top, bool) or not 0 <= top <= MAX_TOP_LOGPROBS:
+            raise ValueError(f"request {request.request_id}: top_logprobs {top!r} outside 0..{MAX_TOP_LOGPROBS}")
+        if top > 0 and not sp.logprobs:
+            raise ValueError(f"request {request.request_id}: top_logprobs = {top} needs logprobs = True")
+        rcb.sampling_params = SamplingParameters(sp.max_tokens, list(sp.eos_token_ids), sp.logprobs, top)
         if not self.ignore_eos:
             rcb.sampling_params.eos_token_ids.append(self.eos_token_id)
 

@@ -9,11 +9,13 @@ produce (`model_dump_json(exclude_unset=True)`) and the prompt its LLaVA chat te
 container by tests/golden/generate_goldens.py."""
 import base64
 import json
+import math
 from dataclasses import dataclass
 from typing import List, Optional
 
 IMAGE_TOKEN = "<image>"            # hydrainfer/model/llava.py:195
 CHUNK_OBJECT = "chat.completion.chunk"
+MAX_TOP_LOGPROBS = 20              # OpenAI's limit
 
 
 class ProtocolError(ValueError):
@@ -28,6 +30,8 @@ class ChatRequest:
     image_png: Optional[bytes]      # decoded bytes of the (at most one) base64 PNG
     max_tokens: int
     stream: bool
+    logprobs: bool = False          # OpenAI's `logprobs`: every chunk carries choices[0].logprobs
+    top_logprobs: int = 0           # OpenAI's `top_logprobs`, 0..20; needs logprobs
 
 
 def parse_chat_completion_request(body: dict) -> ChatRequest:
@@ -74,12 +78,23 @@ def parse_chat_completion_request(body: dict) -> ChatRequest:
         max_tokens = 16
     if not isinstance(max_tokens, int) or isinstance(max_tokens, bool) or max_tokens < 1:
         raise ProtocolError("max_tokens: positive integer required")
+    logprobs, top_logprobs = body.get("logprobs"), body.get("top_logprobs")
+    if logprobs is None:
+        logprobs = False
+    if not isinstance(logprobs, bool):
+        raise ProtocolError("logprobs: boolean required")
+    if top_logprobs is None:
+        top_logprobs = 0
+    if not isinstance(top_logprobs, int) or isinstance(top_logprobs, bool) or not 0 <= top_logprobs <= MAX_TOP_LOGPROBS:
+        raise ProtocolError(f"top_logprobs: integer 0..{MAX_TOP_LOGPROBS} required")
+    if top_logprobs > 0 and not logprobs:
+        raise ProtocolError("top_logprobs requires logprobs: true")
     try:
         png = base64.b64decode(images[0], validate=True) if images else None
     except Exception:
         raise ProtocolError("image_url: invalid base64")
     return ChatRequest(model=model, role=role, text=text, image_png=png, max_tokens=max_tokens,
-                       stream=bool(body.get("stream", False)))
+                       stream=bool(body.get("stream", False)), logprobs=logprobs, top_logprobs=top_logprobs)
 
 
 def render_llava_chat_prompt(role: str, content: str, bos_token: str = "<s>", eos_token: str = "</s>") -> str:
@@ -97,13 +112,36 @@ def _dumps(obj) -> str:
     return json.dumps(obj, separators=(",", ":"), ensure_ascii=False)      # pydantic's model_dump_json: compact, UTF-8
 
 
-def chat_stream_chunk(request_id: str, created: int, model: str, content: Optional[str], first: bool = False) -> str:
+def _finite_or_none(x: float):
+    """JSON has no literal for -inf / NaN (json.dumps would write the non-standard `-Infinity` / `NaN`): a logprob that
+    is not a finite number — a masked (-inf) logit, a row that held a NaN — is sent as null."""
+    return float(x) if math.isfinite(x) else None
+
+
+def _token_logprob(token: str, logprob: float) -> dict:
+    return {"token": token, "logprob": _finite_or_none(logprob), "bytes": list(token.encode("utf-8"))}
+
+
+def chat_logprobs(token: str, logprob: float, alternatives) -> dict:
+    """OpenAI's choices[0].logprobs for one generated token: {"content": [{token, logprob, bytes, top_logprobs:
+    [{token, logprob, bytes}, ...]}]}; alternatives: the (token text, logprob) pairs, most likely first."""
+    entry = _token_logprob(token, logprob)
+    entry["top_logprobs"] = [_token_logprob(t, lp) for t, lp in alternatives]
+    return {"content": [entry]}
+
+
+def chat_stream_chunk(request_id: str, created: int, model: str, content: Optional[str], first: bool = False,
+                      logprobs: Optional[dict] = None) -> str:
     """One `data:` line of the stream (api_server.py:119-146): the first chunk of a choice carries
     delta = {role: assistant, content: ""}, every other one delta = {content: text}; key order and `exclude_unset`
-    as pydantic emits them."""
+    as pydantic emits them.  logprobs: the chat_logprobs object of a request that asked for them (an extension: the
+    reference has no such field); without it the chunk is byte for byte what it always was."""
     delta = {"role": "assistant", "content": ""} if first else {"content": content}
+    choice = {"index": 0, "delta": delta}
+    if logprobs is not None:
+        choice["logprobs"] = logprobs
     return "data: " + _dumps({"id": request_id, "object": CHUNK_OBJECT, "created": created, "model": model,
-                              "choices": [{"index": 0, "delta": delta}]}) + "\n\n"
+                              "choices": [choice]}) + "\n\n"
 
 
 DONE = "data: [DONE]\n\n"

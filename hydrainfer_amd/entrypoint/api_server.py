@@ -32,6 +32,7 @@ class StreamOutputTokenProcessor(OutputTokenProcessor):
         self.loop, self.tokenizer = loop, tokenizer
         self.queue: asyncio.Queue = asyncio.Queue()
         self.n_tokens = 0
+        self.scores = None          # the TokenLogprob of the token the next append_token_id delivers (requests that asked)
         self.on_end: Optional[Callable[["StreamOutputTokenProcessor"], None]] = None     # set by the front end: its registry of live streams
         self.ended = False
 
@@ -52,10 +53,19 @@ class StreamOutputTokenProcessor(OutputTokenProcessor):
             self.fail(RuntimeError("the request was terminated by the engine"))
             return
         self.n_tokens += 1
-        self._put(self.tokenizer.decode(token_id))
+        text = self.tokenizer.decode(token_id)
+        if self.scores is not None:     # a request that asked for logprobs: (text, its OpenAI-shaped logprobs object)
+            entry, self.scores = self.scores, None
+            alternatives = [(self.tokenizer.decode(t) if t >= 0 else "", lp) for t, lp in entry.top]
+            self._put((text, proto.chat_logprobs(text, entry.logprob, alternatives)))
+        else:
+            self._put(text)
         if is_last_token:
             self._put(None)
             self._end()
+
+    def append_logprobs(self, entry) -> None:
+        self.scores = entry
 
     def fail(self, exc: BaseException) -> None:
         if not self.ended:
@@ -190,6 +200,8 @@ class RankEngineFrontend(EngineFrontend):
         self._index = 0
 
     def _start(self, request: TokenRequest, processor: StreamOutputTokenProcessor) -> None:
+        from hydrainfer_amd.engine.distributed import refuse_logprobs
+        refuse_logprobs(request)                      # ValueError: the rank protocol carries no log-probabilities
         self.engine.submit(request, processor, self.creator, self._index)
         self._index += 1
 
@@ -237,7 +249,9 @@ class ApiServer:
             import xxhash
             image_hash = xxhash.xxh64(req.image_png).intdigest() >> 1             # content hash: the prefix cache's image key
         return TokenRequest(request_id=next(self._ids), token_ids=token_ids, pixel_values=pixels, image_size=size,
-                            image_hash=image_hash, sampling_params=SamplingParameters(max_tokens=req.max_tokens))
+                            image_hash=image_hash,
+                            sampling_params=SamplingParameters(max_tokens=req.max_tokens, logprobs=req.logprobs,
+                                                               top_logprobs=req.top_logprobs))
 
     # ------------------------------------------------------------------ HTTP
     @staticmethod
@@ -336,7 +350,9 @@ class ApiServer:
                 if not first_sent:       # api_server.py:119-134: role chunk in front of the first text
                     await self._chunk(writer, proto.chat_stream_chunk(request_id, created, req.model, None, first=True))
                     first_sent = True
-                if item:                 # api_server.py:135: empty pieces are not sent
+                if isinstance(item, tuple):      # a request that asked for logprobs: every token has a chunk, its scores inside
+                    await self._chunk(writer, proto.chat_stream_chunk(request_id, created, req.model, item[0], logprobs=item[1]))
+                elif item:               # api_server.py:135: empty pieces are not sent
                     await self._chunk(writer, proto.chat_stream_chunk(request_id, created, req.model, item))
             await self._chunk(writer, proto.DONE)
         except (ConnectionError, asyncio.CancelledError):

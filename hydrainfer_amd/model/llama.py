@@ -20,7 +20,7 @@ from torch import Tensor
 
 from hydrainfer_amd._C.kernel.activation import silu_and_mul, silu_and_mul_slabs
 from hydrainfer_amd._C.kernel.norm import (StepHead, add_rms_norm, add_rms_norm_slabs, argmax_rows, decode_step_head,
-                                             embed_rms_norm, embed_rms_norm_supported, rms_norm)
+                                             embed_rms_norm, embed_rms_norm_supported, logprob_rows, rms_norm)
 from hydrainfer_amd._C.kernel.position_embedding import rope_set_kv_cache
 from hydrainfer_amd.layer.causal_attention import AttentionParameters
 from hydrainfer_amd._C.kernel.flash_attn import decode_attention_fused, mha_varlen_fwd
@@ -558,5 +558,13 @@ class LlamaForCausalLM:
             out = self.sample_out if (self.sample_out is not None and self.sample_out.shape == (logits.shape[0],)) else None
             return argmax_rows(logits, out)
         return torch.argmax(logits, dim=-1)
+
+    def forward_logprobs(self, input_ids_or_embeds, position_ids, model_params, top_k: int = 0, out=None):
+        """forward() for a step whose requests asked for log-probabilities: the same logits, then ONE launch that gives
+        the greedy ids (the same rule as forward's, so the tokens do not change), their log-softmax values and the top_k
+        alternatives — (ids, logprobs, top_ids, top_logprobs) of _C.kernel.norm.logprob_rows, views of one buffer (`out`).
+        Eager only: not part of the launch plan or the captured graphs."""
+        logits = self.forward_logits(input_ids_or_embeds, position_ids, model_params)
+        return logprob_rows(logits, top_k, out)
 
     __call__ = forward

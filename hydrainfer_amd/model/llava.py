@@ -35,4 +35,11 @@ class LlavaLanguageModel:
                 model_params: LanguageModelParameters) -> Tensor:
         return torch.argmax(self.forward_logits(input_ids, image_features, position_ids, model_params), dim=-1)
 
+    def forward_logprobs(self, input_ids: Tensor, image_features: Optional[Tensor], position_ids: Tensor,
+                         model_params: LanguageModelParameters, top_k: int = 0, out: Optional[Tensor] = None):
+        """forward() plus per-token log-probabilities: (ids, logprobs, top_ids, top_logprobs), one launch behind the
+        logits (hx_logprob_rows); ids follow the same rule as forward's argmax."""
+        from hydrainfer_amd._C.kernel.norm import logprob_rows
+        return logprob_rows(self.forward_logits(input_ids, image_features, position_ids, model_params), top_k, out)
+
     __call__ = forward

@@ -227,6 +227,18 @@ int hx_embed_rms_norm(void* h_out, void* x_out, const void* ids, int ids_are_int
                       int dtype, hx_stream stream);
 int hx_argmax_rows(int64_t* out, const void* logits, int64_t rows, int64_t n, int64_t ld, int dtype,
                    hx_stream stream);
+/* hx_logprob_rows: per-token log-probabilities of a step, one launch (extension; added WITHOUT raising HX_ABI_VERSION:
+ * nothing that existed changed).  Stands in for the greedy sampler of hydrainfer/model/llama.py:99-104 followed by
+ * torch.log_softmax(logits.float(), -1) and torch.topk.  logits: fp16 / bf16 [rows, n], row stride ld elements.  Per row:
+ *   ids[r]            the greedy token, bit-identical to hx_argmax_rows (NaN largest, ties to the smallest index);
+ *   logprobs[r]       logits[r, ids[r]] - logsumexp(logits[r, :n]), all arithmetic in fp32;
+ *   top_ids[r, :K], top_logprobs[r, :K]  (dense [rows, K], K = top_k in 0..20) the K largest entries ordered by value
+ *                     descending, then index ascending (a NaN before every number); entries past n: id -1, logprob -inf.
+ * A -inf logit has logprob -inf and leaves the rest of its row alone; a row that holds a NaN has every logprob NaN.
+ * top_ids / top_logprobs may be NULL when top_k == 0.  rows < 1, n < 1, ld < n, top_k outside 0..20: HX_ERR_SHAPE;
+ * fp32: HX_ERR_DTYPE; a missing pointer: HX_ERR_NULL — nothing is launched. */
+int hx_logprob_rows(int64_t* ids, float* logprobs, int32_t* top_ids, float* top_logprobs, const void* logits,
+                    int64_t rows, int64_t n, int64_t ld, int top_k, int dtype, hx_stream stream);
 /* The same product for M <= 32 with the activations held in REGISTERS (csrc/gemm_xreg.hip): a
  * workgroup spans the whole K of its split, so K <= 4096 needs ONE slab (no K split) and K = 11008
  * three instead of eleven — the fp32 slab traffic of a decode layer drops from 25 MB to 6.5 MB.
