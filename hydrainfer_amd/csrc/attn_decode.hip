@@ -306,16 +306,6 @@ inline int32_t decode_meta(const AttnParams& p) {      // attn_decode_kernel's h
 
 int g_ranked = 1;             // the RANKED form for big batches (hx_debug_set_option("decode_ranked", 0) = the static grid)
 
-int ranked_n_cus() {
-  static int n = [] {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-    return prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }();
-  return n;
-}
-
 template <typename T, int D>
 int launch_decode(const AttnParams& p, int batch, hipStream_t stream) {
   if (p.group > 255 || p.n_splits > 255) return HX_ERR_SHAPE;
@@ -339,7 +329,7 @@ int launch_decode(const AttnParams& p, int batch, hipStream_t stream) {
   // big batches, no key split, the step's rank descriptor at hand: (sequence, head) pairs in length-ranked snake order
   if (g_ranked && p.rank_desc && p.n_splits == 1 && (int64_t)batch * p.n_heads >= 768 && D <= 128) {
     AttnParams pp = p;
-    pp.n_cus = ranked_n_cus();
+    pp.n_cus = n_cus();
     const dim3 grid2(p.n_heads, batch);
     if (p.k_new || p.qkv_partial) hx::launcher(attn_decode_kernel<T, D, 4, true, true, true>, grid2, 256, 0, stream)(pp.k, pp.v, pp.cu_k, pp.cu_q, pp.block_table, pp.cu_block_lens, decode_meta(pp), pp.block_size, pp.rank_desc, pp);
     else hx::launcher(attn_decode_kernel<T, D, 4, true, false, true>, grid2, 256, 0, stream)(pp.k, pp.v, pp.cu_k, pp.cu_q, pp.block_table, pp.cu_block_lens, decode_meta(pp), pp.block_size, pp.rank_desc, pp);

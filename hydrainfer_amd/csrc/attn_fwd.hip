@@ -1111,16 +1111,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd32p_kernel(const AttnParams p)
   }
 }
 
-int fwd_n_cus() {
-  static int n = [] {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-    return prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }();
-  return n;
-}
-
 int g_fwd_ablate = 0;   // EXPERIMENTS builds: timing ablations of attn_fwd32_kernel (wrong results)
 
 unsigned long long* g_fwd_stamps = nullptr;   // EXPERIMENTS builds: hx_debug_fwd_stamps
@@ -1135,7 +1125,7 @@ int launch_fwd32(const AttnParams& p, int batch, hipStream_t stream) {
   const size_t lds = 2 * 64 * (2 * D + 2 * D) + 16;      // two tiles' K / V images + the workgroup's priority flag
   dim3 grid((unsigned)(p.total_q / 128 + batch), p.n_heads, 1);
   AttnParams pp = p;
-  pp.wg_priority = (p.total_q / 128) * (int64_t)p.n_heads > 2 * (int64_t)fwd_n_cus() ? 1 : 0;   // more than two workgroups per CU
+  pp.wg_priority = (p.total_q / 128) * (int64_t)p.n_heads > 2 * (int64_t)n_cus() ? 1 : 0;   // more than two workgroups per CU
   if (g_fwd_priority >= 0) pp.wg_priority = g_fwd_priority;
   if (p.total_q == 0) return HX_OK;
   const int per_item_priority = pp.wg_priority;
@@ -1143,9 +1133,9 @@ int launch_fwd32(const AttnParams& p, int batch, hipStream_t stream) {
   // 238 at equal priorities, 2048 of 4096 112.7 against 113.5, three processes each)
   if (g_fwd_priority < 0) pp.wg_priority = 1;
   pp.n_tile_slots = (int32_t)(p.total_q / 128 + batch);
-  pp.n_cus = fwd_n_cus();
+  pp.n_cus = n_cus();
   const int64_t total = (int64_t)pp.n_tile_slots * p.n_heads;
-  const int64_t g = std::min<int64_t>(total, 2 * (int64_t)fwd_n_cus());
+  const int64_t g = std::min<int64_t>(total, 2 * (int64_t)n_cus());
   // the workgroup's item table: the slot count in front of every group of 4 sequences, 12 words per round
   pp.seq_group = g_fwd_seq_group > 0 ? g_fwd_seq_group : (batch <= 4 ? 4 : 1);
   pp.cu_pairing = g_fwd_pairing;
@@ -1163,7 +1153,7 @@ int launch_fwd32(const AttnParams& p, int batch, hipStream_t stream) {
   // 33.4 persistent in its four settings, 3 x 683 of 704 27.7 / 26.6 against 28.0 - 28.6 / 27.3 - 27.7; 1 x 704, 192
   // items, 20.2 against 21.0: the table is built for little.  Long items gain from the first round on — 2048 new tokens of
   // 4096, one round: 113.6 us against 123.9 — through the pairing of long with short items on a CU.)
-  const bool worth_it = total > 4 * (int64_t)fwd_n_cus() || (total > fwd_n_cus() && p.max_seqlen_k >= 24 * 64);
+  const bool worth_it = total > 4 * (int64_t)n_cus() || (total > n_cus() && p.max_seqlen_k >= 24 * 64);
   if ((g_fwd_persistent == 2 || (g_fwd_persistent && PAGED && worth_it)) && 2 * (lds + table) <= 160 * 1024 &&
       4 * (3 * (size_t)batch + 2 + (size_t)rounds) <= 2 * 64 * (2 * D + 2 * D)) {
     const size_t lds = 2 * 64 * (2 * D + 2 * D) + 16 + table;

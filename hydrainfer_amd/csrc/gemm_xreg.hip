@@ -817,29 +817,53 @@ int g_row_major = 0;   // EXPERIMENTS builds (xreg_row_major): every 32-row laun
 int g_timeline = 0;      // diagnostic (xreg_timeline): phase time stamps of the NORM launches into their sync areas
 int g_force_wgs = 0;     // tuning: cap on workgroups per launch (0 = the CU count)
 
-constexpr int kKwSet[] = {4, 8, 16, 20, 22, 27, 29, 32, 40};
+int stagger_bits() {
+  return (g_stagger ? 1 : 0) | (g_no_producers == 1 ? 2 : 0) | (g_no_producers == 2 ? 4 : 0) | (g_timeline ? 8 : 0) | (g_row_major ? 16 : 0);
+}
 
+// ---- what is built -------------------------------------------------------------------------------------------
+// The instantiations of the two kernels by k-steps per wave (KW).  The plain product (EPI = 0, NORM = 0) is built
+// for every row; `norm` / `silu`: NORM = 1 / EPI = 1 are built too (wide kernel: the silu epilogue only behind the
+// norm).  round_kw, the dispatch below and the plan's predicates all read these tables — a new KW is one row.
+struct XregBuilt { int kw; bool norm, silu; };
+constexpr XregBuilt kNarrowBuilt[] = {{4, true, true},    {8, true, true},    {16, true, true},   {20, false, false}, {22, false, false},
+                                      {27, false, false}, {29, false, false}, {32, true, true},   {40, true, true}};
+constexpr XregBuilt kWideBuilt[] = {{2, true, false},   {4, true, false},   {8, true, false}, {10, false, false},
+                                    {11, false, false}, {14, false, false}, {16, true, true}, {20, true, false}};
+constexpr bool is_built(const XregBuilt& r, bool wide, int epi, int norm) {
+  return (!norm || r.norm) && (!epi || (r.silu && (norm || !wide)));
+}
+template <size_t n>
+const XregBuilt* find_built(const XregBuilt (&table)[n], int kw) {
+  for (const XregBuilt& r : table) if (r.kw == kw) return &r;
+  return nullptr;
+}
 int round_kw(int kw) {
-  for (int v : kKwSet) if (v >= kw) return v;
+  for (const XregBuilt& r : kNarrowBuilt) if (r.kw >= kw) return r.kw;
   return 0;
 }
+constexpr int wide_rg(int kw) { return kw == 20 ? 1 : 2; }      // row groups per work unit (the wide kernel's RG)
 
-int n_cus() {
-  static int n = [] {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-    return prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }();
-  return n;
-}
+// ---- the plan: ONE description of a launch; every entry point answers from it -------------------------------
+struct XregPlan {
+  int64_t M = 0, N = 0, K = 0;
+  bool gate_up = false;      // the packing: gate and up row groups interleaved (N = 2 * inter), never the extra split
+  bool wide = false;         // the kernel: gemm_xreg_wide_kernel (<= 64 rows) over the same packing, else gemm_xreg_kernel (<= 32)
+  bool valid = false;
+  int S = 0, KW = 0;         // the launch: K splits (the slabs of a plain product) and k-steps per wave
+  int pk_S = 0, pk_P = 0;    // the packing: its splits and k-steps per split (the wide kernel's splits are halves of those)
+  const XregBuilt* built = nullptr;      // the table row of KW
+};
 
-// (N, K) -> (splits, k-steps per wave).  The fewest splits whose per-wave share fits the register
-// budget (KW <= 32), or one more when fewer than 80 % of the CUs would get a workgroup and the extra
-// split fills more (one workgroup per CU: K = 11008 with N = 4096 runs 192 workgroups at 3 splits,
-// 256 at 4) without padding more than 4 % of the k-steps.
-// HX_XREG_S="K:S;K:S" overrides the split count per K (tuning).  Pack and launch both come here.
-void xreg_plan(int64_t N, int64_t K, int* S, int* KW, bool fewest_splits = false) {
+// The packing's (splits, k-steps per wave): the fewest splits whose per-wave share fits the register budget
+// (KW <= 40), or one more when fewer than 80 % of the CUs would get a workgroup and the extra split fills more (one
+// workgroup per CU: K = 11008 with N = 4096 runs 192 workgroups at 3 splits, 256 at 4) without padding more than 4 %
+// of the k-steps.  HX_XREG_S="K:S;K:S" overrides the split count per K (tuning).
+// The wide kernel's launch split s = (packing split s / 2, half s % 2) with half the k-steps per wave.
+XregPlan xreg_plan(int64_t M, int64_t N, int64_t K, bool gate_up, bool wide) {
+  XregPlan pl;
+  pl.M = M; pl.N = N; pl.K = K; pl.gate_up = gate_up; pl.wide = wide;
+  if (M < 1 || M > (wide ? 64 : 32) || N <= 0 || K <= 0 || N % (wide ? 32 : 16) || K % 32) return pl;
   const int total_ks = (int)(K >> 5);
   const int n_rg = (int)(N >> 4);
   const int s0 = (total_ks + 159) / 160;   // KW <= 40
@@ -852,7 +876,7 @@ void xreg_plan(int64_t N, int64_t K, int* S, int* KW, bool fewest_splits = false
     return s * ((n_rg + G - 1) / G);
   };
   int s = s0;
-  if (!fewest_splits) {   // the fused gate|up epilogue needs ONE split: it never takes the extra one
+  if (!gate_up) {   // the fused gate|up epilogue needs ONE split: it never takes the extra one
     // padded k-steps (per cent over the real ones) of a split count: what the padding waves re-read
     auto waste_pct = [&](int sc) {
       const int kw = kw_of(sc);
@@ -876,40 +900,87 @@ void xreg_plan(int64_t N, int64_t K, int* S, int* KW, bool fewest_splits = false
       q = semi + 1;
     }
   }
-  *KW = kw_of(s);
-  // the split size is 4*KW k-steps; the number of splits that actually hold data
-  *S = *KW > 0 ? (total_ks + 4 * *KW - 1) / (4 * *KW) : 0;
+  const int kwp = kw_of(s);
+  if (kwp <= 0) return pl;
+  pl.pk_P = 4 * kwp;
+  pl.pk_S = (total_ks + pl.pk_P - 1) / pl.pk_P;      // the splits that actually hold data
+  if (!wide) {
+    pl.S = pl.pk_S; pl.KW = kwp;
+    pl.built = find_built(kNarrowBuilt, kwp);
+  } else {
+    pl.KW = (kwp + 1) / 2;      // an odd packing count halves unevenly: 27 -> 14 + 13 (LLaVA-1.5-13B's down projection)
+    pl.built = find_built(kWideBuilt, pl.KW);
+    // only the last packing split can be partial, so the launch splits that hold k-steps are a prefix of their numbering
+    for (int q = 0; q < pl.pk_S; ++q) pl.S += std::min(pl.pk_P, total_ks - q * pl.pk_P) > 4 * pl.KW ? 2 : 1;
+  }
+  pl.valid = pl.built != nullptr;
+  return pl;
 }
 
-template <typename T, int MB, int KW, int EPI, int NORM = 0>
-int launch_kw(const XregParams& p, int S, hipStream_t stream) {
-  const int n_units = EPI ? (p.N >> 5) : (p.N >> 4);     // row groups, or gate/up pairs of them
-  const int per_unit = EPI ? 2 : 1;
-  const int cap = g_force_wgs > 0 ? g_force_wgs : n_cus();
-  int nb = cap / S;
-  if (nb < 1) nb = 1;
-  if (nb > n_units) nb = n_units;
-  int G = (n_units + nb - 1) / nb;
-  if (G * per_unit > kMaxG) {
+// Grid and dynamic LDS of the plan's launch (epi: with the silu epilogue) — what the launch uses, and what a
+// predicate asks when the answer depends on the device's CU count.
+struct XregGrid { int nb = 0, S = 0; size_t lds = 0; bool ok = false; };
+XregGrid xreg_grid(const XregPlan& pl, bool epi) {
+  XregGrid g;
+  const int per_unit = pl.wide ? wide_rg(pl.KW) : epi ? 2 : 1;      // row groups per work unit (narrow: a gate/up pair)
+  const int n_units = (int)(pl.N >> 4) / per_unit;
+  if (!pl.valid || n_units < 1) return g;
+  g.S = pl.wide && epi ? 1 : pl.S;                   // (wide silu: both K halves in one workgroup)
+  g.nb = (!pl.wide && g_force_wgs > 0 ? g_force_wgs : n_cus()) / g.S;
+  if (g.nb < 1) g.nb = 1;
+  if (g.nb > n_units) g.nb = n_units;
+  if (pl.wide) {
+    g.lds = 2 * per_unit * 4 * 4 * 1024;             // two tile sets x RG row groups x four waves x MB tiles of 1 KiB
+    if (epi) g.lds += (size_t)((n_units + g.nb - 1) / g.nb) * per_unit * 4 * 1024;      // + a unit's reduced tiles (first K half) per unit of a workgroup
+    g.ok = g.lds <= 150 * 1024;      // (on a smaller or partitioned device the units per workgroup grow)
+  } else {
     // the kernel derives its share from gridDim.x (ceil((n_units - b) / nb) units) and keeps one LDS tile set per
     // row group: a share past kMaxG row groups would index LDS beyond the allocation, so the grid grows instead
     // (more workgroups than CUs; they run in rounds)
-    G = kMaxG / per_unit;
-    nb = (n_units + G - 1) / G;
+    int G = (n_units + g.nb - 1) / g.nb;
+    if (G * per_unit > kMaxG) {
+      G = kMaxG / per_unit;
+      g.nb = (n_units + G - 1) / G;
+    }
+    // (one workgroup per CU even when the last round is partial: its short shares go to the first workgroups of the
+    // grid, which are the late starters of a NORM launch — see the kernel)
+    g.lds = (size_t)G * per_unit * 4 * (size_t)((pl.M + 15) / 16) * 1024;
+    g.ok = ((n_units + g.nb - 1) / g.nb) * per_unit <= kMaxG;
   }
-  if (((n_units + nb - 1) / nb) * per_unit > kMaxG) return HX_ERR_SHAPE;   // cannot happen: nb >= n_units / G
-  // (one workgroup per CU even when the last round is partial: its short shares go to the first workgroups of the
-  // grid, which are the late starters of a NORM launch — see the kernel)
-  const size_t lds = (size_t)G * per_unit * 4 * MB * 1024;
+  return g;
+}
+
+// ---- what a plan can do, each written once --------------------------------------------------------------------
+int64_t slab_bytes(const XregPlan& pl) { return pl.valid ? (int64_t)pl.S * pl.M * pl.N * (int64_t)sizeof(float) : 0; }
+// add + RMSNorm in the launch: K in ONE split of the packing, rows of <= 2048 (wide: 1024) x 8 elements
+bool norm_ok(const XregPlan& pl) { return pl.valid && pl.built->norm && pl.pk_S == 1 && pl.K / 8 <= (pl.wide ? 1024 : 2048); }
+// silu(gate) * up in the launch, <= 32 rows: the whole K in the workgroup
+bool silu_ok(const XregPlan& pl) {
+  return pl.valid && !pl.wide && pl.gate_up && pl.N % 64 == 0 && pl.built->silu && pl.S == 1 && xreg_grid(pl, true).ok;
+}
+// the same behind the norm at 33 .. 64 rows: one packing split of two full halves (K = 4096), and the LDS the launch would ask for
+bool wide_silu_ok(const XregPlan& pl) {
+  return norm_ok(pl) && pl.wide && pl.M > 32 && pl.gate_up && pl.N % 64 == 0 && pl.built->silu && pl.S == 2 &&
+         pl.pk_P == 2 * 4 * pl.KW && xreg_grid(pl, true).ok;
+}
+// does a gate|up weight of the one-entry interface keep its halves interleaved?  (hx_decode_weight_plan and _pack)
+bool dw_interleaved(int64_t N, int64_t K, int flags) {
+  return (flags & HX_DW_GATE_UP) && N % 32 == 0 && silu_ok(xreg_plan(32, N, K, true, false));
+}
+
+// ---- launches --------------------------------------------------------------------------------------------------
+template <typename T, int MB, int KW, int EPI, int NORM>
+int launch_kw(const XregParams& p, const XregGrid& g, hipStream_t stream) {
+  const size_t lds = g.lds;
   if (lds > 48 * 1024) {
     hipError_t e = hipFuncSetAttribute((const void*)gemm_xreg_kernel<T, MB, KW, EPI, 0, NORM>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return hip_rc(e);
   }
-  const dim3 grid((unsigned)nb, (unsigned)S);
+  const dim3 grid((unsigned)g.nb, (unsigned)g.S);
   XregHot h;
-  if (!xreg_hot<NORM>(p, (unsigned)nb, &h)) return HX_ERR_SHAPE;
-  if (NORM && S != 1) return HX_ERR_SHAPE;
+  if (!xreg_hot<NORM>(p, (unsigned)g.nb, &h)) return HX_ERR_SHAPE;
+  if (NORM && g.S != 1) return HX_ERR_SHAPE;
 #define HX_XREG_LAUNCH(...) hx::launcher(gemm_xreg_kernel<__VA_ARGS__>, grid, 256, lds, stream)(h.p0, h.p1, h.p2, h.p3, h.p4, h.a, h.b, h.c, h.ldx, p)
   if constexpr (EPI == 0 && NORM == 0 && MB == 2 && (KW == 32 || KW == 29)) if (g_dbg) {   // ablation variants (tools/bench_gemm_xreg.py OPTS=xreg_dbg=..)
     if (g_dbg == 1) HX_XREG_LAUNCH(T, MB, KW, 0, 1);
@@ -930,98 +1001,93 @@ int launch_kw(const XregParams& p, int S, hipStream_t stream) {
   return check_launch();
 }
 
-template <typename T, int MB, int EPI, int NORM = 0>
-int launch_mb(const XregParams& p, int S, int KW, hipStream_t stream) {
-  switch (KW) {
-    case 4: return launch_kw<T, MB, 4, EPI, NORM>(p, S, stream);
-    case 8: return launch_kw<T, MB, 8, EPI, NORM>(p, S, stream);
-    case 16: return launch_kw<T, MB, 16, EPI, NORM>(p, S, stream);
-    case 20: if constexpr (EPI == 0 && NORM == 0) return launch_kw<T, MB, 20, 0>(p, S, stream); else return HX_ERR_SHAPE;
-    case 22: if constexpr (EPI == 0 && NORM == 0) return launch_kw<T, MB, 22, 0>(p, S, stream); else return HX_ERR_SHAPE;
-    case 27: if constexpr (EPI == 0 && NORM == 0) return launch_kw<T, MB, 27, 0>(p, S, stream); else return HX_ERR_SHAPE;
-    case 29: if constexpr (EPI == 0 && NORM == 0) return launch_kw<T, MB, 29, 0>(p, S, stream); else return HX_ERR_SHAPE;
-    case 32: return launch_kw<T, MB, 32, EPI, NORM>(p, S, stream);
-    case 40: return launch_kw<T, MB, 40, EPI, NORM>(p, S, stream);
-    default: return HX_ERR_SHAPE;
-  }
-}
-
-template <int EPI, int NORM = 0>
-int launch_any(const XregParams& p, int S, int KW, int dtype, hipStream_t stream) {
-  const int MB = (p.M + 15) / 16;
-  if (dtype == HX_F16) return MB == 1 ? launch_mb<F16, 1, EPI, NORM>(p, S, KW, stream) : launch_mb<F16, 2, EPI, NORM>(p, S, KW, stream);
-  return MB == 1 ? launch_mb<BF16, 1, EPI, NORM>(p, S, KW, stream) : launch_mb<BF16, 2, EPI, NORM>(p, S, KW, stream);
-}
-
-// ---- 33 .. 64 rows: the wide kernel over the SAME packing (its splits are halves of the packing's) ----------
-// (N, K, how the weight was packed) -> the launch's (splits, k-steps per wave, k-steps per packed split); KW = 0: no
-bool wide_plan(int64_t N, int64_t K, bool gate_up_packing, int* S, int* KW, int* pkP, int* S_packed) {
-  if (N <= 0 || K <= 0 || N % 32 || K % 32) return false;
-  int sp, kwp;
-  xreg_plan(N, K, &sp, &kwp, gate_up_packing);
-  if (kwp <= 0) return false;
-  const int kw = (kwp + 1) / 2;      // an odd packing count halves unevenly: 27 -> 14 + 13 (LLaVA-1.5-13B's down projection)
-  if (kw != 2 && kw != 4 && kw != 8 && kw != 10 && kw != 11 && kw != 14 && kw != 16 && kw != 20) return false;   // the built instantiations
-  const int total_ks = (int)(K >> 5);
-  // launch split s = (packing split s / 2, half s % 2); only the last packing split can be partial, so the splits that
-  // hold k-steps are a prefix of that numbering
-  int n = 0;
-  for (int q = 0; q < sp; ++q) {
-    const int nks_p = std::min(4 * kwp, total_ks - q * 4 * kwp);
-    n += nks_p > 4 * kw ? 2 : 1;
-  }
-  *KW = kw; *pkP = 4 * kwp; *S = n; *S_packed = sp;
-  return true;
-}
-
-constexpr int wide_rg(int kw) { return kw == 20 ? 1 : 2; }      // row groups per work unit (the kernel's RG)
-
-template <typename T, int KW, int NORM, int EPI = 0>
-int launch_wide_kw(const XregParams& p, int S, hipStream_t stream) {
+template <typename T, int KW, int EPI, int NORM>
+int launch_wide_kw(const XregParams& p, const XregGrid& g, hipStream_t stream) {
   constexpr int RG = wide_rg(KW);
-  const int n_units = (int)(p.N >> 4) / RG;
-  if (EPI) S = 1;                                    // both K halves in one workgroup
-  int nb = n_cus() / S;
-  if (nb < 1) nb = 1;
-  if (nb > n_units) nb = n_units;
-  size_t lds = 2 * RG * 4 * 4 * 1024;                // two tile sets x RG row groups x four waves x MB tiles of 1 KiB
-  if (EPI) lds += (size_t)((n_units + nb - 1) / nb) * RG * 4 * 1024;      // + a unit's reduced tiles (first K half) per unit of a workgroup
-  if (lds > 150 * 1024) return HX_ERR_SHAPE;
   {   // up to 64 KiB (EPI: + 8 KiB per unit) of dynamic LDS: above the default limit (per device, so not cached in a static)
     hipError_t e = hipFuncSetAttribute((const void*)gemm_xreg_wide_kernel<T, KW, NORM, RG, EPI>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds);
     if (e != hipSuccess) return hip_rc(e);
   }
   XregHot h;
-  if (!xreg_hot<NORM>(p, (unsigned)nb, &h)) return HX_ERR_SHAPE;
-  hx::launcher(gemm_xreg_wide_kernel<T, KW, NORM, RG, EPI>, dim3((unsigned)nb, (unsigned)S), 256, lds, stream)(
+  if (!xreg_hot<NORM>(p, (unsigned)g.nb, &h)) return HX_ERR_SHAPE;
+  hx::launcher(gemm_xreg_wide_kernel<T, KW, NORM, RG, EPI>, dim3((unsigned)g.nb, (unsigned)g.S), 256, g.lds, stream)(
       h.p0, h.p1, h.p2, h.p3, h.p4, h.a, h.b, h.c, h.ldx, p);
   return check_launch();
 }
 
-template <int NORM>
-int launch_wide(const XregParams& p, int S, int KW, int dtype, hipStream_t stream) {
-#define HX_W(KWV)                                                                                   \
-  case KWV: return dtype == HX_F16 ? launch_wide_kw<F16, KWV, NORM>(p, S, stream) : launch_wide_kw<BF16, KWV, NORM>(p, S, stream)
-  switch (KW) {
-    HX_W(2); HX_W(4); HX_W(8); HX_W(16); HX_W(20);
-    case 14: if constexpr (NORM == 0) return dtype == HX_F16 ? launch_wide_kw<F16, 14, 0>(p, S, stream) : launch_wide_kw<BF16, 14, 0>(p, S, stream); else return HX_ERR_SHAPE;
-    case 10: if constexpr (NORM == 0) return dtype == HX_F16 ? launch_wide_kw<F16, 10, 0>(p, S, stream) : launch_wide_kw<BF16, 10, 0>(p, S, stream); else return HX_ERR_SHAPE;
-    case 11: if constexpr (NORM == 0) return dtype == HX_F16 ? launch_wide_kw<F16, 11, 0>(p, S, stream) : launch_wide_kw<BF16, 11, 0>(p, S, stream); else return HX_ERR_SHAPE;
-    default: return HX_ERR_SHAPE;
-  }
-#undef HX_W
+// f(integral_constant<i>) for the row i of `table` whose k-step count is kw; HX_ERR_SHAPE when there is none
+template <size_t n, typename F, size_t... I>
+int with_built_row(const XregBuilt (&table)[n], int kw, F&& f, std::index_sequence<I...>) {
+  int rc = HX_ERR_SHAPE;
+  (void)((table[I].kw == kw && ((rc = f(std::integral_constant<size_t, I>{})), true)) || ...);
+  return rc;
+}
+template <size_t n, typename F>
+int with_built_row(const XregBuilt (&table)[n], int kw, F&& f) { return with_built_row(table, kw, f, std::make_index_sequence<n>{}); }
+
+template <typename T, int EPI, int NORM>
+int launch_t(const XregParams& p, const XregPlan& pl, const XregGrid& g, hipStream_t stream) {
+  if (pl.wide)
+    return with_built_row(kWideBuilt, pl.KW, [&](auto i) -> int {
+      constexpr XregBuilt r = kWideBuilt[decltype(i)::value];
+      if constexpr (is_built(r, true, EPI, NORM)) return launch_wide_kw<T, r.kw, EPI, NORM>(p, g, stream);
+      else return HX_ERR_SHAPE;
+    });
+  return with_built_row(kNarrowBuilt, pl.KW, [&](auto i) -> int {
+    constexpr XregBuilt r = kNarrowBuilt[decltype(i)::value];
+    if constexpr (!is_built(r, false, EPI, NORM)) return HX_ERR_SHAPE;
+    else return pl.M <= 16 ? launch_kw<T, 1, r.kw, EPI, NORM>(p, g, stream) : launch_kw<T, 2, r.kw, EPI, NORM>(p, g, stream);
+  });
 }
 
-bool xreg_ok(int64_t M, int64_t N, int64_t K) {
-  if (M < 1 || M > 64 || N <= 0 || K <= 0 || N % 16 || K % 32) return false;
-  int S, KW;
-  if (M > 32) {
-    int pkP, sp;
-    return wide_plan(N, K, false, &S, &KW, &pkP, &sp);
+// THE launch path: a plain product returns its slab count, the silu epilogue HX_OK (or either a negative HX_ERR_*)
+template <int EPI, int NORM>
+int xreg_launch(const XregParams& p, const XregPlan& pl, int dtype, hx_stream stream) {
+  const XregGrid g = xreg_grid(pl, EPI);
+  if (!g.ok) return HX_ERR_SHAPE;
+  const int rc = dtype == HX_F16 ? launch_t<F16, EPI, NORM>(p, pl, g, (hipStream_t)stream)
+                                 : launch_t<BF16, EPI, NORM>(p, pl, g, (hipStream_t)stream);
+  return rc || EPI ? rc : pl.S;
+}
+
+// ---- arguments -------------------------------------------------------------------------------------------------
+// the add + RMSNorm in front of a product (hx_add_rms_norm_slabs): what the four norm-fused entries take
+struct NormIn {
+  void* residual; const float* slabs; int32_t n_splits; const void* weight; float eps; void* x_frag; void* sync;
+};
+
+// Everything is zero / null but what the plan and the caller give.  Plain: x as passed; norm-fused: x is produced
+// fragment-major INSIDE the launch.  partial or act is null (a plain product / the silu epilogue).
+XregParams xreg_params(const XregPlan& pl, const void* packed, float* partial, void* act, const void* x, int64_t ldx,
+                       int x_fragment_major, const NormIn* nm = nullptr) {
+  XregParams p{};
+  p.w = packed; p.partial = partial; p.act = act;
+  p.M = (int)pl.M; p.N = (int)pl.N; p.K = (int)pl.K;
+  p.stagger = stagger_bits();
+  if (pl.wide) { p.interleaved = pl.gate_up ? 1 : 0; p.pk_P = pl.pk_P; }
+  p.x = x; p.ldx = ldx; p.x_packed = x_fragment_major ? 1 : 0;
+  if (nm) {
+    p.x = nm->x_frag; p.ldx = pl.K; p.x_packed = 1;
+    p.nm_partial = nm->slabs; p.nm_residual = nm->residual; p.nm_weight = nm->weight; p.sync = (uint32_t*)nm->sync;
+    p.nm_splits = nm->n_splits; p.nm_eps = nm->eps;
   }
-  xreg_plan(N, K, &S, &KW);
-  return KW > 0;
+  return p;
+}
+
+// The checks of every launch entry in the ABI's order of precedence: a null pointer, the shape, the dtype, a
+// misaligned pointer, the workspace.
+int check_args(std::initializer_list<const void*> ptrs, bool shape_ok, int dtype, int64_t have_bytes = 0, int64_t need_bytes = 0) {
+  for (const void* q : ptrs) if (!q) return HX_ERR_NULL;
+  if (!shape_ok) return HX_ERR_SHAPE;
+  if (dtype != HX_F16 && dtype != HX_BF16) return HX_ERR_DTYPE;
+  for (const void* q : ptrs) if (!aligned16(q)) return HX_ERR_STRIDE;
+  return have_bytes < need_bytes ? HX_ERR_WORKSPACE : HX_OK;
+}
+int check_norm_args(const void* out, const void* packed, const NormIn& nm, bool shape_ok, int dtype, int64_t have_bytes = 0,
+                    int64_t need_bytes = 0) {
+  return check_args({out, packed, nm.residual, nm.slabs, nm.weight, nm.x_frag, nm.sync}, nm.n_splits >= 1 && shape_ok, dtype,
+                    have_bytes, need_bytes);
 }
 
 }  // namespace
@@ -1038,64 +1104,16 @@ int xreg_set_option(const char* name, int value) {
 }
 }  // namespace hx
 
-namespace {
-int stagger_bits() {
-  return (g_stagger ? 1 : 0) | (g_no_producers == 1 ? 2 : 0) | (g_no_producers == 2 ? 4 : 0) | (g_timeline ? 8 : 0) | (g_row_major ? 16 : 0);
-}
-
-// plain product of <= 64 rows over a packing (plain or gate|up-interleaved) with the wide kernel; returns the slab count
-int wide_product(float* partial, const void* x, const void* packed, int64_t M, int64_t N, int64_t K, int64_t ldx,
-                 int x_fragment_major, bool gate_up_packing, int dtype, hipStream_t stream) {
-  int S, KW, pkP, sp;
-  if (!wide_plan(N, K, gate_up_packing, &S, &KW, &pkP, &sp)) return HX_ERR_SHAPE;
-  XregParams p;
-  p.x = x; p.w = packed; p.partial = partial; p.ldx = ldx; p.act = nullptr;
-  p.M = (int)M; p.N = (int)N; p.K = (int)K; p.stagger = stagger_bits(); p.x_packed = x_fragment_major ? 1 : 0;
-  p.nm_partial = nullptr; p.nm_residual = nullptr; p.nm_weight = nullptr; p.sync = nullptr; p.nm_splits = 0; p.nm_eps = 0.f;
-  p.interleaved = gate_up_packing ? 1 : 0; p.pk_P = pkP;
-  const int rc = launch_wide<0>(p, S, KW, dtype, stream);
-  return rc ? rc : S;
-}
-
-// add + RMSNorm fused in front of it (K in ONE packed split)
-int wide_norm_product(float* partial, void* residual, const float* slabs_in, int32_t n_splits_in, const void* norm_weight,
-                      float epsilon, void* x_frag, const void* packed, int64_t M, int64_t N, int64_t K, void* sync,
-                      bool gate_up_packing, int dtype, hipStream_t stream, void* act = nullptr) {
-  int S, KW, pkP, sp;
-  if (!wide_plan(N, K, gate_up_packing, &S, &KW, &pkP, &sp) || sp != 1 || K % 8 || K / 8 > 1024) return HX_ERR_SHAPE;
-  XregParams p;
-  p.x = x_frag; p.w = packed; p.partial = partial; p.ldx = K; p.act = act;
-  p.M = (int)M; p.N = (int)N; p.K = (int)K; p.stagger = stagger_bits(); p.x_packed = 1;
-  p.nm_partial = slabs_in; p.nm_residual = residual; p.nm_weight = norm_weight; p.sync = (uint32_t*)sync;
-  p.nm_splits = n_splits_in; p.nm_eps = epsilon; p.interleaved = gate_up_packing ? 1 : 0; p.pk_P = pkP;
-  if (act) {      // silu * mul in the launch: both K halves in one workgroup (gemm_xreg_wide_kernel, EPI = 1)
-    if (KW != 16 || S != 2 || pkP != 2 * 4 * KW || !gate_up_packing) return HX_ERR_SHAPE;
-    return dtype == HX_F16 ? launch_wide_kw<F16, 16, 1, 1>(p, S, stream) : launch_wide_kw<BF16, 16, 1, 1>(p, S, stream);
-  }
-  const int rc = launch_wide<1>(p, S, KW, dtype, stream);
-  return rc ? rc : S;
-}
-}  // namespace
-
-extern "C" int hx_linear_decode_xreg_supported(int64_t M, int64_t N, int64_t K) { return xreg_ok(M, N, K) ? 1 : 0; }
+// ---- the plain product: <= 32 rows the narrow kernel, 33 .. 64 the wide one over the same packing ---------------
+extern "C" int hx_linear_decode_xreg_supported(int64_t M, int64_t N, int64_t K) { return xreg_plan(M, N, K, false, M > 32).valid ? 1 : 0; }
 
 extern "C" int hx_linear_decode_xreg_splits(int64_t N, int64_t K) {
-  if (N <= 0 || N % 16 || K <= 0 || K % 32) return HX_ERR_SHAPE;
-  int S, KW;
-  xreg_plan(N, K, &S, &KW);
-  return KW > 0 ? S : HX_ERR_SHAPE;
+  const XregPlan pl = xreg_plan(1, N, K, false, false);
+  return pl.valid ? pl.S : HX_ERR_SHAPE;
 }
 
 extern "C" int64_t hx_linear_decode_xreg_workspace_bytes(int64_t M, int64_t N, int64_t K) {
-  if (!xreg_ok(M, N, K)) return 0;
-  int S, KW;
-  if (M > 32) {
-    int pkP, sp;
-    wide_plan(N, K, false, &S, &KW, &pkP, &sp);
-  } else {
-    xreg_plan(N, K, &S, &KW);
-  }
-  return (int64_t)S * M * N * (int64_t)sizeof(float);
+  return slab_bytes(xreg_plan(M, N, K, false, M > 32));
 }
 
 extern "C" int64_t hx_fragment_major_elems(int64_t rows, int64_t K) {
@@ -1105,198 +1123,104 @@ extern "C" int64_t hx_fragment_major_elems(int64_t rows, int64_t K) {
 
 extern "C" int hx_pack_decode_weight_xreg(void* packed, const void* weight, int64_t N, int64_t K, int64_t ldw,
                                           int interleave_halves, int dtype, hx_stream stream) {
-  if (!packed || !weight) return HX_ERR_NULL;
-  if (N <= 0 || K <= 0 || N % 16 || K % 32 || ldw % 8) return HX_ERR_SHAPE;
-  if (interleave_halves && N % 32) return HX_ERR_SHAPE;
-  if (dtype != HX_F16 && dtype != HX_BF16) return HX_ERR_DTYPE;
-  if (!aligned16(packed) || !aligned16(weight)) return HX_ERR_STRIDE;
-  int S, KW;
-  xreg_plan(N, K, &S, &KW, interleave_halves != 0);
-  if (KW <= 0) return HX_ERR_SHAPE;
+  const XregPlan pl = xreg_plan(1, N, K, interleave_halves != 0, false);
+  if (int rc = check_args({packed, weight}, pl.valid && ldw % 8 == 0 && !(interleave_halves && N % 32), dtype)) return rc;
   const int64_t n_pieces = N * K / 8;
   hx::launcher(pack_xreg_kernel, (unsigned)((n_pieces + 255) / 256), 256, 0, (hipStream_t)stream)(
-      (u16*)packed, (const u16*)weight, n_pieces, (int)(K >> 5), (int)(N >> 4), ldw, 4 * KW, interleave_halves ? 1 : 0);
+      (u16*)packed, (const u16*)weight, n_pieces, (int)(K >> 5), (int)(N >> 4), ldw, pl.pk_P, interleave_halves ? 1 : 0);
   return check_launch();
 }
 
 extern "C" int hx_linear_decode_partial_xreg(float* partial, const void* x, const void* packed_weight,
                                              int64_t M, int64_t N, int64_t K, int64_t ldx, int x_fragment_major,
                                              int64_t partial_bytes, int dtype, hx_stream stream) {
-  if (!partial || !x || !packed_weight) return HX_ERR_NULL;
-  if (!xreg_ok(M, N, K) || (!x_fragment_major && ldx % 8)) return HX_ERR_SHAPE;
-  if (dtype != HX_F16 && dtype != HX_BF16) return HX_ERR_DTYPE;
-  if (!aligned16(x) || !aligned16(packed_weight) || !aligned16(partial)) return HX_ERR_STRIDE;
-  if (partial_bytes < hx_linear_decode_xreg_workspace_bytes(M, N, K)) return HX_ERR_WORKSPACE;
-  if (M > 32) return wide_product(partial, x, packed_weight, M, N, K, ldx, x_fragment_major, false, dtype, (hipStream_t)stream);
-  int S, KW;
-  xreg_plan(N, K, &S, &KW);
-  XregParams p;
-  p.x = x; p.w = packed_weight; p.partial = partial; p.ldx = ldx; p.act = nullptr;
-  p.M = (int)M; p.N = (int)N; p.K = (int)K; p.stagger = stagger_bits(); p.x_packed = x_fragment_major ? 1 : 0;
-  p.nm_partial = nullptr; p.nm_residual = nullptr; p.nm_weight = nullptr; p.sync = nullptr; p.nm_splits = 0; p.nm_eps = 0.f; p.interleaved = 0; p.pk_P = 0;
-  const int rc = launch_any<0>(p, S, KW, dtype, (hipStream_t)stream);
-  return rc ? rc : S;
+  const XregPlan pl = xreg_plan(M, N, K, false, M > 32);
+  if (int rc = check_args({partial, x, packed_weight}, pl.valid && (x_fragment_major || ldx % 8 == 0), dtype, partial_bytes, slab_bytes(pl))) return rc;
+  return xreg_launch<0, 0>(xreg_params(pl, packed_weight, partial, nullptr, x, ldx, x_fragment_major), pl, dtype, stream);
 }
 
+// ---- gate|up + silu*mul in one launch (<= 32 rows) ---------------------------------------------------------------
 extern "C" int hx_gate_up_silu_xreg_supported(int64_t M, int64_t inter, int64_t K) {
-  if (M > 32 || !xreg_ok(M, 2 * inter, K) || inter % 32) return 0;   // (the fused epilogue needs the whole K in the workgroup)
-  int S, KW;
-  xreg_plan(2 * inter, K, &S, &KW, true);
-  return S == 1 && (KW == 4 || KW == 8 || KW == 16 || KW == 32 || KW == 40) ? 1 : 0;   // the fused epilogue is built for these
+  return silu_ok(xreg_plan(M, 2 * inter, K, true, false)) ? 1 : 0;
 }
 
 extern "C" int hx_gate_up_silu_xreg(void* act, const void* x, const void* packed_gate_up, int64_t M,
                                     int64_t inter, int64_t K, int64_t ldx, int x_fragment_major, int dtype,
                                     hx_stream stream) {
-  if (!act || !x || !packed_gate_up) return HX_ERR_NULL;
-  if (!hx_gate_up_silu_xreg_supported(M, inter, K) || (!x_fragment_major && ldx % 8)) return HX_ERR_SHAPE;
-  if (dtype != HX_F16 && dtype != HX_BF16) return HX_ERR_DTYPE;
-  if (!aligned16(x) || !aligned16(packed_gate_up) || !aligned16(act)) return HX_ERR_STRIDE;
-  int S, KW;
-  xreg_plan(2 * inter, K, &S, &KW, true);
-  XregParams p;
-  p.x = x; p.w = packed_gate_up; p.partial = nullptr; p.ldx = ldx; p.act = act;
-  p.M = (int)M; p.N = (int)(2 * inter); p.K = (int)K; p.stagger = stagger_bits(); p.x_packed = x_fragment_major ? 1 : 0;
-  p.nm_partial = nullptr; p.nm_residual = nullptr; p.nm_weight = nullptr; p.sync = nullptr; p.nm_splits = 0; p.nm_eps = 0.f; p.interleaved = 0; p.pk_P = 0;
-  return launch_any<1>(p, 1, KW, dtype, (hipStream_t)stream);
+  const XregPlan pl = xreg_plan(M, 2 * inter, K, true, false);
+  if (int rc = check_args({act, x, packed_gate_up}, silu_ok(pl) && (x_fragment_major || ldx % 8 == 0), dtype)) return rc;
+  return xreg_launch<1, 0>(xreg_params(pl, packed_gate_up, nullptr, act, x, ldx, x_fragment_major), pl, dtype, stream);
 }
 
 // ---- add + RMSNorm fused in front of the product (one launch instead of two) --------------------
-static bool norm_kw_ok(int S, int KW) { return S == 1 && (KW == 4 || KW == 8 || KW == 16 || KW == 32 || KW == 40); }
-
 extern "C" int hx_norm_xreg_supported(int64_t M, int64_t N, int64_t K, int gate_up) {
-  if (gate_up) return hx_gate_up_silu_xreg_supported(M, N / 2, K);   // same condition: one split, a built k-step count
-  if (!xreg_ok(M, N, K)) return 0;
-  if (M > 32) {          // wide kernel: K must sit in ONE split of the packing, rows of <= 4096 x 2 elements
-    int S, KW, pkP, sp;
-    return wide_plan(N, K, false, &S, &KW, &pkP, &sp) && sp == 1 && K % 8 == 0 && K / 8 <= 1024 && KW != 10 && KW != 11 && KW != 14 ? 1 : 0;
-  }
-  int S, KW;
-  xreg_plan(N, K, &S, &KW);
-  return norm_kw_ok(S, KW) && K % 8 == 0 && K / 8 <= 2048 ? 1 : 0;
-}
-
-static int norm_args_ok(const void* residual, const float* slabs, int32_t n_splits, const void* weight, const void* x_frag,
-                        const void* sync) {
-  if (!residual || !slabs || !weight || !x_frag || !sync) return HX_ERR_NULL;
-  if (n_splits < 1) return HX_ERR_SHAPE;
-  if (!aligned16(residual) || !aligned16(slabs) || !aligned16(weight) || !aligned16(x_frag) || !aligned16(sync)) return HX_ERR_STRIDE;
-  return HX_OK;
+  if (gate_up) return hx_gate_up_silu_xreg_supported(M, N / 2, K);   // (a silu row of the table is a norm row, one split <= 5120 elements)
+  return norm_ok(xreg_plan(M, N, K, false, M > 32)) ? 1 : 0;
 }
 
 extern "C" int hx_norm_linear_decode_xreg(float* partial, void* residual, const float* slabs_in, int32_t n_splits_in,
                                           const void* norm_weight, float epsilon, void* x_frag,
                                           const void* packed_weight, int64_t M, int64_t N, int64_t K, void* sync,
                                           int64_t partial_bytes, int dtype, hx_stream stream) {
-  if (!partial || !packed_weight) return HX_ERR_NULL;
-  int rc = norm_args_ok(residual, slabs_in, n_splits_in, norm_weight, x_frag, sync);
-  if (rc) return rc;
-  if (!hx_norm_xreg_supported(M, N, K, 0)) return HX_ERR_SHAPE;
-  if (dtype != HX_F16 && dtype != HX_BF16) return HX_ERR_DTYPE;
-  if (!aligned16(packed_weight) || !aligned16(partial)) return HX_ERR_STRIDE;
-  if (partial_bytes < hx_linear_decode_xreg_workspace_bytes(M, N, K)) return HX_ERR_WORKSPACE;
-  if (M > 32) return wide_norm_product(partial, residual, slabs_in, n_splits_in, norm_weight, epsilon, x_frag, packed_weight, M, N, K,
-                                       sync, false, dtype, (hipStream_t)stream);
-  int S, KW;
-  xreg_plan(N, K, &S, &KW);
-  XregParams p;
-  p.x = x_frag; p.w = packed_weight; p.partial = partial; p.ldx = K; p.act = nullptr;
-  p.M = (int)M; p.N = (int)N; p.K = (int)K; p.stagger = stagger_bits(); p.x_packed = 1;
-  p.nm_partial = slabs_in; p.nm_residual = residual; p.nm_weight = norm_weight; p.sync = (uint32_t*)sync;
-  p.nm_splits = n_splits_in; p.nm_eps = epsilon; p.interleaved = 0; p.pk_P = 0;
-  rc = launch_any<0, 1>(p, S, KW, dtype, (hipStream_t)stream);
-  return rc ? rc : S;
+  const NormIn nm{residual, slabs_in, n_splits_in, norm_weight, epsilon, x_frag, sync};
+  const XregPlan pl = xreg_plan(M, N, K, false, M > 32);
+  if (int rc = check_norm_args(partial, packed_weight, nm, norm_ok(pl), dtype, partial_bytes, slab_bytes(pl))) return rc;
+  return xreg_launch<0, 1>(xreg_params(pl, packed_weight, partial, nullptr, nullptr, 0, 1, &nm), pl, dtype, stream);
 }
 
 extern "C" int hx_norm_gate_up_silu_xreg(void* act, void* residual, const float* slabs_in, int32_t n_splits_in,
                                          const void* norm_weight, float epsilon, void* x_frag,
                                          const void* packed_gate_up, int64_t M, int64_t inter, int64_t K, void* sync,
                                          int dtype, hx_stream stream) {
-  if (!act || !packed_gate_up) return HX_ERR_NULL;
-  int rc = norm_args_ok(residual, slabs_in, n_splits_in, norm_weight, x_frag, sync);
-  if (rc) return rc;
-  if (!hx_norm_xreg_supported(M, 2 * inter, K, 1)) return HX_ERR_SHAPE;
-  if (dtype != HX_F16 && dtype != HX_BF16) return HX_ERR_DTYPE;
-  if (!aligned16(packed_gate_up) || !aligned16(act)) return HX_ERR_STRIDE;
-  int S, KW;
-  xreg_plan(2 * inter, K, &S, &KW, true);
-  XregParams p;
-  p.x = x_frag; p.w = packed_gate_up; p.partial = nullptr; p.ldx = K; p.act = act;
-  p.M = (int)M; p.N = (int)(2 * inter); p.K = (int)K; p.stagger = stagger_bits(); p.x_packed = 1;
-  p.nm_partial = slabs_in; p.nm_residual = residual; p.nm_weight = norm_weight; p.sync = (uint32_t*)sync;
-  p.nm_splits = n_splits_in; p.nm_eps = epsilon; p.interleaved = 0; p.pk_P = 0;
-  return launch_any<1, 1>(p, 1, KW, dtype, (hipStream_t)stream);
+  const NormIn nm{residual, slabs_in, n_splits_in, norm_weight, epsilon, x_frag, sync};
+  const XregPlan pl = xreg_plan(M, 2 * inter, K, true, false);
+  if (int rc = check_norm_args(act, packed_gate_up, nm, silu_ok(pl) && norm_ok(pl), dtype)) return rc;
+  return xreg_launch<1, 1>(xreg_params(pl, packed_gate_up, nullptr, act, nullptr, 0, 1, &nm), pl, dtype, stream);
 }
 
 // ---- the gate|up product WITHOUT the fused silu*mul, over the interleaved packing (batches of 33 .. 64 rows: x for
-// 64 rows needs two K splits per workgroup, silu*mul the whole K) — slabs in [gate | up] column order for
-// hx_silu_and_mul_slabs.  Optionally with the add + RMSNorm in front.
+// 64 rows needs two K splits per workgroup, silu*mul the whole K) — the wide kernel at every row count, slabs in
+// [gate | up] column order for hx_silu_and_mul_slabs.  Optionally with the add + RMSNorm in front.
 extern "C" int hx_gate_up_xreg_supported(int64_t M, int64_t inter, int64_t K, int with_norm) {
-  if (M < 1 || M > 64 || inter <= 0 || inter % 32 || K <= 0 || K % 32) return 0;
-  int S, KW, pkP, sp;
-  if (!wide_plan(2 * inter, K, true, &S, &KW, &pkP, &sp)) return 0;
-  if (with_norm && (sp != 1 || K % 8 || K / 8 > 1024 || KW == 10 || KW == 11 || KW == 14)) return 0;
-  return 1;
+  const XregPlan pl = xreg_plan(M, 2 * inter, K, true, true);
+  return pl.valid && inter % 32 == 0 && (!with_norm || norm_ok(pl)) ? 1 : 0;
 }
 
 extern "C" int64_t hx_gate_up_xreg_workspace_bytes(int64_t M, int64_t inter, int64_t K) {
-  int S, KW, pkP, sp;
-  if (M < 1 || M > 64 || !wide_plan(2 * inter, K, true, &S, &KW, &pkP, &sp)) return 0;
-  return (int64_t)S * M * 2 * inter * (int64_t)sizeof(float);
+  return slab_bytes(xreg_plan(M, 2 * inter, K, true, true));
 }
 
 extern "C" int hx_gate_up_xreg(float* partial, const void* x, const void* packed_gate_up, int64_t M, int64_t inter, int64_t K,
                                int64_t ldx, int x_fragment_major, int64_t partial_bytes, int dtype, hx_stream stream) {
-  if (!partial || !x || !packed_gate_up) return HX_ERR_NULL;
-  if (!hx_gate_up_xreg_supported(M, inter, K, 0) || (!x_fragment_major && ldx % 8)) return HX_ERR_SHAPE;
-  if (dtype != HX_F16 && dtype != HX_BF16) return HX_ERR_DTYPE;
-  if (!aligned16(x) || !aligned16(packed_gate_up) || !aligned16(partial)) return HX_ERR_STRIDE;
-  if (partial_bytes < hx_gate_up_xreg_workspace_bytes(M, inter, K)) return HX_ERR_WORKSPACE;
-  return wide_product(partial, x, packed_gate_up, M, 2 * inter, K, ldx, x_fragment_major, true, dtype, (hipStream_t)stream);
-}
-
-extern "C" int hx_gate_up_silu_wide_xreg_supported(int64_t M, int64_t inter, int64_t K) {
-  if (M < 33 || M > 64 || !hx_gate_up_xreg_supported(M, inter, K, 1)) return 0;
-  int S, KW, pkP, sp;
-  if (!wide_plan(2 * inter, K, true, &S, &KW, &pkP, &sp)) return 0;
-  if (!(KW == 16 && S == 2 && sp == 1 && pkP == 2 * 4 * KW)) return 0;      // one packing split of two full halves (K = 4096)
-  // the launch's LDS (launch_wide_kw, EPI = 1: 64 KiB + 8 KiB per unit of a workgroup) depends on the CU count of the
-  // device: on a smaller or partitioned one the units per workgroup grow — answer what the launch itself would (round-5
-  // ADVICE: the plan said yes, the launch HX_ERR_SHAPE, and the 33 .. 64-row step had no other path)
-  constexpr int RG = wide_rg(16);
-  const int n_units = (int)((2 * inter) >> 4) / RG;
-  const int nb = std::max(1, std::min(n_cus(), n_units));
-  const size_t lds = (size_t)2 * RG * 4 * 4 * 1024 + (size_t)((n_units + nb - 1) / nb) * RG * 4 * 1024;
-  return lds <= 150 * 1024 ? 1 : 0;
-}
-
-extern "C" int hx_norm_gate_up_silu_wide_xreg(void* act, void* residual, const float* slabs_in, int32_t n_splits_in,
-                                              const void* norm_weight, float epsilon, void* x_frag,
-                                              const void* packed_gate_up, int64_t M, int64_t inter, int64_t K, void* sync,
-                                              int dtype, hx_stream stream) {
-  if (!act || !packed_gate_up) return HX_ERR_NULL;
-  int rc = norm_args_ok(residual, slabs_in, n_splits_in, norm_weight, x_frag, sync);
-  if (rc) return rc;
-  if (!hx_gate_up_silu_wide_xreg_supported(M, inter, K)) return HX_ERR_SHAPE;
-  if (dtype != HX_F16 && dtype != HX_BF16) return HX_ERR_DTYPE;
-  if (!aligned16(packed_gate_up) || !aligned16(act)) return HX_ERR_STRIDE;
-  return wide_norm_product(nullptr, residual, slabs_in, n_splits_in, norm_weight, epsilon, x_frag, packed_gate_up, M, 2 * inter, K,
-                           sync, true, dtype, (hipStream_t)stream, act);
+  const XregPlan pl = xreg_plan(M, 2 * inter, K, true, true);
+  if (int rc = check_args({partial, x, packed_gate_up}, pl.valid && inter % 32 == 0 && (x_fragment_major || ldx % 8 == 0), dtype,
+                          partial_bytes, slab_bytes(pl))) return rc;
+  return xreg_launch<0, 0>(xreg_params(pl, packed_gate_up, partial, nullptr, x, ldx, x_fragment_major), pl, dtype, stream);
 }
 
 extern "C" int hx_norm_gate_up_xreg(float* partial, void* residual, const float* slabs_in, int32_t n_splits_in,
                                     const void* norm_weight, float epsilon, void* x_frag, const void* packed_gate_up,
                                     int64_t M, int64_t inter, int64_t K, void* sync, int64_t partial_bytes, int dtype,
                                     hx_stream stream) {
-  if (!partial || !packed_gate_up) return HX_ERR_NULL;
-  int rc = norm_args_ok(residual, slabs_in, n_splits_in, norm_weight, x_frag, sync);
-  if (rc) return rc;
-  if (!hx_gate_up_xreg_supported(M, inter, K, 1)) return HX_ERR_SHAPE;
-  if (dtype != HX_F16 && dtype != HX_BF16) return HX_ERR_DTYPE;
-  if (!aligned16(packed_gate_up) || !aligned16(partial)) return HX_ERR_STRIDE;
-  if (partial_bytes < hx_gate_up_xreg_workspace_bytes(M, inter, K)) return HX_ERR_WORKSPACE;
-  return wide_norm_product(partial, residual, slabs_in, n_splits_in, norm_weight, epsilon, x_frag, packed_gate_up, M, 2 * inter, K,
-                           sync, true, dtype, (hipStream_t)stream);
+  const NormIn nm{residual, slabs_in, n_splits_in, norm_weight, epsilon, x_frag, sync};
+  const XregPlan pl = xreg_plan(M, 2 * inter, K, true, true);
+  if (int rc = check_norm_args(partial, packed_gate_up, nm, inter % 32 == 0 && norm_ok(pl), dtype, partial_bytes, slab_bytes(pl))) return rc;
+  return xreg_launch<0, 1>(xreg_params(pl, packed_gate_up, partial, nullptr, nullptr, 0, 1, &nm), pl, dtype, stream);
+}
+
+// ---- the same with silu*mul in the launch (33 .. 64 rows): both K halves in one workgroup, no slabs ---------------
+extern "C" int hx_gate_up_silu_wide_xreg_supported(int64_t M, int64_t inter, int64_t K) {
+  return wide_silu_ok(xreg_plan(M, 2 * inter, K, true, true)) ? 1 : 0;
+}
+
+extern "C" int hx_norm_gate_up_silu_wide_xreg(void* act, void* residual, const float* slabs_in, int32_t n_splits_in,
+                                              const void* norm_weight, float epsilon, void* x_frag,
+                                              const void* packed_gate_up, int64_t M, int64_t inter, int64_t K, void* sync,
+                                              int dtype, hx_stream stream) {
+  const NormIn nm{residual, slabs_in, n_splits_in, norm_weight, epsilon, x_frag, sync};
+  const XregPlan pl = xreg_plan(M, 2 * inter, K, true, true);
+  if (int rc = check_norm_args(act, packed_gate_up, nm, wide_silu_ok(pl), dtype)) return rc;
+  return xreg_launch<1, 1>(xreg_params(pl, packed_gate_up, nullptr, act, nullptr, 0, 1, &nm), pl, dtype, stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1315,12 +1239,8 @@ extern "C" int hx_decode_weight_plan(hx_decode_weight* w, int64_t N, int64_t K, 
   w->N = N; w->K = K; w->dtype = dtype; w->flags = flags; w->max_rows = max_rows;
   // the activations-in-registers layout serves <= 32 rows always, 33 .. 64 rows where the wide kernel can read the same
   // packing (a gate|up weight keeps its halves interleaved then: the plain product un-interleaves its slab columns)
-  bool xreg = !force_lds && hx_linear_decode_xreg_supported(max_rows < 32 ? max_rows : 32, N, K) == 1;
-  if (xreg && max_rows > 32) {
-    int S, KW, pkP, sp;
-    const bool gu = (flags & HX_DW_GATE_UP) && N % 32 == 0 && hx_gate_up_silu_xreg_supported(32, N / 2, K) == 1;
-    xreg = wide_plan(N, K, gu, &S, &KW, &pkP, &sp);
-  }
+  const bool xreg = !force_lds && xreg_plan(std::min(max_rows, 32), N, K, false, false).valid &&
+                    (max_rows <= 32 || xreg_plan(max_rows, N, K, dw_interleaved(N, K, flags), true).valid);
   if (!xreg && (N % 16 || K % 256)) return HX_ERR_SHAPE;
   if ((flags & HX_DW_GATE_UP) && (!xreg || N % 32)) w->flags &= ~HX_DW_GATE_UP;   // no fused epilogue on this layout: halves stay in order
   w->layout = xreg ? HX_DW_XREG : HX_DW_LDS_SLICE;
@@ -1331,8 +1251,8 @@ extern "C" int hx_decode_weight_pack(hx_decode_weight* w, void* packed, const vo
   if (!w || !packed || !weight) return HX_ERR_NULL;
   int rc;
   if (w->layout == HX_DW_XREG) {
-    const int inter = (w->flags & HX_DW_GATE_UP) && hx_gate_up_silu_xreg_supported(w->max_rows < 32 ? w->max_rows : 32, w->N / 2, w->K) == 1;
-    if (!inter) w->flags &= ~HX_DW_GATE_UP;
+    const bool inter = dw_interleaved(w->N, w->K, w->flags);
+    if (!inter) w->flags &= ~HX_DW_GATE_UP;      // (K in more than one split: the plan kept the flag, the halves stay in order)
     rc = hx_pack_decode_weight_xreg(packed, weight, w->N, w->K, ldw, inter, w->dtype, stream);
   } else if (w->layout == HX_DW_LDS_SLICE) {
     rc = hx_pack_decode_weight(packed, weight, w->N, w->K, ldw, w->dtype, stream);

@@ -79,6 +79,18 @@ inline Launcher<P...> launcher(void (*kernel)(P...), dim3 grid, dim3 block, size
   return Launcher<P...>{kernel, grid, block, lds, stream};
 }
 
+// CUs of the current device, asked once.  Without a device 256, the MI355X's own count: the planning entries
+// (workspace sizes, split counts, "supported") answer on a machine that has none.
+inline int n_cus() {
+  static const int n = [] {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
+    return prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  }();
+  return n;
+}
+
 inline int64_t dtype_size(int dtype) {
   switch (dtype) {
     case HX_F32: return 4;
