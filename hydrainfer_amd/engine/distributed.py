@@ -45,6 +45,17 @@ def refuse_logprobs(request) -> None:
                          "(one engine process per GPU); use the single-process server or the offline engine")
 
 
+def refuse_penalties(request) -> None:
+    """Nor frequency / presence / repetition penalties: the wire format carries max_tokens and the end-of-sequence ids
+    only (rcb_to_wire), and the request's history of generated tokens would have to follow it from rank to rank.  A
+    request with the identity (0, 0, 1) passes."""
+    from hydrainfer_amd.sampling import is_penalized
+    sp = getattr(request, "sampling_params", None)
+    if sp is not None and is_penalized(sp):
+        raise ValueError(f"request {request.request_id}: sampling penalties are not available in multi-process serving "
+                         "(one engine process per GPU); use the single-process server or the offline engine")
+
+
 def rcb_to_wire(rcb: RequestControlBlock) -> dict:
     """Everything the next stage needs: the instructions from the current one on (a flat list —
     the linked chain would pickle recursively), the block tables + IPC handles of the caches, the
@@ -295,6 +306,7 @@ class RankEngine:
         ranks, text-only ones over the P ranks — two balancers, each with its own cursor); its tokens — sampled on
         whichever ranks run its prefill and decode — are delivered to `processor` on THIS rank."""
         refuse_logprobs(request)
+        refuse_penalties(request)
         self.token_handlers[request.request_id] = processor
         has_image = request.pixel_values is not None
         dst = entry_rank(self._n_submitted[has_image], self.roles, has_image, self.dead)

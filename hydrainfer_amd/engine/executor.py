@@ -12,7 +12,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from hydrainfer_amd._C.kernel.norm import logprob_rows_packed, logprob_rows_views
+from hydrainfer_amd._C.kernel.norm import logprob_rows, logprob_rows_packed, logprob_rows_views
 from hydrainfer_amd._lib import HydraHipError
 
 from hydrainfer_amd.engine import rcb as rcb_module
@@ -20,6 +20,7 @@ from hydrainfer_amd.engine.isa import Fill, TextFill
 from hydrainfer_amd.engine.parameters_builder import LanguageModelParametersBuilder
 from hydrainfer_amd.engine.rcb import BatchRequest, TokenLogprob
 from hydrainfer_amd.model.llama import LanguageModelParameters
+from hydrainfer_amd.sampling import NO_PENALTIES, pack_penalty_step, penalized_argmax_rows
 
 
 class PendingToken:
@@ -86,8 +87,10 @@ class BatchFillExecutor:
         bs = self.kv_manager.block_size
         pending_launch = self.pending[0] if self.pending is not None else None
         for rcb, inst in batch:
-            if len(inst.token_ids) != 1 or not inst.sample or rcb.sampling_params.logprobs:
-                return None                    # (a request that wants log-probabilities decodes eagerly: execute())
+            if (len(inst.token_ids) != 1 or not inst.sample or rcb.sampling_params.logprobs
+                    or rcb.penalty_history is not None):
+                return None                    # (a request that wants log-probabilities, or one under sampling
+                                               # penalties, decodes eagerly: execute())
             token = inst.token_ids[0]
             if isinstance(token, PendingToken):
                 if token.launch != pending_launch:
@@ -280,6 +283,8 @@ class BatchFillExecutor:
             if not inst.is_chunked:
                 rcb.metric.token_times.append(now)
                 rcb.output_token_ids.append(token)
+                if rcb.penalty_history is not None:
+                    rcb.penalty_history.append(token)           # generated tokens only: a chunk head's sample never gets here
                 if scores is not None and rcb.sampling_params.logprobs:
                     k = rcb.sampling_params.top_logprobs        # this request's own count out of the batch's largest
                     entry = TokenLogprob(token, scores[0][i - 1], list(zip(scores[1][i - 1][:k], scores[2][i - 1][:k])))
@@ -306,6 +311,41 @@ class BatchFillExecutor:
         if inputs.all_sequences_decode and rows != len(inputs.selected_token_ids):
             sel = inputs.selected_token_ids
             sampled, scores = [sampled[j] for j in sel], tuple([col[j] for j in sel] for col in scores)
+        return sampled, scores
+
+    def _sample_penalized(self, batch: BatchRequest, inputs, params, top_k: Optional[int]):
+        """The eager step of a batch in which some request is under frequency / presence / repetition penalties: the same
+        logits, then hx_penalized_argmax_rows in place of the argmax — ONE launch for the whole batch; the rows of
+        unpenalised requests ride along with an empty history and (0, 0, 1) and get the id they would have got.  The
+        step's (token, count) tables reach the device as one pinned buffer in one copy.  top_k: None, or the largest
+        top_logprobs of the batch's OTHER requests that asked for log-probabilities (no request has both): their scores
+        come from hx_logprob_rows over the same logits."""
+        sel, decode = inputs.selected_token_ids, inputs.all_sequences_decode
+        n_rows = inputs.input_ids.shape[0] if decode else len(sel)        # the rows of the logits
+        entries = [(None, NO_PENALTIES)] * n_rows
+        i = 0
+        for rcb, inst in batch:
+            if not isinstance(inst, Fill) or not inst.sample:
+                continue
+            if rcb.penalty_history is not None:
+                sp = rcb.sampling_params
+                entries[sel[i] if decode else i] = (rcb.penalty_history,
+                                                    (sp.frequency_penalty, sp.presence_penalty, sp.repetition_penalty))
+            i += 1
+        tables = pack_penalty_step(entries).to_device(self.device)
+        lm, scores = self.language_model, None
+        if top_k is None:
+            sampled = lm.forward_penalized(inputs.input_ids, inputs.image_features, inputs.position_ids, params,
+                                           *tables).tolist()                       # the step's only device sync
+        else:
+            logits = lm.forward_logits(inputs.input_ids, inputs.image_features, inputs.position_ids, params)
+            packed = logprob_rows_packed(logprob_rows(logits, top_k)[0], top_k)
+            sampled = penalized_argmax_rows(logits, *tables).tolist()
+            _, lp, top_ids, top_lp = logprob_rows_views(packed.cpu(), n_rows, top_k)
+            scores = (lp.tolist(), top_ids.tolist(), top_lp.tolist())
+        if decode and n_rows != len(sel):
+            sampled = [sampled[j] for j in sel]
+            scores = scores and tuple([col[j] for j in sel] for col in scores)
         return sampled, scores
 
     def _publish_prefix_blocks(self, batch: BatchRequest) -> None:
@@ -351,6 +391,9 @@ class BatchFillExecutor:
             return
         asking = [rcb.sampling_params.top_logprobs for rcb, inst in batch
                   if rcb.sampling_params.logprobs and isinstance(inst, Fill) and inst.sample and not inst.is_chunked]
+        if any(rcb.penalty_history is not None for rcb, inst in batch if isinstance(inst, Fill) and inst.sample):
+            self._deliver(batch, *self._sample_penalized(batch, inputs, params, max(asking) if asking else None))
+            return
         if asking:
             self._deliver(batch, *self._sample_with_logprobs(inputs, params, max(asking)))
             return

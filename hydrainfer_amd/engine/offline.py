@@ -36,6 +36,9 @@ class OfflineRequest:
     token_params: Optional[TokenParameters] = None     # token_pruning_policy='focal': the image as n_embed_output_tokens tokens
     logprobs: bool = False        # the log-probability of every generated token (such a request decodes eagerly)
     top_logprobs: int = 0         # and of its 0..20 most likely alternatives
+    frequency_penalty: float = 0.0      # the reference's process_logits steps 1-2 over the generated tokens
+    presence_penalty: float = 0.0       # (hydrainfer_amd/sampling); a penalised request decodes eagerly
+    repetition_penalty: float = 1.0
 
 
 class OfflineInferenceEngine:
@@ -81,7 +84,8 @@ class OfflineInferenceEngine:
                                    image_size=(r.image.size[1], r.image.size[0]) if r.image is not None else (0, 0),
                                    image_hash=compute_image_hash(r.image) if r.image is not None else 0,
                                    sampling_params=SamplingParameters(r.max_tokens, list(r.eos_token_ids), r.logprobs,
-                                                                      r.top_logprobs),
+                                                                      r.top_logprobs, r.frequency_penalty,
+                                                                      r.presence_penalty, r.repetition_penalty),
                                    token_params=r.token_params)
                 rcb = self.creator.process(req)
                 rcb.metric.arrival_time = time.perf_counter()

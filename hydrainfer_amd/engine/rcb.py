@@ -15,6 +15,12 @@ class SamplingParameters:
     eos_token_ids: List[int] = field(default_factory=list)
     logprobs: bool = False      # a TokenLogprob per generated token (OpenAI's `logprobs`); such a request decodes eagerly
     top_logprobs: int = 0       # 0..20 most likely alternatives in each of them; needs logprobs
+    # steps 1-2 of the reference's process_logits (hydrainfer/sampling/logits_processor.py:65-72) over the request's
+    # GENERATED tokens (hydrainfer_amd/sampling); (0, 0, 1) is the identity: such a request is sampled as before.  A
+    # penalised request decodes eagerly and cannot ask for logprobs.
+    frequency_penalty: float = 0.0      # subtracted once per earlier occurrence of a token
+    presence_penalty: float = 0.0       # subtracted once from every token that occurred
+    repetition_penalty: float = 1.0     # > 0: a token that occurred has its logit divided (if negative: multiplied) by it
 
 
 MAX_TOP_LOGPROBS = 20
@@ -116,6 +122,7 @@ class RequestControlBlock:
         self.output_token_processors: List[OutputTokenProcessor] = []
         self.output_token_ids: List[int] = []
         self.output_logprobs: List[TokenLogprob] = []     # parallel to output_token_ids when sampling_params.logprobs, else empty
+        self.penalty_history = None      # sampling.PenaltyHistory of a penalised request (its delivered tokens), else None
         self.scenario_type: Optional[ScenarioType] = None
         self.metric = RequestMetric()
         self.eos_hit = False      # set when a token read back late (decode look-ahead) was end-of-sequence

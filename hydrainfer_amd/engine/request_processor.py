@@ -11,6 +11,7 @@ from hydrainfer_amd.engine.isa import (EPMigrate, ImageEmbed, ImageEmbedFill, In
 from hydrainfer_amd.engine.rcb import (MAX_TOP_LOGPROBS, RequestControlBlock, RequestMetaData, SamplingParameters,
                                        ScenarioClassifier, TokenParameters)
 from hydrainfer_amd.memory.shared_cache import compute_hash
+from hydrainfer_amd.sampling import PenaltyHistory, check_penalties, is_penalized
 
 
 @dataclass
@@ -100,7 +101,17 @@ class InstructionCreator:
             raise ValueError(f"request {request.request_id}: top_logprobs {top!r} outside 0..{MAX_TOP_LOGPROBS}")
         if top > 0 and not sp.logprobs:
             raise ValueError(f"request {request.request_id}: top_logprobs = {top} needs logprobs = True")
-        rcb.sampling_params = SamplingParameters(sp.max_tokens, list(sp.eos_token_ids), sp.logprobs, top)
+        try:
+            penalties = check_penalties(sp.frequency_penalty, sp.presence_penalty, sp.repetition_penalty)
+        except ValueError as e:
+            raise ValueError(f"request {request.request_id}: {e}") from None
+        rcb.sampling_params = SamplingParameters(sp.max_tokens, list(sp.eos_token_ids), sp.logprobs, top, *penalties)
+        if is_penalized(rcb.sampling_params):
+            if sp.logprobs:
+                raise ValueError(f"request {request.request_id}: frequency / presence / repetition penalties cannot be "
+                                 "combined with logprobs yet: the score of a penalised choice needs the log-softmax "
+                                 "kernel to see the penalties, a follow-up change")
+            rcb.penalty_history = PenaltyHistory()
         if not self.ignore_eos:
             rcb.sampling_params.eos_token_ids.append(self.eos_token_id)
 

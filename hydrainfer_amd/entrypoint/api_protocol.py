@@ -32,6 +32,9 @@ class ChatRequest:
     stream: bool
     logprobs: bool = False          # OpenAI's `logprobs`: every chunk carries choices[0].logprobs
     top_logprobs: int = 0           # OpenAI's `top_logprobs`, 0..20; needs logprobs
+    frequency_penalty: float = 0.0  # OpenAI's `frequency_penalty`, -2..2
+    presence_penalty: float = 0.0   # OpenAI's `presence_penalty`, -2..2
+    repetition_penalty: float = 1.0 # extension (the reference's process_logits step 2): > 0, 1 = none
 
 
 def parse_chat_completion_request(body: dict) -> ChatRequest:
@@ -89,12 +92,28 @@ def parse_chat_completion_request(body: dict) -> ChatRequest:
         raise ProtocolError(f"top_logprobs: integer 0..{MAX_TOP_LOGPROBS} required")
     if top_logprobs > 0 and not logprobs:
         raise ProtocolError("top_logprobs requires logprobs: true")
+    penalties = {}
+    for name in ("frequency_penalty", "presence_penalty"):
+        v = body.get(name)
+        if v is None:
+            v = 0.0
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not -2.0 <= v <= 2.0:      # (a NaN fails the range)
+            raise ProtocolError(f"{name}: number in -2..2 required")
+        penalties[name] = float(v)
+    v = body.get("repetition_penalty")
+    if v is None:
+        v = 1.0
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v <= 0:
+        raise ProtocolError("repetition_penalty: number > 0 required")
+    penalties["repetition_penalty"] = float(v)
+    if logprobs and (penalties["frequency_penalty"] or penalties["presence_penalty"] or v != 1):
+        raise ProtocolError("logprobs cannot be combined with frequency / presence / repetition penalties yet")
     try:
         png = base64.b64decode(images[0], validate=True) if images else None
     except Exception:
         raise ProtocolError("image_url: invalid base64")
     return ChatRequest(model=model, role=role, text=text, image_png=png, max_tokens=max_tokens,
-                       stream=bool(body.get("stream", False)), logprobs=logprobs, top_logprobs=top_logprobs)
+                       stream=bool(body.get("stream", False)), logprobs=logprobs, top_logprobs=top_logprobs, **penalties)
 
 
 def render_llava_chat_prompt(role: str, content: str, bos_token: str = "<s>", eos_token: str = "</s>") -> str:

@@ -200,8 +200,9 @@ class RankEngineFrontend(EngineFrontend):
         self._index = 0
 
     def _start(self, request: TokenRequest, processor: StreamOutputTokenProcessor) -> None:
-        from hydrainfer_amd.engine.distributed import refuse_logprobs
+        from hydrainfer_amd.engine.distributed import refuse_logprobs, refuse_penalties
         refuse_logprobs(request)                      # ValueError: the rank protocol carries no log-probabilities
+        refuse_penalties(request)                     # nor sampling penalties
         self.engine.submit(request, processor, self.creator, self._index)
         self._index += 1
 
@@ -251,7 +252,10 @@ class ApiServer:
         return TokenRequest(request_id=next(self._ids), token_ids=token_ids, pixel_values=pixels, image_size=size,
                             image_hash=image_hash,
                             sampling_params=SamplingParameters(max_tokens=req.max_tokens, logprobs=req.logprobs,
-                                                               top_logprobs=req.top_logprobs))
+                                                               top_logprobs=req.top_logprobs,
+                                                               frequency_penalty=req.frequency_penalty,
+                                                               presence_penalty=req.presence_penalty,
+                                                               repetition_penalty=req.repetition_penalty))
 
     # ------------------------------------------------------------------ HTTP
     @staticmethod

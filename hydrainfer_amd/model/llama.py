@@ -567,4 +567,14 @@ class LlamaForCausalLM:
         logits = self.forward_logits(input_ids_or_embeds, position_ids, model_params)
         return logprob_rows(logits, top_k, out)
 
+    def forward_penalized(self, input_ids_or_embeds, position_ids, model_params, hist_ids, hist_counts, cu_hist, penalties,
+                          out=None):
+        """forward() for a step with a request under frequency / presence / repetition penalties: the same logits, then
+        ONE launch (sampling.penalized_argmax_rows) in place of argmax_rows — row r's (token, count) table is the CSR slice
+        cu_hist[r] .. cu_hist[r + 1], a row with an empty table gets forward()'s id.  Eager only: not part of the launch
+        plan or the captured graphs."""
+        from hydrainfer_amd.sampling import penalized_argmax_rows
+        logits = self.forward_logits(input_ids_or_embeds, position_ids, model_params)
+        return penalized_argmax_rows(logits, hist_ids, hist_counts, cu_hist, penalties, out)
+
     __call__ = forward

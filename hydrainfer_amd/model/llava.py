@@ -42,4 +42,14 @@ class LlavaLanguageModel:
         from hydrainfer_amd._C.kernel.norm import logprob_rows
         return logprob_rows(self.forward_logits(input_ids, image_features, position_ids, model_params), top_k, out)
 
+    def forward_penalized(self, input_ids: Tensor, image_features: Optional[Tensor], position_ids: Tensor,
+                          model_params: LanguageModelParameters, hist_ids: Tensor, hist_counts: Tensor, cu_hist: Tensor,
+                          penalties: Tensor, out: Optional[Tensor] = None) -> Tensor:
+        """forward() under frequency / presence / repetition penalties: one launch behind the logits
+        (hx_penalized_argmax_rows) with the rows' (token, count) tables as a CSR; a row with an empty table gets the id
+        forward's argmax gives."""
+        from hydrainfer_amd.sampling import penalized_argmax_rows
+        return penalized_argmax_rows(self.forward_logits(input_ids, image_features, position_ids, model_params),
+                                     hist_ids, hist_counts, cu_hist, penalties, out)
+
     __call__ = forward

@@ -239,6 +239,29 @@ int hx_argmax_rows(int64_t* out, const void* logits, int64_t rows, int64_t n, in
  * fp32: HX_ERR_DTYPE; a missing pointer: HX_ERR_NULL — nothing is launched. */
 int hx_logprob_rows(int64_t* ids, float* logprobs, int32_t* top_ids, float* top_logprobs, const void* logits,
                     int64_t rows, int64_t n, int64_t ld, int top_k, int dtype, hx_stream stream);
+/* hx_penalized_argmax_rows: greedy sampling under frequency, presence and repetition penalties, one launch and one read
+ * of the logits (extension; added WITHOUT raising HX_ABI_VERSION: nothing that existed changed).  Steps 1-2 of
+ * hydrainfer/sampling/logits_processor.py:65-72 followed by the argmax of hydrainfer/model/llama.py:99-104; steps 3-5
+ * there (temperature, top-k, top-p) never move the largest entry.  logits: fp16 / bf16 [rows, n], row stride ld elements,
+ * n <= 262144 (2^18: the row's bitmap in LDS, 32 KiB).  The history is a CSR — the reference's unique_token_ids /
+ * unique_token_counts / unique_token_lens without the padding: row r owns hist_ids[j], hist_counts[j] for
+ * cu_hist[r] <= j < cu_hist[r + 1] (cu_hist int32 [rows + 1], its values are held inside [0, total] by the kernel), the
+ * ids of a row pairwise distinct.  penalties: fp32 [rows, 3] = (frequency f, presence p, repetition r) per row.
+ * For a history entry (t, c) of row r, with x = (float)logits[r, t], each operation rounded to fp32 on its own, in the
+ * reference's order (bit-identical to torch's fp32 result):
+ *     s = x - (float)c * f;   s = s - (c > 0 ? p : 0);   s = s < 0 ? s * r : s / r
+ * every other element keeps its value.  ids[r]: the index of the first element in the order of hx_argmax_rows (a NaN
+ * first, then the larger value, then the lower index) — a row with an empty history gives hx_argmax_rows' answer bit for
+ * bit.  scores_out (fp32 [total], may be NULL): s of every history entry, in CSR order (the reference's `score`).
+ * An entry with t < 0 or t >= n is ignored: nothing is read for it, and its scores_out entry is NaN.  A token that
+ * appears twice in one row breaks the contract: the row's answer uses one of the two values, nothing is read or written
+ * out of bounds.  total == 0 is legal and returns HX_OK: every row is plain argmax, cu_hist is still read (all zeros),
+ * hist_ids / hist_counts may be NULL.  rows < 1, n < 1, ld < n, n > 262144, total < 0: HX_ERR_SHAPE; fp32:
+ * HX_ERR_DTYPE; ids, logits, cu_hist or penalties NULL, or hist_ids / hist_counts NULL with total > 0: HX_ERR_NULL —
+ * nothing is launched. */
+int hx_penalized_argmax_rows(int64_t* ids, float* scores_out, const void* logits, int64_t rows, int64_t n, int64_t ld,
+                             const int32_t* hist_ids, const int32_t* hist_counts, const int32_t* cu_hist, int64_t total,
+                             const float* penalties, int dtype, hx_stream stream);
 /* The same product for M <= 32 with the activations held in REGISTERS (csrc/gemm_xreg.hip): a
  * workgroup spans the whole K of its split, so K <= 4096 needs ONE slab (no K split) and K = 11008
  * three instead of eleven — the fp32 slab traffic of a decode layer drops from 25 MB to 6.5 MB.
