@@ -4,6 +4,8 @@ grids of the reference's tests/kernel/test_moe.py:7-158."""
 import pytest
 import torch
 
+from tests.rowwise_ref import misaligned
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
@@ -162,13 +164,6 @@ def test_unpermute_and_sum_out_streaming_forms_equal_the_scalar_forms(dtype):
     gating = torch.randn((n, n_exp), generator=g)
     weights, indices = gating.topk(topk, dim=-1)
     probs = weights.softmax(dim=-1).to(dtype).to(DEV)
-
-    def misaligned(t):
-        buf = torch.empty(t.numel() + 8, dtype=t.dtype, device=t.device)
-        v = buf[1:1 + t.numel()].view(t.shape)
-        v.copy_(t)
-        assert v.data_ptr() % 16 != 0 and v.is_contiguous()
-        return v
 
     p, rmap = permute_with_index_map(tokens, indices.to(torch.int32).to(DEV))
     fast = unpermute_with_index_map(p, rmap, probs)
