@@ -80,6 +80,19 @@ template <> struct Mfma32<BF16> {
   }
 };
 
+// One LDS-DMA instruction: 64 lanes x 16 bytes from the lanes' addresses to 1 KiB at LDS address `lds`.  Through
+// registers (global load, ds_write at the end of the tile) the K / V requests cost 8 of the 37 us of the 4 x 704 launch
+// (tools/ablate_attn_prefill32.py: "no tile loads"), this way 3.  Inline assembly: told about an LDS-DMA, hipcc waits
+// for it (vmcnt(0)) in front of every LDS read that follows — the reads of the OTHER image.
+// (m0 — the LDS address of the DMA — is a reserved register: naming it as clobbered is all that can be done, and
+// nothing else in these kernels uses it)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
+__device__ __forceinline__ void dma_flat(const void* addr, uint32_t lds) {
+  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" :: "v"(addr), "s"(lds) : "memory", "m0");
+}
+#pragma clang diagnostic pop
+
 // two workgroups per CU (LDS: 2 x 74 KiB): registers + accumulator registers must stay within 256,
 // or one wave per SIMD runs with nothing to hide its latencies behind (measured: 0.8 waves per SIMD
 // on average and 80 us for 4 x 704 tokens with the default bound)
@@ -87,26 +100,7 @@ template <> struct Mfma32<BF16> {
 // 4 no Q K product, 8 no tile staging and no barrier after the first tile, 16 no barrier, 32 no tile requests
 template <typename T, int D, bool PAGED, int ABL = 0>
 __global__ __launch_bounds__(256, 2) void attn_fwd32_kernel(const AttnParams p) {
-  constexpr int KS = D / 16;         // QK k-steps
-  constexpr int NDB = D / 32;        // 32-dim output blocks
-  constexpr int KT = 64;             // keys per tile (two 32-key sub-tiles)
-  // LDS images: UNPADDED rows of 2 D bytes with the 16-byte chunks XOR-swizzled per row — the tiles arrive by LDS-DMA
-  // (global_load_lds_dwordx4: 64 lanes x 16 bytes land contiguously, so a row cannot be padded; which chunk of its row
-  // a lane fetches is free).  Chunk c of row r sits at position c ^ kswz(r) in the K and Q images, c ^ vswz(r) in V:
-  //   K / Q, ds_read_b128 of chunk 2 ks + h of rows c = 0 .. 31 (16-lane groups {0-3,12-15,20-27}, ... on 64 banks,
-  //     MI355X_MICROARCH.md LDS): the 16 rows of a group need 16 different positions (D = 128: row & 15) resp. 8
-  //     different ones per row parity (D = 64, two rows per bank row: (row >> 1) & 7);
-  //   V, ds_read_b64_tr_b16 of rows q = 0 .. 3 x 64 bytes (32-lane groups): the four rows go to four different
-  //     64-byte quarters of the bank row (D = 128: (row & 3) << 2) resp. two different ones per row parity (D = 64).
-  constexpr int RSK = 2 * D, RSV = 2 * D;
-  constexpr int LPR = D / 8;
-  constexpr int NL = KT * LPR / 256;
-  constexpr int KTILE = KT * RSK, VTILE = KT * RSV;
-  constexpr int IMG = KTILE + VTILE;       // one tile: K image, V image; two of them
-  constexpr int TQ = 128;
-  extern __shared__ __attribute__((aligned(16))) char smem[];   // [2][K[KT][RSK] | V[KT][RSV]] | priority flag
-  auto kswz = [](int row) { return LPR == 16 ? (row & 15) : ((row >> 1) & 7); };
-  auto vswz = [](int row) { return LPR == 16 ? ((row & 3) << 2) : (((row >> 1) & 1) << 2); };
+#include "attn_fwd32_geom.inc"
   if (ABL == 256) return;                                        // the launch alone
 
   // Workgroup -> (sequence, query tile, head).  Compact grid (x = tile slots, y = heads) as in the
@@ -117,7 +111,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd32_kernel(const AttnParams p) 
   // (4 x 704 tokens: 49 -> see tools/bench_attn_prefill32.py).
   // the per-sequence index arrays through the scalar cache (uniform indices; as vector loads each was a ~1 us round
   // trip in a chain of five before the first K / V request could be formed)
-  typedef __attribute__((address_space(4))) const int32_t c_i32;
   c_i32* cu_q_s = (c_i32*)p.cu_q;
   c_i32* cu_k_s = (c_i32*)p.cu_k;
   int mblk = -1, h, b = 0;
@@ -194,10 +187,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd32_kernel(const AttnParams p) 
   const u16* vbase = reinterpret_cast<const u16*>(p.v) + (int64_t)hk * p.v_head_stride;
   const int32_t* bt = PAGED ? p.block_table + bt_off : nullptr;
 
-  // Staging map of a wave (Q here, K / V tiles below, O at the end): instruction j takes rows RPI j .. RPI j + RPI - 1
-  // of the wave's block, D / 8 lanes per row — the whole row contiguous.
-  constexpr int RPI = 64 / LPR;         // rows per instruction
-  const int st_r4 = lane / LPR;         // row RPI j + st_r4
+  const int st_r4 = lane / LPR;         // staging map: row RPI j + st_r4 of the wave's block
   const int st_ch = lane % LPR;         // 16-byte chunk of the row
   const int shift = kv_len - q_len;
   const int limit_c = p.causal ? min(kv_len - 1, q_row0 + c + shift) : kv_len - 1;
@@ -205,13 +195,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd32_kernel(const AttnParams p) 
   const int last_key_wg = p.causal ? min(kv_len - 1, min(q_row0_wg + TQ - 1, q_len - 1) + shift) : kv_len - 1;
   const int n_tiles = (last_key_wg >= 0) ? last_key_wg / KT + 1 : 0;
 
-  // ---- tile staging by LDS-DMA.  Wave w stages the tile's keys 16 w .. 16 w + 15 (a 16-key group never straddles a
-  // page: block_size % 16 == 0), instruction j its rows RPI j .. RPI j + RPI - 1 — D / 8 lanes per row, 1 KiB of the
-  // image per instruction and cache, every cache line touched by one instruction.  Through registers (global load,
-  // ds_write at the end of the tile) the same requests cost 8 of the 37 us of the 4 x 704 launch
-  // (tools/ablate_attn_prefill32.py: "no tile loads"), this way 3.  The loads are inline assembly: told about an LDS-DMA,
-  // hipcc waits for it (vmcnt(0)) in front of every LDS read that follows — the reads of the OTHER image.
-  static_assert(NL * RPI == 16 && RPI * RSK == 1024, "a wave stages one 16-key group, 1 KiB per instruction");
+  // ---- tile staging by LDS-DMA (dma_flat).
   // Page of my keys in the tile that will be requested next.  A wave stages ONE 16-key group, hence one page: the
   // table entry is read through the SCALAR cache, in front of the barrier (a scalar load shares its counter with the
   // LDS reads and returns out of order — while one is outstanding every LDS read is waited for singly).
@@ -244,18 +228,10 @@ __global__ __launch_bounds__(256, 2) void attn_fwd32_kernel(const AttnParams p) 
       const uint32_t r = (uint32_t)min(R, r_max);                  // rows past the last key repeat it
       const u16* ka = kbase + kb + r * (uint32_t)p.k_row_stride + 8 * (st_ch ^ kswz(R));
       const u16* va = vbase + vb + r * (uint32_t)p.v_row_stride + 8 * (st_ch ^ vswz(R));
-      // (m0 — the LDS address of the DMA — is a reserved register: naming it as clobbered is all that can be done, and
-      // nothing else in this kernel uses it)
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-      asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" :: "v"(ka), "s"(kd + 1024u * j) : "memory", "m0");
-      asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" :: "v"(va), "s"(vd + 1024u * j) : "memory", "m0");
-#pragma clang diagnostic pop
+      dma_flat(ka, kd + 1024u * j);
+      dma_flat(va, vd + 1024u * j);
     }
   };
-  auto tiles_landed = [&]() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };
-  using Set0 = std::integral_constant<int, 0>;
-  using Set1 = std::integral_constant<int, 1>;
 
   f32x16 acc[NDB];
 #pragma unroll
@@ -276,21 +252,20 @@ __global__ __launch_bounds__(256, 2) void attn_fwd32_kernel(const AttnParams p) 
   // straight into the fragment layout every instruction took 32 bytes of each of 32 rows.
   u16x8 qf[KS];
   {
-    constexpr int RSO = RSK;
-    char* qb = smem + IMG + w * 32 * RSO;
+    char* qb = smem + IMG + w * 32 * RSK;
     const u16* qbase = reinterpret_cast<const u16*>(p.q) + (int64_t)h * D + 8 * st_ch;
-    u16x8 qrow[32 / RPI];
+    u16x8 qrow[NQI];
 #pragma unroll
-    for (int j = 0; j < 32 / RPI; ++j) {
+    for (int j = 0; j < NQI; ++j) {
       const int qr = max(q_row0 + RPI * j + st_r4, 0);
       if (ABL == 512) qrow[j] = u16x8{(u16)(0x3c00 + lane), 0x3800, 0x3400, 0x3000, 0x2c00, 0x2800, (u16)(0x2400 + j), 0x2000};
       else qrow[j] = *reinterpret_cast<const u16x8*>(qbase + (int64_t)(q_start + qr) * p.q_row_stride);
     }
 #pragma unroll
-    for (int j = 0; j < 32 / RPI; ++j)
-      *reinterpret_cast<u16x8*>(qb + (RPI * j + st_r4) * RSO + 16 * (st_ch ^ kswz(RPI * j + st_r4))) = qrow[j];
+    for (int j = 0; j < NQI; ++j)
+      *reinterpret_cast<u16x8*>(qb + (RPI * j + st_r4) * RSK + 16 * (st_ch ^ kswz(RPI * j + st_r4))) = qrow[j];
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) qf[ks] = *reinterpret_cast<const u16x8*>(qb + c * RSO + 16 * ((2 * ks + hi) ^ kswz(c)));
+    for (int ks = 0; ks < KS; ++ks) qf[ks] = *reinterpret_cast<const u16x8*>(qb + c * RSK + 16 * ((2 * ks + hi) ^ kswz(c)));
   }
   if (n_tiles > 0) tiles_landed();
   // The two workgroups of a CU at DIFFERENT priorities.  At equal priority two waves of a SIMD that happen to be in
@@ -309,134 +284,13 @@ __global__ __launch_bounds__(256, 2) void attn_fwd32_kernel(const AttnParams p) 
   __syncthreads();
   if (queued && *prio_flag) __builtin_amdgcn_s_setprio(3);
 
-  // transposed-read lane address inside a 4-row x 32-dim block: lane 4q + pp of each 16-lane group
-  // supplies row q, dims 16 half + 4 pp .. + 3 (half = which 16 of the 32 dims this group takes)
-  const int tr_q = (lane & 15) >> 2, tr_pp = lane & 3, tr_half = (lane >> 4) & 1;
-  const int tr_off = (4 * hi + tr_q) * RSV + (16 * tr_half + 4 * tr_pp) * 2;      // + 64 * (db ^ tr_x): the swizzled quarter
-  const int tr_x = vswz(tr_q) >> 2;
-
+#include "attn_fwd32_lane.inc"
   auto tile_step = [&](int t, auto par_tag) {
     constexpr int PAR = decltype(par_tag)::value;       // t & 1: this tile's LDS image
-    const int cur = (ABL & 8) ? 0 : PAR;
+    const int img_cur = (ABL & 8) ? 0 : PAR;
     if (!(ABL & (8 | 32)) && t + 1 < n_tiles) request_tile(t + 1, 1 - PAR);   // lands under this tile's arithmetic
-    if (t * KT <= last_key_wave) {
-      const char* kt = smem + cur * IMG;
-      const char* vt = kt + KTILE;
-      f32x16 s[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s[u][r] = 0.f;
-      {
-        // all K fragments of sub-tile 0 are requested before its first MFMA, those of sub-tile 1
-        // under sub-tile 0's MFMAs: no MFMA waits for a read issued just before it
-        const char* krd = kt + c * RSK;
-        const int kz = kswz(c);
-        u16x8 kfa[KS], kfb[KS];
-        if (ABL & 4) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) { s[0][r] = 0.01f * (r + lane); s[1][r] = 0.02f * (r + t); }
-        } else {
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) kfa[ks] = *reinterpret_cast<const u16x8*>(krd + 16 * ((2 * ks + hi) ^ kz));
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-          kfb[ks] = *reinterpret_cast<const u16x8*>(krd + 32 * RSK + 16 * ((2 * ks + hi) ^ kz));
-          s[0] = Mfma32<T>::mma(kfa[ks], qf[ks], s[0]);
-        }
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) s[1] = Mfma32<T>::mma(kfb[ks], qf[ks], s[1]);
-        // keep that order: left alone the scheduler issues read, wait, MFMA, read, wait, MFMA (fewest registers)
-        __builtin_amdgcn_sched_group_barrier(0x100, KS, 0);
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, KS, 0);
-        }
-      }
-      const bool interior = t * KT + KT - 1 <= min(kv_len - 1, p.causal ? q_row0 + shift : kv_len - 1);
-      float mx = HX_NEG_BIG;
-      u16x8 pf[2][2];
-      if (ABL & 1) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) pf[u][r >> 3][r & 7] = T::from_float(s[u][r]);
-        l += 1.f;
-      } else {
-      if (interior) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[u][r]);
-      } else {
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int key = t * KT + 32 * u + (r & 3) + 8 * (r >> 2) + 4 * hi;
-            if (key > limit_c) s[u][r] = -INFINITY;
-            mx = fmaxf(mx, s[u][r]);
-          }
-      }
-      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-      // Lazy running maximum: a row keeps its reference m until a score exceeds it by more than 2^8 (the exponentials
-      // then stay below 256: exact in fp32, eight mantissa bits as ever in T) — with the exact maximum as reference some
-      // row of the 32 moved in nearly every tile and all 64 accumulator registers were rescaled every time (PMC: 33
-      // v_pk_mul per wave and tile).  O = acc / l is unchanged in exact arithmetic: both carry the same factor.
-      const float m_cand = fmaxf(m, mx * p.scale_log2);
-      const bool grow = m_cand > m + 8.0f;
-      float m_new = m;
-      if (__builtin_amdgcn_ballot_w64(grow)) {
-        m_new = grow ? m_cand : m;
-        const float alpha = fast_exp2(m - m_new);      // 1 for the rows that keep their reference
-        l *= alpha;
-#pragma unroll
-        for (int i = 0; i < NDB; ++i)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[i][r] *= alpha;
-        m = m_new;
-      }
-      // (single-instruction fma / add: a packed f32 instruction beside MFMAs costs more than the two it replaces —
-      // MI355X_MICROARCH.md, per-instruction constants; the file is compiled without the SLP vectorizer for the same reason)
-      float pa = 0.f, pb = 0.f;
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; r += 2) {
-          const float e0 = fast_exp2(fmaf(s[u][r], p.scale_log2, -m_new));
-          const float e1 = fast_exp2(fmaf(s[u][r + 1], p.scale_log2, -m_new));
-          pa += e0;
-          pb += e1;
-          pf[u][r >> 3][r & 7] = T::from_float(e0);
-          pf[u][r >> 3][(r & 7) + 1] = T::from_float(e1);
-        }
-      l += pa + pb;
-      }
-      if (ABL & 2) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-          for (int k2 = 0; k2 < 2; ++k2) acc[0][u * 2 + k2] += __builtin_bit_cast(float, (uint32_t)pf[u][k2][0] << 16);
-      } else
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int k2 = 0; k2 < 2; ++k2) {
-          const char* vrd = vt + (32 * u + 16 * k2) * RSV + tr_off;
-#pragma unroll
-          for (int db = 0; db < NDB; ++db) {
-            const u16x4 lo = lds_tr_read(vrd + 64 * (db ^ tr_x));
-            const u16x4 hh = lds_tr_read(vrd + 8 * RSV + 64 * (db ^ tr_x));
-            u16x8 vf;
-            vf[0] = lo[0]; vf[1] = lo[1]; vf[2] = lo[2]; vf[3] = lo[3];
-            vf[4] = hh[0]; vf[5] = hh[1]; vf[6] = hh[2]; vf[7] = hh[3];
-            acc[db] = Mfma32<T>::mma(vf, pf[u][k2], acc[db]);
-          }
-        }
-    }
+    auto half_max = [](float x) { return fmaxf(x, __shfl_xor(x, 32, 64)); };      // max with lane ^ 32
+#include "attn_fwd32_tile.inc"
     if (!(ABL & 8)) {
       if (!(ABL & 32)) lookup_page(min(t + 2, t_last));       // the table entry for the next request, in front of the barrier's wait
       tiles_landed();                                        // this wave's part of tile t+1 is in LDS
@@ -449,19 +303,10 @@ __global__ __launch_bounds__(256, 2) void attn_fwd32_kernel(const AttnParams p) 
   }
 
   if (ABL == 79 && acc[0][0] != 123.f) return;   // (1039 = 1024 + 15: empty loop, epilogue without its LDS reads)                   // everything but the epilogue
-  // epilogue: O[query c][dim 32 db + 8 (r >> 2) + 4 hi + (r & 3)] = acc[db][r] / L
+  // epilogue: acc / L, through LDS so that a store instruction writes whole rows (swizzle: attn_fwd32_geom.inc, o_from_lds)
   float lr = l + __shfl_xor(l, 32, 64);
   const float inv = (lr > 0.f) ? 1.0f / lr : 0.f;
-  // Through LDS (the K / V images are free: every wave has passed the last tile's barrier), so that a store
-  // instruction writes whole rows: straight from the accumulator layout each instruction put 16 bytes into each of 32
-  // rows — sixteen such instructions per wave, ~10 us of the 4 x 704 launch by themselves
-  // (tools/ablate_attn_prefill32.py, "empty loop" 16.3 us against 6.1 without the stores).
   if (q_row0 + 31 >= 0) {
-    // Unpadded rows with an XOR swizzle of the 8-byte slots (MI355X_MICROARCH.md, LDS): a ds_write_b64 is served in four
-    // groups of 16 contiguous lanes on 32 banks — 16 rows at the same column need 16 different slot positions mod 16
-    // (slot ^ row does it; a padded stride of 4 banks met pairwise, PMC 6 % of the LDS cycles) — and the ds_read_b128
-    // of whole rows in its four non-contiguous groups is conflict-free exactly when the rows are 256 bytes apart.
-    constexpr int RSO = 2 * D;
     char* ob = smem + w * 32 * RSO;      // this wave's 32 rows
 #pragma unroll
     for (int db = 0; db < NDB; ++db)
@@ -470,15 +315,13 @@ __global__ __launch_bounds__(256, 2) void attn_fwd32_kernel(const AttnParams p) 
         u16x4 o;
 #pragma unroll
         for (int i = 0; i < 4; ++i) o[i] = T::from_float(acc[db][4 * rq + i] * inv);
-        *reinterpret_cast<u16x4*>(ob + c * RSO + (((8 * db + 2 * rq + hi) ^ (c & (LPR - 1))) << 3)) = o;
+        *reinterpret_cast<u16x4*>(ob + c * RSO + (((8 * db + 2 * rq + hi) ^ (c & (LPR - 1))) << 3)) = o;      // slot ^ row'
       }
     u16* obase = reinterpret_cast<u16*>(p.out) + (int64_t)h * D + 8 * st_ch;
 #pragma unroll
-    for (int j = 0; j < 32 / RPI; ++j) {
+    for (int j = 0; j < NQI; ++j) {
       const int rl = RPI * j + st_r4;
-      // slots 2 ch, 2 ch + 1 of row rl sit in chunk ch ^ (rl' >> 1), swapped when rl' is odd (rl' = rl mod D / 8)
-      u16x8 v = *reinterpret_cast<const u16x8*>(ob + rl * RSO + 16 * (st_ch ^ ((rl & (LPR - 1)) >> 1)));
-      if (rl & 1) v = u16x8{v[4], v[5], v[6], v[7], v[0], v[1], v[2], v[3]};
+      const u16x8 v = o_from_lds(ob + rl * RSO, rl, st_ch);
       if (q_row0 + rl >= 0) *reinterpret_cast<u16x8*>(obase + (int64_t)(q_start + q_row0 + rl) * p.o_row_stride) = v;
     }
   }
@@ -505,22 +348,7 @@ template <typename V> __device__ __forceinline__ V sfresh(V x) { asm volatile(""
 // to its 512-word list in p.stamps (tools/fwd_timeline.py)
 template <typename T, int D, bool PAGED, bool STAMPS = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd32p_kernel(const AttnParams p) {
-  constexpr int KS = D / 16;         // QK k-steps
-  constexpr int NDB = D / 32;        // 32-dim output blocks
-  constexpr int KT = 64;             // keys per tile (two 32-key sub-tiles)
-  constexpr int RSK = 2 * D, RSV = 2 * D;
-  constexpr int LPR = D / 8;
-  constexpr int NL = KT * LPR / 256;
-  constexpr int KTILE = KT * RSK, VTILE = KT * RSV;
-  constexpr int IMG = KTILE + VTILE;
-  constexpr int TQ = 128;
-  constexpr int RPI = 64 / LPR;         // rows per staging instruction
-  constexpr int NQI = 32 / RPI;         // staging instructions per 32-row block of Q / O
-  static_assert(NL * RPI == 16 && RPI * RSK == 1024, "a wave stages one 16-key group, 1 KiB per instruction");
-  extern __shared__ __attribute__((aligned(16))) char smem[];   // [2][K[KT][RSK] | V[KT][RSV]] | priority flag
-  auto kswz = [](int row) { return LPR == 16 ? (row & 15) : ((row >> 1) & 7); };
-  auto vswz = [](int row) { return LPR == 16 ? ((row & 3) << 2) : (((row >> 1) & 1) << 2); };
-  typedef __attribute__((address_space(4))) const int32_t c_i32;
+#include "attn_fwd32_geom.inc"
 
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -536,34 +364,25 @@ __global__ __launch_bounds__(256, 2) void attn_fwd32p_kernel(const AttnParams p)
   auto kargs = [&]() __attribute__((always_inline)) { return sfresh((c_params*)__builtin_amdgcn_kernarg_segment_ptr()); };
 
   int n_stamps = 0;
-  auto stamp = [&](int id) __attribute__((always_inline)) {
+  auto put_stamp = [&](uint64_t word) __attribute__((always_inline)) {      // append a word to this workgroup's list
     if constexpr (STAMPS) {
       if (w == 0 && n_stamps < 512) {
-        const uint64_t v = (__builtin_amdgcn_s_memrealtime() << 8) | (uint64_t)id;
-        if (lane == 0) p.stamps[(size_t)blockIdx.x * 512 + n_stamps] = v;
+        if (lane == 0) p.stamps[(size_t)blockIdx.x * 512 + n_stamps] = word;
         ++n_stamps;
       }
     }
+  };
+  auto stamp = [&](int id) __attribute__((always_inline)) {
+    if constexpr (STAMPS) put_stamp((__builtin_amdgcn_s_memrealtime() << 8) | (uint64_t)id);
+  };
+  auto stamp_cycles = [&](int id) __attribute__((always_inline)) {      // the shader clock's counter beside the 100 MHz one
+    if constexpr (STAMPS) put_stamp((__builtin_readcyclecounter() << 8) | (uint64_t)id);
   };
   stamp(1);
-  auto stamp_cycles = [&](int id) __attribute__((always_inline)) {      // the shader clock's counter beside the 100 MHz one
-    if constexpr (STAMPS) {
-      if (w == 0 && n_stamps < 512) {
-        const uint64_t v = (__builtin_readcyclecounter() << 8) | (uint64_t)id;
-        if (lane == 0) p.stamps[(size_t)blockIdx.x * 512 + n_stamps] = v;
-        ++n_stamps;
-      }
-    }
-  };
   stamp_cycles(30);
-  if constexpr (STAMPS) {      // where the workgroup runs: HW_ID (CU_ID [11:8], SH_ID [12], SE_ID [15:13]) and XCC_ID
-    if (w == 0 && n_stamps < 512) {
-      const uint64_t v = ((uint64_t)__builtin_amdgcn_s_getreg(20 | (0 << 6) | (31 << 11)) << 40) |
-                         ((uint64_t)__builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11)) << 8) | 32u;
-      if (lane == 0) p.stamps[(size_t)blockIdx.x * 512 + n_stamps] = v;
-      ++n_stamps;
-    }
-  }
+  if constexpr (STAMPS)        // where the workgroup runs: HW_ID (CU_ID [11:8], SH_ID [12], SE_ID [15:13]) and XCC_ID
+    put_stamp(((uint64_t)__builtin_amdgcn_s_getreg(20 | (0 << 6) | (31 << 11)) << 40) |
+              ((uint64_t)__builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11)) << 8) | 32u);
 
   // ---- the items of this workgroup: a table in LDS, built once.  Thread r decodes the item of round r — the r-th entry
   // of the snake walk over the item list —, all rounds at the same time.  (Decoded one at a time by every wave, through
@@ -703,7 +522,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd32p_kernel(const AttnParams p)
       const int q_start = sq[b], q_len = sq[b + 1] - q_start;
       const int k_start = sk[b], kv_len = sk[b + 1] - k_start;
       if (q_len <= 0) continue;
-      // query tiles aligned to the END of the sequence (see attn_fwd32_kernel)
+      // query tiles aligned to the END of the sequence, the partial tile first
       const int q_row0_wg = q_len - ((q_len + TQ - 1) / TQ - mblk) * TQ;
       const int last_key_wg = p.causal ? min(kv_len - 1, min(q_row0_wg + TQ - 1, q_len - 1) + kv_len - q_len) : kv_len - 1;
       if (!mine) { rec[0] = max(last_key_wg / KT + 1, 0); continue; }
@@ -778,7 +597,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd32p_kernel(const AttnParams p)
     bt_s = PAGED ? (c_i32*)(P->block_table + wk.bt_off) : nullptr;
   };
 
-  // ---- K / V tile staging by LDS-DMA (see attn_fwd32_kernel).  The address of a request is a wave-uniform base — page,
+  // ---- K / V tile staging by LDS-DMA (dma_flat).  The address of a request is a wave-uniform base — page,
   // first row of the wave's 16-key group, the instruction's rows: scalar arithmetic — plus a per-lane offset that never
   // changes (row inside the instruction, swizzled chunk): the vector ALU is not involved, except in a sequence's last
   // group, whose rows past the last key are clamped to it.
@@ -793,13 +612,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd32p_kernel(const AttnParams p)
   voff = (uint32_t)st_r4 * (uint32_t)p.v_row_stride * 2u + 16u * (uint32_t)(st_ch ^ vswz(st_r4));   // vswz(RPI j + r) = vswz(r)
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winline-asm"
+  // (dma_flat with the address as a uniform base and a 32-bit lane offset)
   auto dma = [&](const void* base, uint32_t off, uint32_t lds) __attribute__((always_inline)) {
-    // (m0 — the LDS address of the DMA — is a reserved register: naming it as clobbered is all that can be done, and
-    // nothing else in this kernel uses it)
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(off), "s"(base), "s"(lds) : "memory", "m0");
-  };
-  auto dma_flat = [&](const void* addr, uint32_t lds) __attribute__((always_inline)) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" :: "v"(addr), "s"(lds) : "memory", "m0");
   };
 #pragma clang diagnostic pop
   auto request_tile = [&](int t, int img) __attribute__((always_inline)) {
@@ -849,9 +664,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd32p_kernel(const AttnParams p)
       dma_flat(qbase + (int64_t)(wk.q_start + qr) * P->q_row_stride + 8 * (st_ch ^ kswz(R)), qd + 1024u * j);
     }
   };
-  auto tiles_landed = [&]() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };
-  using Set0 = std::integral_constant<int, 0>;
-  using Set1 = std::integral_constant<int, 1>;
 
   u16x8 qf[KS];
   auto read_q = [&](int img) __attribute__((always_inline)) {
@@ -894,11 +706,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd32p_kernel(const AttnParams p)
   __syncthreads();
   if (favoured) __builtin_amdgcn_s_setprio(3);
 
-  // transposed-read lane address inside a 4-row x 32-dim block (see attn_fwd32_kernel)
-  const int tr_q = (lane & 15) >> 2, tr_pp = lane & 3, tr_half = (lane >> 4) & 1;
-  const int tr_off = (4 * hi + tr_q) * RSV + (16 * tr_half + 4 * tr_pp) * 2;
-  const int tr_x = vswz(tr_q) >> 2;
-
+#include "attn_fwd32_lane.inc"
   auto half_max = [](float x) __attribute__((always_inline)) {      // max with lane ^ 32, without the LDS crossbar
     const uint32_t u = __builtin_bit_cast(uint32_t, x);
     auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
@@ -923,99 +731,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd32p_kernel(const AttnParams p)
       read_item(rn, nx);
       request_q(nx, 1 - PAR);                           // the free image takes the next item's Q rows
     }
-    if (t * KT <= last_key_wave) {
-      const char* kt = smem + PAR * IMG;
-      const char* vt = kt + KTILE;
-      f32x16 s[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s[u][r] = 0.f;
-      {
-        const char* krd = kt + c * RSK;
-        const int kz = kswz(c);
-        u16x8 kfa[KS], kfb[KS];
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) kfa[ks] = *reinterpret_cast<const u16x8*>(krd + 16 * ((2 * ks + hi) ^ kz));
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-          kfb[ks] = *reinterpret_cast<const u16x8*>(krd + 32 * RSK + 16 * ((2 * ks + hi) ^ kz));
-          s[0] = Mfma32<T>::mma(kfa[ks], qf[ks], s[0]);
-        }
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) s[1] = Mfma32<T>::mma(kfb[ks], qf[ks], s[1]);
-        __builtin_amdgcn_sched_group_barrier(0x100, KS, 0);
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, KS, 0);
-      }
-      const bool interior = t * KT + KT - 1 <= min(last_key, p.causal ? q_row0 + shift : last_key);
-      float mx = HX_NEG_BIG;
-      u16x8 pf[2][2];
-      if (interior) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[u][r]);
-      } else {
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int key = t * KT + 32 * u + (r & 3) + 8 * (r >> 2) + 4 * hi;
-            if (key > limit_c) s[u][r] = -INFINITY;
-            mx = fmaxf(mx, s[u][r]);
-          }
-      }
-      mx = half_max(mx);
-      // lazy running maximum (see attn_fwd32_kernel)
-      const float m_cand = fmaxf(m, mx * p.scale_log2);
-      const bool grow = m_cand > m + 8.0f;
-      float m_new = m;
-      if (__builtin_amdgcn_ballot_w64(grow)) {
-        m_new = grow ? m_cand : m;
-        const float alpha = fast_exp2(m - m_new);
-        l *= alpha;
-#pragma unroll
-        for (int i = 0; i < NDB; ++i)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[i][r] *= alpha;
-        m = m_new;
-      }
-      // (single-instruction fma / add: a packed f32 instruction beside MFMAs costs more than the two it replaces —
-      // MI355X_MICROARCH.md, per-instruction constants; the file is compiled without the SLP vectorizer for the same reason)
-      float pa = 0.f, pb = 0.f;
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; r += 2) {
-          const float e0 = fast_exp2(fmaf(s[u][r], p.scale_log2, -m_new));
-          const float e1 = fast_exp2(fmaf(s[u][r + 1], p.scale_log2, -m_new));
-          pa += e0;
-          pb += e1;
-          pf[u][r >> 3][r & 7] = T::from_float(e0);
-          pf[u][r >> 3][(r & 7) + 1] = T::from_float(e1);
-        }
-      l += pa + pb;
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int k2 = 0; k2 < 2; ++k2) {
-          const char* vrd = vt + (32 * u + 16 * k2) * RSV + tr_off;
-#pragma unroll
-          for (int db = 0; db < NDB; ++db) {
-            const u16x4 lo = lds_tr_read(vrd + 64 * (db ^ tr_x));
-            const u16x4 hh = lds_tr_read(vrd + 8 * RSV + 64 * (db ^ tr_x));
-            u16x8 vf;
-            vf[0] = lo[0]; vf[1] = lo[1]; vf[2] = lo[2]; vf[3] = lo[3];
-            vf[4] = hh[0]; vf[5] = hh[1]; vf[6] = hh[2]; vf[7] = hh[3];
-            acc[db] = Mfma32<T>::mma(vf, pf[u][k2], acc[db]);
-          }
-        }
-    }
+    constexpr int ABL = 0, img_cur = PAR;
+#include "attn_fwd32_tile.inc"
     stamp(11);
     if (!last) {
       lookup_page(min(t + 2, t_last));     // the table entry for the next request, in front of the barrier's wait
@@ -1043,13 +760,11 @@ __global__ __launch_bounds__(256, 2) void attn_fwd32p_kernel(const AttnParams p)
       page_next = __builtin_amdgcn_readfirstlane(items[ri * REC + 8 + w]);      // looked up when the table was built
       request_tile(0, 1 - PAR);            // in flight while the finished item's rows go out
     }
-    // O[query c][dim 32 db + 8 (r >> 2) + 4 hi + (r & 3)] = acc[db][r] / L, through LDS so that a store instruction
-    // writes whole rows (see attn_fwd32_kernel); this wave's 32 rows sit in image PAR
+    // the finished item's O rows = acc / L, through LDS (swizzle: attn_fwd32_geom.inc, o_from_lds): this wave's 32 rows sit in image PAR
     {
       const float lr = half_sum(l);
       const float inv = (lr > 0.f) ? 1.0f / lr : 0.f;
       if (e_q_row0 + 31 >= 0) {
-        constexpr int RSO = 2 * D;
         // (the lane's addresses are derived HERE from a lane id the compiler cannot see through: as loop invariants they
         // were computed at kernel entry, spilled, and every reload waited for vmcnt(0) — the first tile's requests)
         int ln = lane;
@@ -1063,17 +778,14 @@ __global__ __launch_bounds__(256, 2) void attn_fwd32p_kernel(const AttnParams p)
             u16x4 o;
 #pragma unroll
             for (int i = 0; i < 4; ++i) o[i] = T::from_float(acc[db][4 * rq + i] * inv);
-            *reinterpret_cast<u16x4*>(ob + ec * RSO + (((8 * db + 2 * rq + ehi) ^ (ec & (LPR - 1))) << 3)) = o;
+            *reinterpret_cast<u16x4*>(ob + ec * RSO + (((8 * db + 2 * rq + ehi) ^ (ec & (LPR - 1))) << 3)) = o;      // slot ^ row'
           }
         c_params* P = kargs();
         const int64_t ors = P->o_row_stride;
         u16* orow = reinterpret_cast<u16*>(P->out) + (int64_t)e_h * D + 8 * ech + (e_row + er4) * ors;
         const char* ord = ob + er4 * RSO;
         auto o_row = [&](int j) __attribute__((always_inline)) {
-          const int rl = RPI * j + er4;
-          u16x8 v = *reinterpret_cast<const u16x8*>(ord + RPI * j * RSO + 16 * (ech ^ ((rl & (LPR - 1)) >> 1)));
-          if (rl & 1) v = u16x8{v[4], v[5], v[6], v[7], v[0], v[1], v[2], v[3]};
-          return v;
+          return o_from_lds(ord + RPI * j * RSO, RPI * j + er4, ech);
         };
         if (e_q_row0 >= 0) {             // all 32 rows exist: NQI store instructions, no predicate
 #pragma unroll
@@ -1109,6 +821,18 @@ __global__ __launch_bounds__(256, 2) void attn_fwd32p_kernel(const AttnParams p)
     if (tile_step(Set0{})) break;
     if (tile_step(Set1{})) break;
   }
+}
+
+// Every launch of this file: 256 threads, `lds` bytes of dynamic LDS — the kernel's limit is raised where that is more
+// than the 48 KiB a kernel may ask for by default —, the launch error as the status.
+template <typename K>
+int launch_lds(K kernel, dim3 grid, size_t lds, hipStream_t stream, const AttnParams& p) {
+  if (lds > 48 * 1024) {
+    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return hip_rc(e);
+  }
+  hx::launcher(kernel, grid, 256, lds, stream)(p);
+  return check_launch();
 }
 
 int g_fwd_ablate = 0;   // EXPERIMENTS builds: timing ablations of attn_fwd32_kernel (wrong results)
@@ -1157,41 +881,29 @@ int launch_fwd32(const AttnParams& p, int batch, hipStream_t stream) {
   if ((g_fwd_persistent == 2 || (g_fwd_persistent && PAGED && worth_it)) && 2 * (lds + table) <= 160 * 1024 &&
       4 * (3 * (size_t)batch + 2 + (size_t)rounds) <= 2 * 64 * (2 * D + 2 * D)) {
     const size_t lds = 2 * 64 * (2 * D + 2 * D) + 16 + table;
-    hipError_t e = hipFuncSetAttribute((const void*)attn_fwd32p_kernel<T, D, PAGED>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return hip_rc(e);
+    const dim3 grid((unsigned)g, 1, 1);
 #if HX_EXPERIMENTS
     if constexpr (D == 128 && PAGED && std::is_same<T, BF16>::value) {
       if (g_fwd_stamps) {
         pp.stamps = g_fwd_stamps;
-        e = hipFuncSetAttribute((const void*)attn_fwd32p_kernel<T, D, PAGED, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return hip_rc(e);
-        hx::launcher(attn_fwd32p_kernel<T, D, PAGED, true>, dim3((unsigned)g, 1, 1), 256, lds, stream)(pp);
-        return check_launch();
+        return launch_lds(attn_fwd32p_kernel<T, D, PAGED, true>, grid, lds, stream, pp);
       }
     }
 #endif
-    hx::launcher(attn_fwd32p_kernel<T, D, PAGED>, dim3((unsigned)g, 1, 1), 256, lds, stream)(pp);
-    return check_launch();
+    return launch_lds(attn_fwd32p_kernel<T, D, PAGED>, grid, lds, stream, pp);
   }
   pp.wg_priority = per_item_priority;
-  if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)attn_fwd32_kernel<T, D, PAGED>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return hip_rc(e);
-  }
 #if HX_EXPERIMENTS
   if constexpr (D == 128 && PAGED && std::is_same<T, BF16>::value) {
     switch (g_fwd_ablate) {
-#define HX_ABL(n) case n: hx::launcher(attn_fwd32_kernel<T, D, PAGED, n>, grid, 256, lds, stream)(pp); return check_launch();
+#define HX_ABL(n) case n: return launch_lds(attn_fwd32_kernel<T, D, PAGED, n>, grid, lds, stream, pp);
       HX_ABL(1) HX_ABL(2) HX_ABL(4) HX_ABL(8) HX_ABL(3) HX_ABL(5) HX_ABL(6) HX_ABL(7) HX_ABL(9) HX_ABL(15) HX_ABL(16) HX_ABL(32) HX_ABL(48) HX_ABL(256) HX_ABL(79) HX_ABL(512) HX_ABL(1039)
 #undef HX_ABL
       default: break;
     }
   }
 #endif
-  hx::launcher(attn_fwd32_kernel<T, D, PAGED>, grid, 256, lds, stream)(pp);
-  return check_launch();
+  return launch_lds(attn_fwd32_kernel<T, D, PAGED>, grid, lds, stream, pp);
 }
 
 int g_fwd_mfma32 = 1;   // tuning: 0 = always the 16x16x32 kernel
@@ -1203,13 +915,7 @@ int launch_fwd_cfg(const AttnParams& p, int batch, int max_seqlen_q, hipStream_t
   // tile slots: sum_b ceil(q_b / TQ) <= total_q / TQ + batch
   dim3 grid((unsigned)(p.total_q / (64 * QR) + batch), p.n_heads, 1);
   if (p.total_q == 0) return HX_OK;
-  if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)attn_fwd_kernel<T, D, PAGED, QR, KU>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return hip_rc(e);
-  }
-  hx::launcher(attn_fwd_kernel<T, D, PAGED, QR, KU>, grid, 256, lds, stream)(p);
-  return check_launch();
+  return launch_lds(attn_fwd_kernel<T, D, PAGED, QR, KU>, grid, lds, stream, p);
 }
 
 int g_fwd_rows = 0;   // tuning: 0 = automatic, 1 / 2 = row blocks per wave
@@ -1221,13 +927,7 @@ int launch_fwd_alibi(const AttnParams& p, int batch, hipStream_t stream) {
   const size_t lds = 4 * 32 * RS;   // K[2][32][RS] + V[2][32][RS]
   dim3 grid((unsigned)(p.total_q / 64 + batch), p.n_heads, 1);
   if (p.total_q == 0) return HX_OK;
-  if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)attn_fwd_alibi_kernel<T, D, PAGED>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return hip_rc(e);
-  }
-  hx::launcher(attn_fwd_alibi_kernel<T, D, PAGED>, grid, 256, lds, stream)(p);
-  return check_launch();
+  return launch_lds(attn_fwd_alibi_kernel<T, D, PAGED>, grid, lds, stream, p);
 }
 
 template <typename T, int D, bool PAGED>
