@@ -56,6 +56,17 @@ def refuse_penalties(request) -> None:
                          "(one engine process per GPU); use the single-process server or the offline engine")
 
 
+def refuse_sampling(request) -> None:
+    """Nor sampled decoding (temperature > 0): the wire format carries neither the sampling parameters nor the seed, and
+    the offset of the draw would have to follow the request from rank to rank.  A greedy request passes."""
+    from hydrainfer_amd.sampling import is_sampled
+    sp = getattr(request, "sampling_params", None)
+    if sp is not None and is_sampled(sp):
+        raise ValueError(f"request {request.request_id}: sampled decoding (temperature > 0) is not available in "
+                         "multi-process serving (one engine process per GPU); use the single-process server or the "
+                         "offline engine")
+
+
 def rcb_to_wire(rcb: RequestControlBlock) -> dict:
     """Everything the next stage needs: the instructions from the current one on (a flat list —
     the linked chain would pickle recursively), the block tables + IPC handles of the caches, the
@@ -307,6 +318,7 @@ class RankEngine:
         whichever ranks run its prefill and decode — are delivered to `processor` on THIS rank."""
         refuse_logprobs(request)
         refuse_penalties(request)
+        refuse_sampling(request)
         self.token_handlers[request.request_id] = processor
         has_image = request.pixel_values is not None
         dst = entry_rank(self._n_submitted[has_image], self.roles, has_image, self.dead)

@@ -20,7 +20,8 @@ from hydrainfer_amd.engine.isa import Fill, TextFill
 from hydrainfer_amd.engine.parameters_builder import LanguageModelParametersBuilder
 from hydrainfer_amd.engine.rcb import BatchRequest, TokenLogprob
 from hydrainfer_amd.model.llama import LanguageModelParameters
-from hydrainfer_amd.sampling import NO_PENALTIES, pack_penalty_step, penalized_argmax_rows
+from hydrainfer_amd.sampling import (GREEDY_RECORD, NO_PENALTIES, pack_penalty_step, pack_sample_step, penalized_argmax_rows,
+                                     sample_rows)
 
 
 class PendingToken:
@@ -88,9 +89,9 @@ class BatchFillExecutor:
         pending_launch = self.pending[0] if self.pending is not None else None
         for rcb, inst in batch:
             if (len(inst.token_ids) != 1 or not inst.sample or rcb.sampling_params.logprobs
-                    or rcb.penalty_history is not None):
-                return None                    # (a request that wants log-probabilities, or one under sampling
-                                               # penalties, decodes eagerly: execute())
+                    or rcb.penalty_history is not None or rcb.sampling_params.temperature > 0):
+                return None                    # (a request that wants log-probabilities, one under sampling penalties
+                                               # or a sampled one decodes eagerly: execute())
             token = inst.token_ids[0]
             if isinstance(token, PendingToken):
                 if token.launch != pending_launch:
@@ -348,6 +349,42 @@ class BatchFillExecutor:
             scores = scores and tuple([col[j] for j in sel] for col in scores)
         return sampled, scores
 
+    def _sample_drawn(self, batch: BatchRequest, inputs, params, top_k: Optional[int]):
+        """The eager step of a batch in which some request is SAMPLED (temperature > 0): the same logits, then
+        hx_sample_rows — ONE launch for the whole batch.  Greedy requests ride along with temperature 0 and get the id
+        they would have got, penalised ones (greedy or sampled) ride along with their history.  A request's offset is the
+        number of tokens it has generated so far (the eager path has every token on the host).  The step's sampling
+        records and (token, count) tables reach the device as one pinned buffer in one copy.  top_k: as in
+        _sample_penalized, for the batch's OTHER requests that asked for log-probabilities."""
+        sel, decode = inputs.selected_token_ids, inputs.all_sequences_decode
+        n_rows = inputs.input_ids.shape[0] if decode else len(sel)        # the rows of the logits
+        entries = [(None, NO_PENALTIES, GREEDY_RECORD)] * n_rows
+        i = 0
+        for rcb, inst in batch:
+            if not isinstance(inst, Fill) or not inst.sample:
+                continue
+            sp = rcb.sampling_params
+            record = (sp.temperature, sp.top_p, sp.top_k, sp.seed, len(rcb.output_token_ids)) if sp.temperature > 0 \
+                else GREEDY_RECORD
+            entries[sel[i] if decode else i] = (rcb.penalty_history,
+                                                (sp.frequency_penalty, sp.presence_penalty, sp.repetition_penalty), record)
+            i += 1
+        tables = pack_sample_step(entries).to_device(self.device)
+        lm, scores = self.language_model, None
+        if top_k is None:
+            sampled = lm.forward_sampled(inputs.input_ids, inputs.image_features, inputs.position_ids, params,
+                                         *tables).tolist()                         # the step's only device sync
+        else:
+            logits = lm.forward_logits(inputs.input_ids, inputs.image_features, inputs.position_ids, params)
+            packed = logprob_rows_packed(logprob_rows(logits, top_k)[0], top_k)
+            sampled = sample_rows(logits, *tables).tolist()
+            _, lp, top_ids, top_lp = logprob_rows_views(packed.cpu(), n_rows, top_k)
+            scores = (lp.tolist(), top_ids.tolist(), top_lp.tolist())
+        if decode and n_rows != len(sel):
+            sampled = [sampled[j] for j in sel]
+            scores = scores and tuple([col[j] for j in sel] for col in scores)
+        return sampled, scores
+
     def _publish_prefix_blocks(self, batch: BatchRequest) -> None:
         """A block's hash enters the prefix cache in the step that computes its last token
         (executor.py:111-127); decode tokens are never published."""
@@ -391,6 +428,9 @@ class BatchFillExecutor:
             return
         asking = [rcb.sampling_params.top_logprobs for rcb, inst in batch
                   if rcb.sampling_params.logprobs and isinstance(inst, Fill) and inst.sample and not inst.is_chunked]
+        if any(rcb.sampling_params.temperature > 0 for rcb, inst in batch if isinstance(inst, Fill) and inst.sample):
+            self._deliver(batch, *self._sample_drawn(batch, inputs, params, max(asking) if asking else None))
+            return
         if any(rcb.penalty_history is not None for rcb, inst in batch if isinstance(inst, Fill) and inst.sample):
             self._deliver(batch, *self._sample_penalized(batch, inputs, params, max(asking) if asking else None))
             return

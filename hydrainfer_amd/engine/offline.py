@@ -39,6 +39,10 @@ class OfflineRequest:
     frequency_penalty: float = 0.0      # the reference's process_logits steps 1-2 over the generated tokens
     presence_penalty: float = 0.0       # (hydrainfer_amd/sampling); a penalised request decodes eagerly
     repetition_penalty: float = 1.0
+    temperature: float = 0.0            # > 0: sampled decoding (steps 3-5 of process_logits and a seeded draw); 0: greedy
+    top_p: float = 1.0                  # a sampled request decodes eagerly
+    top_k: int = 0
+    seed: Optional[int] = None          # None: the engine assigns one (it is in the request's sampling_params afterwards)
 
 
 class OfflineInferenceEngine:
@@ -85,7 +89,8 @@ class OfflineInferenceEngine:
                                    image_hash=compute_image_hash(r.image) if r.image is not None else 0,
                                    sampling_params=SamplingParameters(r.max_tokens, list(r.eos_token_ids), r.logprobs,
                                                                       r.top_logprobs, r.frequency_penalty,
-                                                                      r.presence_penalty, r.repetition_penalty),
+                                                                      r.presence_penalty, r.repetition_penalty,
+                                                                      r.temperature, r.top_p, r.top_k, r.seed),
                                    token_params=r.token_params)
                 rcb = self.creator.process(req)
                 rcb.metric.arrival_time = time.perf_counter()

@@ -21,6 +21,13 @@ class SamplingParameters:
     frequency_penalty: float = 0.0      # subtracted once per earlier occurrence of a token
     presence_penalty: float = 0.0       # subtracted once from every token that occurred
     repetition_penalty: float = 1.0     # > 0: a token that occurred has its logit divided (if negative: multiplied) by it
+    # steps 3-5 of process_logits and a seeded draw (hx_sample_rows, include/hydra_hip.h).  temperature 0 is GREEDY
+    # (OpenAI's meaning of 0), and an absent temperature means 0 here, where OpenAI's default is 1: every request that does
+    # not ask for sampling keeps the argmax paths.  A sampled request decodes eagerly and cannot ask for logprobs.
+    temperature: float = 0.0            # >= 0; > 0: the logits are divided by it and a token is drawn
+    top_p: float = 1.0                  # (0, 1]: the smallest set of most likely tokens holding this much probability
+    top_k: int = 0                      # >= 0: only the k most likely tokens (ties at the cut are all kept); 0: off
+    seed: Optional[int] = None          # 0 .. 2^63 - 1; a sampled request without one is given one at admission
 
 
 MAX_TOP_LOGPROBS = 20

@@ -1,6 +1,7 @@
 """Request -> instruction chain — mirror of hydrainfer/engine/request_processor.py:47-173
 (InstructionCreator) without the tokenizer / image processor (the caller passes token ids and
 pre-processed pixel values; there are no checkpoints or tokenizers offline)."""
+import secrets
 from dataclasses import dataclass
 from typing import List, Optional, Tuple
 
@@ -11,7 +12,7 @@ from hydrainfer_amd.engine.isa import (EPMigrate, ImageEmbed, ImageEmbedFill, In
 from hydrainfer_amd.engine.rcb import (MAX_TOP_LOGPROBS, RequestControlBlock, RequestMetaData, SamplingParameters,
                                        ScenarioClassifier, TokenParameters)
 from hydrainfer_amd.memory.shared_cache import compute_hash
-from hydrainfer_amd.sampling import PenaltyHistory, check_penalties, is_penalized
+from hydrainfer_amd.sampling import PenaltyHistory, check_penalties, check_sampling, is_penalized, is_sampled
 
 
 @dataclass
@@ -103,9 +104,19 @@ class InstructionCreator:
             raise ValueError(f"request {request.request_id}: top_logprobs = {top} needs logprobs = True")
         try:
             penalties = check_penalties(sp.frequency_penalty, sp.presence_penalty, sp.repetition_penalty)
+            sampling = check_sampling(sp.temperature, sp.top_p, sp.top_k, sp.seed)
         except ValueError as e:
             raise ValueError(f"request {request.request_id}: {e}") from None
-        rcb.sampling_params = SamplingParameters(sp.max_tokens, list(sp.eos_token_ids), sp.logprobs, top, *penalties)
+        rcb.sampling_params = SamplingParameters(sp.max_tokens, list(sp.eos_token_ids), sp.logprobs, top, *penalties,
+                                                 *sampling)
+        if is_sampled(rcb.sampling_params):
+            if sp.logprobs:
+                raise ValueError(f"request {request.request_id}: temperature > 0 cannot be combined with logprobs yet: "
+                                 "OpenAI reports the log-probability of the sampled token, hx_logprob_rows that of the "
+                                 "greedy one")
+            if rcb.sampling_params.seed is None:
+                # 63 random bits, kept with the request: a finished request can be replayed from its parameters
+                rcb.sampling_params.seed = secrets.randbits(63)
         if is_penalized(rcb.sampling_params):
             if sp.logprobs:
                 raise ValueError(f"request {request.request_id}: frequency / presence / repetition penalties cannot be "

@@ -35,6 +35,10 @@ class ChatRequest:
     frequency_penalty: float = 0.0  # OpenAI's `frequency_penalty`, -2..2
     presence_penalty: float = 0.0   # OpenAI's `presence_penalty`, -2..2
     repetition_penalty: float = 1.0 # extension (the reference's process_logits step 2): > 0, 1 = none
+    temperature: float = 0.0        # OpenAI's `temperature`, 0..2; absent means 0 (greedy) here, OpenAI's default is 1
+    top_p: float = 1.0              # OpenAI's `top_p`, (0, 1]
+    top_k: int = 0                  # extension (the reference's process_logits step 4): integer >= 0, 0 = off
+    seed: Optional[int] = None      # OpenAI's `seed`, 0..2^63-1; absent: the engine assigns one
 
 
 def parse_chat_completion_request(body: dict) -> ChatRequest:
@@ -108,12 +112,37 @@ def parse_chat_completion_request(body: dict) -> ChatRequest:
     penalties["repetition_penalty"] = float(v)
     if logprobs and (penalties["frequency_penalty"] or penalties["presence_penalty"] or v != 1):
         raise ProtocolError("logprobs cannot be combined with frequency / presence / repetition penalties yet")
+    sampling = {}
+    v = body.get("temperature")
+    if v is None:
+        v = 0.0
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 <= v <= 2.0:           # (a NaN fails the range)
+        raise ProtocolError("temperature: number in 0..2 required")
+    sampling["temperature"] = float(v)
+    v = body.get("top_p")
+    if v is None:
+        v = 1.0
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 < v <= 1.0:
+        raise ProtocolError("top_p: number in (0, 1] required")
+    sampling["top_p"] = float(v)
+    v = body.get("top_k")
+    if v is None:
+        v = 0
+    if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 0x7fffffff:
+        raise ProtocolError("top_k: integer >= 0 required")
+    sampling["top_k"] = v
+    v = body.get("seed")
+    if v is not None and (isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= (1 << 63) - 1):
+        raise ProtocolError("seed: integer in 0..2^63-1 required")
+    sampling["seed"] = v
+    if logprobs and sampling["temperature"] > 0:
+        raise ProtocolError("logprobs cannot be combined with temperature > 0 yet")
     try:
         png = base64.b64decode(images[0], validate=True) if images else None
     except Exception:
         raise ProtocolError("image_url: invalid base64")
     return ChatRequest(model=model, role=role, text=text, image_png=png, max_tokens=max_tokens,
-                       stream=bool(body.get("stream", False)), logprobs=logprobs, top_logprobs=top_logprobs, **penalties)
+                       stream=bool(body.get("stream", False)), logprobs=logprobs, top_logprobs=top_logprobs, **penalties, **sampling)
 
 
 def render_llava_chat_prompt(role: str, content: str, bos_token: str = "<s>", eos_token: str = "</s>") -> str:

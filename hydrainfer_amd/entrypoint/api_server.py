@@ -200,9 +200,10 @@ class RankEngineFrontend(EngineFrontend):
         self._index = 0
 
     def _start(self, request: TokenRequest, processor: StreamOutputTokenProcessor) -> None:
-        from hydrainfer_amd.engine.distributed import refuse_logprobs, refuse_penalties
+        from hydrainfer_amd.engine.distributed import refuse_logprobs, refuse_penalties, refuse_sampling
         refuse_logprobs(request)                      # ValueError: the rank protocol carries no log-probabilities
         refuse_penalties(request)                     # nor sampling penalties
+        refuse_sampling(request)                      # nor sampled decoding
         self.engine.submit(request, processor, self.creator, self._index)
         self._index += 1
 
@@ -255,7 +256,9 @@ class ApiServer:
                                                                top_logprobs=req.top_logprobs,
                                                                frequency_penalty=req.frequency_penalty,
                                                                presence_penalty=req.presence_penalty,
-                                                               repetition_penalty=req.repetition_penalty))
+                                                               repetition_penalty=req.repetition_penalty,
+                                                               temperature=req.temperature, top_p=req.top_p,
+                                                               top_k=req.top_k, seed=req.seed))
 
     # ------------------------------------------------------------------ HTTP
     @staticmethod

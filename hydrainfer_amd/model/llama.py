@@ -577,4 +577,13 @@ class LlamaForCausalLM:
         logits = self.forward_logits(input_ids_or_embeds, position_ids, model_params)
         return penalized_argmax_rows(logits, hist_ids, hist_counts, cu_hist, penalties, out)
 
+    def forward_sampled(self, input_ids_or_embeds, position_ids, model_params, sample_params, hist_ids=None, hist_counts=None,
+                        cu_hist=None, penalties=None, out=None):
+        """forward() for a step with a sampled request (temperature > 0): the same logits, then ONE launch
+        (sampling.sample_rows) in place of argmax_rows — row r's record is sample_params[r], a row with temperature 0
+        gets forward_penalized()'s id.  Eager only: not part of the launch plan or the captured graphs."""
+        from hydrainfer_amd.sampling import sample_rows
+        logits = self.forward_logits(input_ids_or_embeds, position_ids, model_params)
+        return sample_rows(logits, sample_params, hist_ids, hist_counts, cu_hist, penalties, out)
+
     __call__ = forward

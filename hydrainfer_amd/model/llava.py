@@ -52,4 +52,14 @@ class LlavaLanguageModel:
         return penalized_argmax_rows(self.forward_logits(input_ids, image_features, position_ids, model_params),
                                      hist_ids, hist_counts, cu_hist, penalties, out)
 
+    def forward_sampled(self, input_ids: Tensor, image_features: Optional[Tensor], position_ids: Tensor,
+                        model_params: LanguageModelParameters, sample_params: Tensor, hist_ids: Optional[Tensor] = None,
+                        hist_counts: Optional[Tensor] = None, cu_hist: Optional[Tensor] = None,
+                        penalties: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+        """forward() with sampled decoding: one launch behind the logits (hx_sample_rows) with the rows' sampling records
+        and, optionally, their (token, count) tables; a row with temperature 0 gets the id forward_penalized gives."""
+        from hydrainfer_amd.sampling import sample_rows
+        return sample_rows(self.forward_logits(input_ids, image_features, position_ids, model_params), sample_params,
+                           hist_ids, hist_counts, cu_hist, penalties, out)
+
     __call__ = forward

@@ -1,16 +1,22 @@
-"""hydrainfer.sampling — counterpart of the reference's hydrainfer/sampling/logits_processor.py for a greedy engine.
+"""hydrainfer.sampling — counterpart of the reference's hydrainfer/sampling/logits_processor.py, and the draw the
+reference never makes (its models end in torch.argmax).
 
-Of `process_logits` (logits_processor.py:49-93) only steps 1-2, the frequency / presence / repetition penalties
-(lines 65-72), can change the token a greedy sampler picks: a positive temperature keeps the order of the logits, top-k
-and top-p mask entries below the maximum.  `penalized_argmax_rows` (hx_penalized_argmax_rows, csrc/penalties.hip) is
-those two steps and the argmax in one launch behind the logits.
+`process_logits` (logits_processor.py:49-93) is five steps: frequency / presence and repetition penalties (1-2, lines
+65-72), temperature (3), top-k (4), top-p (5).  Two kernels cover it:
+- `penalized_argmax_rows` (hx_penalized_argmax_rows, csrc/penalties.hip): steps 1-2 and the argmax in one launch.  For a
+  GREEDY request nothing else matters: a positive temperature keeps the order of the logits, top-k and top-p mask
+  entries below the maximum.
+- `sample_rows` (hx_sample_rows, csrc/sampling.hip): all five steps and a seeded draw in one launch.  A row with
+  temperature 0 is greedy there and gets `penalized_argmax_rows`' id bit for bit, which is how greedy requests ride
+  along in a batch that also holds sampled ones.  The exact semantics — what a tie at a cut does, where the random
+  number comes from — are in include/hydra_hip.h; `temperature` absent means 0 here (OpenAI's default is 1).
 
 The history.  The reference's processor takes one table of (token, count) per sequence and leaves open what goes into
 it.  Here it holds the GENERATED tokens only, for all three penalties: prompts contain image placeholders (hundreds of
 copies of one id) and chat-template tokens, which a prompt-inclusive repetition penalty would push down; OpenAI's
 frequency / presence penalties are defined over the sampled text as well.  The first generated token therefore sees an
 empty history.  `PenaltyHistory` is that table on the host, `pack_penalty_step` turns a step's tables into the kernel's
-CSR — one buffer, one host-to-device copy."""
+CSR, `pack_sample_step` does the same with the rows' sampling records in front — one buffer, one host-to-device copy."""
 import math
 from array import array
 from typing import Optional, Sequence, Tuple
@@ -23,6 +29,10 @@ from hydrainfer_amd import _lib
 
 MAX_VOCAB = 1 << 18             # the widest row hx_penalized_argmax_rows takes (its LDS bitmap)
 NO_PENALTIES = (0.0, 0.0, 1.0)  # (frequency, presence, repetition): the identity
+SAMPLE_MAX_N = 35840            # the widest row hx_sample_rows takes (HX_SAMPLE_MAX_N: the row as fp32 in LDS)
+SAMPLE_RECORD_WORDS = 8         # a row's record: [temperature, top_p (fp32 bits), top_k, 0, seed lo, hi, offset lo, hi]
+GREEDY_RECORD = (0.0, 1.0, 0, 0, 0)     # (temperature, top_p, top_k, seed, offset): the row is penalised argmax
+MAX_SEED = (1 << 63) - 1
 
 
 def penalized_argmax_rows(logits: Tensor, hist_ids: Tensor, hist_counts: Tensor, cu_hist: Tensor, penalties: Tensor,
@@ -141,3 +151,125 @@ def pack_penalty_step(entries) -> PenaltyStep:
             buf[at + total:at + total + n] = np.frombuffer(h.counts, dtype=np.int32)
             at += n
     return PenaltyStep(buf, rows, total)
+
+
+def sample_rows(logits: Tensor, sample_params: Tensor, hist_ids: Optional[Tensor] = None,
+                hist_counts: Optional[Tensor] = None, cu_hist: Optional[Tensor] = None,
+                penalties: Optional[Tensor] = None, out: Optional[Tensor] = None, cut_out: Optional[Tensor] = None,
+                u_out: Optional[Tensor] = None) -> Tensor:
+    """Sampled ids of fp16 / bf16 logits [rows, n]: penalties, temperature, top-k, top-p and a seeded draw in one launch
+    (include/hydra_hip.h: hx_sample_rows).  sample_params: int32 [rows, 8], the rows' records (`pack_sample_records`); a
+    row with temperature 0 gets `penalized_argmax_rows`' id.  The four history tensors are those of
+    `penalized_argmax_rows`, all given or all None (no row is penalised).  Returns int64 [rows] (`out` if given).
+    cut_out / u_out: fp32 [rows] tensors that receive each row's top-p cut v* (NaN for a greedy or degenerate row) and
+    its uniform number u."""
+    _lib.require_gpu(logits, sample_params, hist_ids, hist_counts, cu_hist, penalties, out, cut_out, u_out)
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.dtype not in (torch.float16, torch.bfloat16) \
+            or logits.shape[0] < 1 or not 1 <= logits.shape[1] <= SAMPLE_MAX_N or logits.stride(0) < logits.shape[1]:
+        raise _lib.HydraHipError(f"sample_rows: logits must be fp16 / bf16 [rows, n] (rows >= 1, 1 <= n <= {SAMPLE_MAX_N}) "
+                                 "with contiguous rows")
+    rows = logits.shape[0]
+    if sample_params.dtype != torch.int32 or tuple(sample_params.shape) != (rows, SAMPLE_RECORD_WORDS) \
+            or not sample_params.is_contiguous():
+        raise _lib.HydraHipError(f"sample_rows: sample_params must be a contiguous int32 tensor of shape "
+                                 f"[{rows}, {SAMPLE_RECORD_WORDS}]")
+    tables = (hist_ids, hist_counts, cu_hist, penalties)
+    total = 0
+    if any(t is not None for t in tables):
+        if any(t is None for t in tables):
+            raise _lib.HydraHipError("sample_rows: hist_ids, hist_counts, cu_hist and penalties come together or not at all")
+        total = hist_ids.numel()
+        for name, t, shape in (("hist_ids", hist_ids, (total,)), ("hist_counts", hist_counts, (total,)),
+                               ("cu_hist", cu_hist, (rows + 1,))):
+            if t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous():
+                raise _lib.HydraHipError(f"sample_rows: {name} must be a contiguous int32 tensor of shape {list(shape)}")
+        if penalties.dtype != torch.float32 or tuple(penalties.shape) != (rows, 3) or not penalties.is_contiguous():
+            raise _lib.HydraHipError(f"sample_rows: penalties must be a contiguous fp32 tensor of shape [{rows}, 3]")
+    if out is None:
+        out = torch.empty(rows, dtype=torch.int64, device=logits.device)
+    elif out.dtype != torch.int64 or out.shape != (rows,) or not out.is_contiguous() or out.device != logits.device:
+        raise _lib.HydraHipError("sample_rows: out must be a contiguous int64 [rows] tensor on the logits' device")
+    for name, t in (("cut_out", cut_out), ("u_out", u_out)):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (rows,) or not t.is_contiguous()):
+            raise _lib.HydraHipError(f"sample_rows: {name} must be a contiguous fp32 tensor of shape [{rows}]")
+    ptr = (lambda t: t.data_ptr()) if total else (lambda t: None)
+    _lib.check(_lib.lib().hx_sample_rows(
+        out.data_ptr(), cut_out.data_ptr() if cut_out is not None else None, u_out.data_ptr() if u_out is not None else None,
+        logits.data_ptr(), rows, logits.shape[1], logits.stride(0), ptr(hist_ids), ptr(hist_counts), ptr(cu_hist), total,
+        ptr(penalties), sample_params.data_ptr(), _lib.dtype_code(logits), _lib.current_stream()), "sample_rows")
+    return out
+
+
+def check_sampling(temperature, top_p, top_k, seed) -> Tuple[float, float, int, Optional[int]]:
+    """The four values checked, or ValueError: temperature a finite number >= 0 (0: greedy), top_p a number in (0, 1],
+    top_k an integer >= 0 (0: off), seed None or an integer in 0 .. 2^63 - 1.  A bool is no number."""
+    for name, v in (("temperature", temperature), ("top_p", top_p)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError(f"{name} {v!r} must be a finite number")
+    if temperature < 0:
+        raise ValueError(f"temperature {temperature!r} must be >= 0")
+    if not 0 < top_p <= 1:
+        raise ValueError(f"top_p {top_p!r} must be in (0, 1]")
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or not 0 <= top_k <= 0x7fffffff:
+        raise ValueError(f"top_k {top_k!r} must be an integer >= 0")
+    if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed <= MAX_SEED):
+        raise ValueError(f"seed {seed!r} must be an integer in 0 .. 2^63 - 1")
+    return float(temperature), float(top_p), top_k, seed
+
+
+def is_sampled(sampling_params) -> bool:
+    """False for temperature 0: such a request is greedy and takes the engine's argmax paths."""
+    return sampling_params.temperature > 0
+
+
+def pack_sample_records(records, out: Optional[np.ndarray] = None) -> np.ndarray:
+    """records: one (temperature, top_p, top_k, seed, offset) per logits row -> int32 [rows, 8], the layout of
+    include/hydra_hip.h (into `out` if given)."""
+    rows = len(records)
+    if out is None:
+        out = np.zeros((rows, SAMPLE_RECORD_WORDS), dtype=np.int32)
+    out[:, :2] = np.asarray([(r[0], r[1]) for r in records], dtype=np.float32).reshape(rows, 2).view(np.int32)
+    out[:, 2] = [r[2] for r in records]
+    out[:, 3] = 0
+    out[:, 4:].view(np.uint64)[:] = np.asarray([(r[3], r[4]) for r in records], dtype=np.uint64).reshape(rows, 2)
+    return out
+
+
+class SampleStep:
+    """A sampled step's packed tables: one int32 host buffer [records (8 rows) | cu_hist (rows + 1) | penalties (3 rows,
+    fp32 bits) | hist_ids (total) | hist_counts (total)] — `views` cuts it (on the host or on the device) into
+    sample_rows' five table arguments."""
+    __slots__ = ("buffer", "rows", "total")
+
+    def __init__(self, buffer: np.ndarray, rows: int, total: int):
+        self.buffer, self.rows, self.total = buffer, rows, total
+
+    def views(self, t: Optional[Tensor] = None):
+        """(sample_params, hist_ids, hist_counts, cu_hist, penalties) inside `t`, a tensor holding the buffer (default: a
+        host copy)."""
+        if t is None:
+            t = torch.from_numpy(self.buffer)
+        r = SAMPLE_RECORD_WORDS * self.rows
+        a, b = r + self.rows + 1, r + 4 * self.rows + 1
+        return (t[:r].view(self.rows, SAMPLE_RECORD_WORDS), t[b:b + self.total], t[b + self.total:b + 2 * self.total],
+                t[r:a], t[a:b].view(torch.float32).view(self.rows, 3))
+
+    def to_device(self, device):
+        """The five arguments on `device`: the buffer goes through pinned memory in ONE host-to-device copy."""
+        host = torch.from_numpy(self.buffer)
+        if torch.device(device).type == "cuda":
+            host = host.pin_memory()
+        return self.views(host.to(device, non_blocking=True))
+
+
+def pack_sample_step(entries) -> SampleStep:
+    """entries: one (PenaltyHistory or None, (frequency, presence, repetition), (temperature, top_p, top_k, seed,
+    offset)) per logits row, in row order.  The rows' records come first (8-byte aligned: the seeds are 64-bit), the
+    layout of `pack_penalty_step` follows."""
+    rows = len(entries)
+    tables = pack_penalty_step([(h, p) for h, p, _ in entries])
+    r = SAMPLE_RECORD_WORDS * rows
+    buf = np.empty(r + tables.buffer.size, dtype=np.int32)
+    pack_sample_records([rec for _, _, rec in entries], buf[:r].reshape(rows, SAMPLE_RECORD_WORDS))
+    buf[r:] = tables.buffer
+    return SampleStep(buf, rows, tables.total)

@@ -262,6 +262,34 @@ int hx_logprob_rows(int64_t* ids, float* logprobs, int32_t* top_ids, float* top_
 int hx_penalized_argmax_rows(int64_t* ids, float* scores_out, const void* logits, int64_t rows, int64_t n, int64_t ld,
                              const int32_t* hist_ids, const int32_t* hist_counts, const int32_t* cu_hist, int64_t total,
                              const float* penalties, int dtype, hx_stream stream);
+/* hx_sample_rows: seeded sampled decoding — penalties, temperature, top-k, top-p and the draw in one launch and one read
+ * of the logits (extension: the reference's models end in torch.argmax; added WITHOUT raising HX_ABI_VERSION).  logits:
+ * fp16 / bf16 [rows, n], row stride ld elements, n <= HX_SAMPLE_MAX_N (the row as fp32 in LDS).  The history arguments are
+ * hx_penalized_argmax_rows'; with total == 0 no row is penalised and hist_ids, hist_counts, cu_hist and penalties may
+ * all be NULL.  sample_params: one 32-byte record per row, eight 32-bit words:
+ *     [0] temperature T (fp32)   [1] top_p (fp32)   [2] top_k (int32)   [3] 0
+ *     [4] seed, low word   [5] seed, high word   [6] offset, low word   [7] offset, high word
+ * offset: the index of the token being generated (0 for the first).  Per row:
+ *   u = (Philox4x32-10(counter = (offset_lo, offset_hi, 0, 0), key = (seed_lo, seed_hi))[0] >> 8) * 2^-24, in [0, 1).
+ *   s_i: the penalised value of hx_penalized_argmax_rows (float(x_i) outside the history).
+ *   Greedy row — T == 0 (or not > 0): ids[r] is hx_penalized_argmax_rows' id bit for bit; no draw.  Degenerate row — a
+ *   NaN in the row, or a largest z that is not finite: the same id.
+ *   z_i = s_i / T, one correctly rounded fp32 division.
+ *   top-k: K = n if top_k <= 0 or top_k >= n, else top_k; v_K = the K-th largest z counting multiplicity; every
+ *   z_i >= v_K is kept (tied values stand or fall together).
+ *   top-p: skipped if top_p >= 1 (v* = v_K).  Else, with m = max z, e_i = expf(z_i - m), Z_K = sum of e over {z >= v_K},
+ *   A(v) = sum of e over {z > v}: v* = the smallest value of the row with v* >= v_K and A(v*) <= top_p * Z_K.
+ *   draw: over S = {i : z_i >= v*} in INDEX order, the first i whose inclusive running sum of e exceeds u * Z_S (Z_S the
+ *   sum over S); the last element of S if rounding leaves none.
+ * Sums are fp32: per thread over the elements it owns, then a wave tree and the wave sums in order.  The same (row,
+ * record) gives the same token whatever else is in the batch.  cut_out, u_out (fp32 [rows], may be NULL): v* and u; a
+ * greedy or degenerate row gets NaN and its u.  rows < 1, n < 1, ld < n, n > HX_SAMPLE_MAX_N, total < 0: HX_ERR_SHAPE;
+ * fp32: HX_ERR_DTYPE; ids, logits or sample_params NULL, or a history pointer NULL with total > 0: HX_ERR_NULL —
+ * nothing is launched. */
+#define HX_SAMPLE_MAX_N 35840
+int hx_sample_rows(int64_t* ids, float* cut_out, float* u_out, const void* logits, int64_t rows, int64_t n, int64_t ld,
+                   const int32_t* hist_ids, const int32_t* hist_counts, const int32_t* cu_hist, int64_t total,
+                   const float* penalties, const void* sample_params, int dtype, hx_stream stream);
 /* The same product for M <= 32 with the activations held in REGISTERS (csrc/gemm_xreg.hip): a
  * workgroup spans the whole K of its split, so K <= 4096 needs ONE slab (no K split) and K = 11008
  * three instead of eleven — the fp32 slab traffic of a decode layer drops from 25 MB to 6.5 MB.
