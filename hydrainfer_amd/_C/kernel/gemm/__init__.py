@@ -1,5 +1,6 @@
 """Extension op (no counterpart in hydrainfer._C): decode-batch linear layer on the
 weight-streaming HIP kernel (csrc/gemm_skinny.hip)."""
+import collections
 import ctypes
 from typing import Optional
 
@@ -100,6 +101,25 @@ def gate_up_silu_supported(M: int, inter: int, K: int, dtype: torch.dtype) -> bo
 
 def xreg_workspace_floats(M: int, N: int, K: int) -> int:
     return _lib.lib().hx_linear_decode_xreg_workspace_bytes(M, N, K) // 4
+
+
+XregLaunch = collections.namedtuple("XregLaunch", "kernel kw row_blocks splits packing_splits workgroups lds_bytes ok")
+
+
+def xreg_plan(M: int, N: int, K: int, gate_up: bool = False, wide: bool = False, epi: bool = False) -> XregLaunch:
+    """What the launch of M rows over a [N, K] weight will be (hx_debug_xreg_plan; host only): kernel "narrow" /
+    "wide", k-steps per wave, 16-row blocks of x, K splits, the packing's splits, workgroups, LDS bytes, ok."""
+    out = (ctypes.c_int32 * 8)()
+    _lib.check(_lib.lib().hx_debug_xreg_plan(M, N, K, int(gate_up), int(wide), int(epi), out), "debug_xreg_plan")
+    return XregLaunch("wide" if out[0] else "narrow", *out[1:7], bool(out[7]))
+
+
+def xreg_built(wide: bool):
+    """The table of built instantiations of the narrow / wide kernel: [(k-steps per wave, norm, silu), ...]."""
+    rows, out = [], (ctypes.c_int32 * 3)()
+    while _lib.lib().hx_debug_xreg_built(int(wide), len(rows), out) == 0:
+        rows.append((out[0], bool(out[1]), bool(out[2])))
+    return rows
 
 
 def fragment_major_elems(rows: int, K: int) -> int:

@@ -33,6 +33,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <iterator>
 #include <type_traits>
 #include "attn_common.h"
 
@@ -500,7 +501,7 @@ __global__ __launch_bounds__(256) void gemm_xreg_kernel(HX_XREG_HOT_SIG, const X
       // act[m = 16mb + c][k = 16j + 4g + e], j = pair index: piece ((k/32)*MB + mb)*64 + ((k%32)/8)*16 + c, element k%8
       const int k = 16 * (b + ip * nb) + 4 * g;
       u16* dst = reinterpret_cast<u16*>(p.act) + ((((int64_t)(k >> 5) * MB + mb) * 64 + ((k & 31) >> 3) * 16 + c) << 3) + (k & 7);
-      *reinterpret_cast<u16x4*>(dst) = r;
+      if (mb * 16 + c < p.M) *reinterpret_cast<u16x4*>(dst) = r;      // rows M .. of the last block stay as they are (like the slabs' and the wide kernel's)
     }
   }
   stamp(11);
@@ -1221,6 +1222,33 @@ extern "C" int hx_norm_gate_up_silu_wide_xreg(void* act, void* residual, const f
   const XregPlan pl = xreg_plan(M, 2 * inter, K, true, true);
   if (int rc = check_norm_args(act, packed_gate_up, nm, wide_silu_ok(pl), dtype)) return rc;
   return xreg_launch<1, 1>(xreg_params(pl, packed_gate_up, nullptr, act, nullptr, 0, 1, &nm), pl, dtype, stream);
+}
+
+// ---- what a launch will be (tests pick a shape per instantiation with these; host only, nothing is launched) -------
+extern "C" int hx_debug_xreg_plan(int64_t M, int64_t N, int64_t K, int gate_up, int wide, int epi, int32_t out[8]) {
+  if (!out) return HX_ERR_NULL;
+  const XregPlan pl = xreg_plan(M, N, K, gate_up != 0, wide != 0);
+  const XregGrid g = xreg_grid(pl, epi != 0);
+  out[0] = pl.wide ? 1 : 0;
+  out[1] = pl.KW;
+  out[2] = (int32_t)((M + 15) / 16);
+  out[3] = g.S;
+  out[4] = pl.pk_S;
+  out[5] = g.nb * g.S;
+  out[6] = (int32_t)g.lds;
+  out[7] = pl.valid && g.ok ? 1 : 0;
+  return HX_OK;
+}
+
+extern "C" int hx_debug_xreg_built(int wide, int index, int32_t out[3]) {
+  if (!out) return HX_ERR_NULL;
+  const XregBuilt* table = wide ? kWideBuilt : kNarrowBuilt;
+  const int n = (int)(wide ? std::size(kWideBuilt) : std::size(kNarrowBuilt));
+  if (index < 0 || index >= n) return HX_ERR_SHAPE;
+  out[0] = table[index].kw;
+  out[1] = table[index].norm ? 1 : 0;
+  out[2] = table[index].silu ? 1 : 0;
+  return HX_OK;
 }
 
 // ------------------------------------------------------------------------------------------------------------

@@ -307,7 +307,8 @@ int hx_sample_rows(int64_t* ids, float* cut_out, float* u_out, const void* logit
  * in order): deterministic, not bit-identical to it.  N % 16 == 0, K % 32 == 0.
  * hx_gate_up_silu_xreg: act = silu(x Wg^T) * (x Wu^T) in one launch for K with a single split
  * (hx_gate_up_silu_xreg_supported), act fragment-major [inter]; rounding exactly as
- * hx_linear_decode_partial_xreg -> hx_silu_and_mul_slabs (bit-identical, tested).
+ * hx_linear_decode_partial_xreg -> hx_silu_and_mul_slabs (bit-identical, tested); like that form it leaves rows
+ * M .. 16*MB-1 of act as they were.
  * Replaces: torch.nn.functional.linear at decode batch sizes and silu(gate) * up
  * (hydrainfer/model/llama.py:24-27,48-50, model_forward.py:36). */
 int hx_linear_decode_xreg_supported(int64_t M, int64_t N, int64_t K);
@@ -369,6 +370,20 @@ int hx_gate_up_silu_xreg_supported(int64_t M, int64_t inter, int64_t K);
 int hx_gate_up_silu_xreg(void* act, const void* x, const void* packed_gate_up, int64_t M,
                          int64_t inter, int64_t K, int64_t ldx, int x_fragment_major, int dtype,
                          hx_stream stream);
+/* What a launch of the activations-in-registers kernels WILL BE, answered on the host from the plan and the
+ * instantiation tables the launches themselves read (tests choose their shapes with it; nothing is launched).
+ * hx_debug_xreg_plan: the launch of M rows over a [N, K] weight — gate_up: the interleaved gate|up packing (N = 2 *
+ *   inter); wide: the 33 .. 64-row kernel (which hx_gate_up_xreg runs at every row count); epi: with the silu*mul
+ *   epilogue.  out[0] kernel (0 = 32-row kernel, 1 = wide kernel), out[1] k-steps per wave (the instantiation), out[2]
+ *   16-row blocks of x, out[3] K splits of the launch (the slabs of a plain product), out[4] splits of the packing,
+ *   out[5] workgroups, out[6] dynamic LDS bytes, out[7] 1 if the shape has a built instantiation and a grid, else 0
+ *   (the other words are then what the plan got to).  Whether NORM / EPI are built for it: the *_supported entries.
+ * hx_debug_xreg_built: row `index` of the 32-row (wide = 0) or the wide kernel's table of built instantiations:
+ *   out[0] k-steps per wave, out[1] 1 if built with the norm in front, out[2] 1 if built with the silu*mul epilogue
+ *   (wide kernel: behind the norm only).  index past the end (or negative): HX_ERR_SHAPE.
+ * out == NULL: HX_ERR_NULL. */
+int hx_debug_xreg_plan(int64_t M, int64_t N, int64_t K, int gate_up, int wide, int epi, int32_t out[8]);
+int hx_debug_xreg_built(int wide, int index, int32_t out[3]);
 /* Slab consumers: sum the n_splits slabs in order, round once to T (the projection's output
  * rounding), then behave exactly like hx_add_rms_norm / hx_silu_and_mul on that tensor.
  * partial: [n_splits][rows][hidden] resp. [n_splits][rows][2*inter] (gate | up columns). */
