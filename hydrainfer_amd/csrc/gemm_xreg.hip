@@ -27,6 +27,8 @@
 //             prefetch weights meanwhile, wait on their XCD's flag line, then load x.  Rows are
 //             owned by whoever claims their state word first, and a workgroup that has waited 30 us
 //             claims unstarted rows itself: progress needs ONE resident workgroup (hx_norm_*_xreg).
+//             This hand-over is ONE text for both kernels, included into each: gemm_xreg_produce.inc (the
+//             protocol is stated there) in front of the kernel's weight prefetch, gemm_xreg_wait.inc behind it.
 // Activations between these launches are FRAGMENT-MAJOR (the order the B operands are loaded in;
 // include/hydra_hip.h): row-major x makes every x load touch 16 cache lines for 16 bytes each.
 #include <algorithm>
@@ -247,6 +249,7 @@ __global__ __launch_bounds__(256) void gemm_xreg_kernel(HX_XREG_HOT_SIG, const X
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NBUF = (KW + 7) / 8;
   constexpr int P = 4 * KW;
+  constexpr int mbl = MB;      // 16-row blocks of the fragment-major x
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int g = lane >> 4, c = lane & 15;
@@ -310,57 +313,11 @@ __global__ __launch_bounds__(256) void gemm_xreg_kernel(HX_XREG_HOT_SIG, const X
   u16x8 xb[KW][MB];
   const u16* xp = reinterpret_cast<const u16*>(p.x) + 8 * g;
   const u16* zp = reinterpret_cast<const u16*>(g_zero_line) + 8 * g;
-  auto load_x_block = [&](int q) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int t = 8 * q + j;
-      if (t < KW) {
-        const int r = rot(t);
-        const bool ok = r < kw;
-        const int ks = min(ks0 + w * KW + r, total_ks - 1);
-#pragma unroll
-        for (int mb = 0; mb < MB; ++mb) {
-          const int m = min(mb * 16 + c, p.M - 1);
-          const u16* src = ok ? (p.x_packed ? reinterpret_cast<const u16*>(p.x) + ((int64_t)(ks * MB + mb) * 64 + lane) * 8
-                                            : xp + (int64_t)m * p.ldx + (int64_t)ks * 32)
-                              : zp;
-          if (DBG & 1) xb[t][mb] = u16x8{1, 2, 3, 4, 5, 6, (u16)t, (u16)lane};   // ablation: no x loads
-          else xb[t][mb] = *reinterpret_cast<const u16x8*>(src);
-        }
-      }
-    }
-  };
+#include "gemm_xreg_load_x.inc"
   if (NORM) {
-    // Sync area (zeroed by the caller): word 0 rows done, word 1 error, word 32*(1+xcc) the flag line of
-    // that XCD, words kStateWord.. one ownership word per row.
-    uint32_t* st = p.sync + kStateWord;
-    float* red = reinterpret_cast<float*>(smem);
-    int* cmd = reinterpret_cast<int*>(smem) + 16;
-    auto produce = [&](int row) {      // whole workgroup; true if this workgroup computed the row
-      const bool own = norm_row_256<T, (KW + 31) / 32, MB>(p.nm_partial, p.nm_splits, (int64_t)p.M * p.K,
-                                                           reinterpret_cast<u16*>(p.nm_residual),
-                                                           reinterpret_cast<const u16*>(p.nm_weight), p.nm_eps, p.K, row,
-                                                           const_cast<void*>(p.x), st, red);
-      if (own) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // x is written through: drained = visible
-        __syncthreads();
-        if (threadIdx.x == 0) {
-          const uint32_t old = __hip_atomic_fetch_add(p.sync, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if (old + 1 == (uint32_t)p.M) {   // last row: one flag line per XCD (a single polled line stalls its channel)
-#pragma unroll
-            for (int cpy = 0; cpy < 8; ++cpy)
-              __hip_atomic_store(p.sync + 32 * (1 + cpy), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-        }
-      }
-      return own;
-    };
-    // 1. producers: workgroup r < M computes row r of x FIRST (nothing of its own in flight yet: the row's
-    //    loads and the store drain are not queued behind weight loads — prefetching first cost the whole gain)
-    const int flat = flat_id;
+    constexpr int kNormMaxV = (KW + 31) / 32, kNormKB = 6;
     const int n_wg = nb;      // (a norm-fused launch has ONE split: gridDim.y == 1)
-    if (flat < p.M && !(p.stagger & 6))   // (bit 1 of `stagger`: test hook — nobody produces up front, every row is rescued)
-      for (int row = flat; row < p.M; row += n_wg) produce(row);   // several rows only when N is tiny
+#include "gemm_xreg_produce.inc"
     stamp(1);
     // 2. everyone: weight prefetch (independent of x).  (Round 3, tools/xreg_timeline.py: a producer sees the flag 3 us
     //    later than the others — its first poll returns behind its own prefetch, loads return in order — but letting it
@@ -368,66 +325,10 @@ __global__ __launch_bounds__(256) void gemm_xreg_kernel(HX_XREG_HOT_SIG, const X
 #pragma unroll
     for (int q = 0; q < NBUF; ++q) load_buf(rg_of(0), q);
     __builtin_amdgcn_sched_barrier(0);
-    // 3. wait for the last row.  Wave 0 polls its XCD's flag line.  RESCUE: a producer workgroup that has
-    //    not been dispatched yet cannot be waited for if every CU it could get is held by waiters (two
-    //    processes sharing the GPU, each with such a launch: their workgroups interleave per XCD) — so a
-    //    workgroup that has waited kRescueTicks looks for a row nobody has claimed and computes it itself.
-    //    Progress therefore needs ONE resident workgroup, not the first M.
-    for (;;) {
-      if (threadIdx.x < 64) {
-        const uint32_t* fl = p.sync + 32 * (1 + (__builtin_amdgcn_s_getreg(20 | (3 << 11)) & 7));
-        const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-        int c = -1;   // -1: flag seen; >= 0: row to rescue; -2: gave up
-        while (!__builtin_amdgcn_readfirstlane(__hip_atomic_load(fl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-          __builtin_amdgcn_s_sleep(8);
-          const uint64_t waited = __builtin_amdgcn_s_memrealtime() - t0;
-          if (waited > kRescueTicks && !(p.stagger & 4)) {
-            const uint32_t sv = lane < p.M ? __hip_atomic_load(st + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 1u;
-            uint64_t free_rows = __ballot(sv == 0u);
-            if (free_rows) {
-              // rescuers spread over the unclaimed rows (workgroup f takes the (f mod n)-th of them): K missing
-              // producers are then rescued side by side, not one after the other through the same lowest row
-              for (int skip = flat % __builtin_popcountll(free_rows); skip > 0; --skip) free_rows &= free_rows - 1;
-              c = __builtin_ctzll(free_rows);
-              break;
-            }
-          }
-          // 1 s at 100 MHz: report, never hang the GPU (bit 2 of `stagger`: test hook — no producers, no rescue,
-          // 2 ms bound: every norm-fused launch gives up and must be reported by its caller)
-          if (waited > ((p.stagger & 4) ? 200000ull : 100000000ull)) {
-            if (threadIdx.x == 0) __hip_atomic_fetch_or(p.sync + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            c = -2;
-            break;
-          }
-        }
-        if (threadIdx.x == 0) *cmd = c;
-      }
-      __syncthreads();
-      const int c = *cmd;
-      __syncthreads();
-      if (c < 0) break;
-      produce(c);
-    }
-    stamp(2);
-    asm volatile("" ::: "memory");
-    // 4. x: sc1 loads (served past this CU's L1 and the XCD's L2; the bytes were written through by other CUs).
-    //    Round 3 measured what that costs — 256 CUs x 256 KiB = 67 MB over the XCD links: with sc0 loads (L2 hits; sound
-    //    only by the argument that a kernel's start invalidates the L2) or with no x loads at all the first row group
-    //    ends ~1 us earlier (12.7 -> 11.5 us, tools/xreg_timeline.py) and the decode step does not move: not taken.
-    {
-      const rsrc_t xrs = make_rsrc(p.x), zrs = make_rsrc(g_zero_line);
-#pragma unroll
-      for (int t = 0; t < KW; ++t) {
-        const int r = rot(t);
-        const bool ok = r < kw;
-        const int ks = min(ks0 + w * KW + r, total_ks - 1);
-#pragma unroll
-        for (int mb = 0; mb < MB; ++mb) {
-          // padding slots (K rounded up to the wave's k-step count) read the zero line
-          xb[t][mb] = __builtin_bit_cast(u16x8, __builtin_amdgcn_raw_buffer_load_b128(
-              ok ? xrs : zrs, ok ? (uint32_t)((ks * MB + mb) * 64 + lane) * 16 : (uint32_t)(lane & 7) * 16, 0, kXAux));
-        }
-      }
+#include "gemm_xreg_wait.inc"
+    {      // 4. x
+      const int &x_ks0 = ks0, &x_kw = kw;      // (by reference, here and in the wide kernel: as copies they change its SGPR spill lanes)
+#include "gemm_xreg_load_x_norm.inc"
     }
     __builtin_amdgcn_sched_barrier(0);
   } else {
@@ -514,7 +415,7 @@ __global__ __launch_bounds__(256) void gemm_xreg_kernel(HX_XREG_HOT_SIG, const X
 // PAIR of 16-row groups (two A fragments per k-step share the four x fragments).  The four waves' tiles are summed
 // through LDS after every unit (one barrier per unit, two tile sets used alternately) — a share of up to 11 units
 // would not fit LDS at 16 KiB each.  EPI = 0 only (silu*mul needs the whole K: hx_silu_and_mul_slabs behind it);
-// NORM as in the 32-row kernel, with up to 64 producers.  Same k-step rotation and summation order per split.
+// NORM: the same hand-over text, with up to 64 producers.  Same k-step rotation and summation order per split.
 // Round 5: (a) a launch split is HALF of a packing split in the general sense — split s = (packing split s / 2, half
 // s % 2), the first half takes P = 4 KW k-steps, the second one what is left of the packing split (LLaVA-1.5-13B's down
 // projection: 27 k-steps per wave in the packing -> halves of 14 and 13); (b) RG = row groups per work unit: 2 keeps
@@ -578,102 +479,21 @@ __global__ __launch_bounds__(256) void gemm_xreg_wide_kernel(HX_XREG_HOT_SIG, co
   u16x8 xb[KW][MB];
   const u16* xp = reinterpret_cast<const u16*>(p.x) + 8 * g;
   const u16* zp = reinterpret_cast<const u16*>(g_zero_line) + 8 * g;
-  auto load_x_block = [&](int q) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int t = 8 * q + j;
-      if (t < KW) {
-        const int r = rot(t);
-        const bool ok = r < kw;
-        const int ks = min(ks0 + w * KW + r, total_ks - 1);
-#pragma unroll
-        for (int mb = 0; mb < MB; ++mb) {
-          const int m = min(mb * 16 + c, p.M - 1);
-          const u16* src = ok ? (p.x_packed ? reinterpret_cast<const u16*>(p.x) + ((int64_t)(ks * mbl + min(mb, mbl - 1)) * 64 + lane) * 8
-                                            : xp + (int64_t)m * p.ldx + (int64_t)ks * 32)
-                              : zp;
-          xb[t][mb] = *reinterpret_cast<const u16x8*>(src);
-        }
-      }
-    }
-  };
+  constexpr int DBG = 0;      // (no ablation variants of this kernel)
+#include "gemm_xreg_load_x.inc"
   if (NORM) {
-    uint32_t* st = p.sync + kStateWord;
-    float* red = reinterpret_cast<float*>(smem);
-    int* cmd = reinterpret_cast<int*>(smem) + 16;
-    auto produce = [&](int row) {
-      const bool own = norm_row_256<T, (2 * KW + 31) / 32, MB, 8>(p.nm_partial, p.nm_splits, (int64_t)p.M * p.K,
-                                                               reinterpret_cast<u16*>(p.nm_residual),
-                                                               reinterpret_cast<const u16*>(p.nm_weight), p.nm_eps, p.K, row,
-                                                               const_cast<void*>(p.x), st, red, mbl);
-      if (own) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (threadIdx.x == 0) {
-          const uint32_t old = __hip_atomic_fetch_add(p.sync, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if (old + 1 == (uint32_t)p.M) {
-#pragma unroll
-            for (int cpy = 0; cpy < 8; ++cpy)
-              __hip_atomic_store(p.sync + 32 * (1 + cpy), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-        }
-      }
-      return own;
-    };
+    constexpr int kNormMaxV = (2 * KW + 31) / 32, kNormKB = 8;      // (the down projection hands over 8 slabs)
     const int n_wg = nb * (int)gridDim.y;
-    if (flat_id < p.M && !(p.stagger & 6))
-      for (int row = flat_id; row < p.M; row += n_wg) produce(row);
+#include "gemm_xreg_produce.inc"
 #pragma unroll
     for (int q = 0; q < NBUF; ++q) load_buf(unit_of(0), q, pa);
     __builtin_amdgcn_sched_barrier(0);
-    stamp(1);
-    for (;;) {
-      if (threadIdx.x < 64) {
-        const uint32_t* fl = p.sync + 32 * (1 + (__builtin_amdgcn_s_getreg(20 | (3 << 11)) & 7));
-        const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-        int cc = -1;
-        while (!__builtin_amdgcn_readfirstlane(__hip_atomic_load(fl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-          __builtin_amdgcn_s_sleep(8);
-          const uint64_t waited = __builtin_amdgcn_s_memrealtime() - t0;
-          if (waited > kRescueTicks && !(p.stagger & 4)) {
-            const uint32_t sv = lane < p.M ? __hip_atomic_load(st + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 1u;
-            uint64_t free_rows = __ballot(sv == 0u);
-            if (free_rows) {
-              for (int skip = flat_id % __builtin_popcountll(free_rows); skip > 0; --skip) free_rows &= free_rows - 1;
-              cc = __builtin_ctzll(free_rows);
-              break;
-            }
-          }
-          if (waited > ((p.stagger & 4) ? 200000ull : 100000000ull)) {
-            if (threadIdx.x == 0) __hip_atomic_fetch_or(p.sync + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            cc = -2;
-            break;
-          }
-        }
-        if (threadIdx.x == 0) *cmd = cc;
-      }
-      __syncthreads();
-      const int cc = *cmd;
-      __syncthreads();
-      if (cc < 0) break;
-      produce(cc);
-    }
-    stamp(2);
-    asm volatile("" ::: "memory");
+    stamp(1);      // (behind the prefetch here, in front of it in the 32-row kernel)
+#include "gemm_xreg_wait.inc"
   }
-  // the produced x of one K half (behind the hand-over: kXAux loads)
-  auto load_x_norm = [&](const PassK& ps) {
-    const rsrc_t xrs = make_rsrc(p.x), zrs = make_rsrc(g_zero_line);
-#pragma unroll
-    for (int t = 0; t < KW; ++t) {
-      const int r = rot(t);
-      const bool ok = r < ps.kw;
-      const int ks = min(ps.ks0 + w * KW + r, total_ks - 1);
-#pragma unroll
-      for (int mb = 0; mb < MB; ++mb)
-        xb[t][mb] = __builtin_bit_cast(u16x8, __builtin_amdgcn_raw_buffer_load_b128(
-            ok ? xrs : zrs, ok ? (uint32_t)((ks * mbl + min(mb, mbl - 1)) * 64 + lane) * 16 : (uint32_t)(lane & 7) * 16, 0, kXAux));
-    }
+  auto load_x_norm = [&](const PassK& ps) {      // the produced x of one K half
+    const int &x_ks0 = ps.ks0, &x_kw = ps.kw;
+#include "gemm_xreg_load_x_norm.inc"
   };
   if (NORM) {
     load_x_norm(pa);
@@ -970,51 +790,35 @@ bool dw_interleaved(int64_t N, int64_t K, int flags) {
 }
 
 // ---- launches --------------------------------------------------------------------------------------------------
-template <typename T, int MB, int KW, int EPI, int NORM>
-int launch_kw(const XregParams& p, const XregGrid& g, hipStream_t stream) {
-  const size_t lds = g.lds;
-  if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_xreg_kernel<T, MB, KW, EPI, 0, NORM>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+// One launch of either kernel: its dynamic-LDS limit raised where the launch needs more than the default (per
+// device, so not cached in a static), the hot arguments packed, the launch, its status.
+template <int NORM, typename... P>
+int launch_hot(void (*kernel)(P...), const XregParams& p, const XregGrid& g, hipStream_t stream) {
+  if (g.lds > 48 * 1024) {
+    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds);
     if (e != hipSuccess) return hip_rc(e);
   }
-  const dim3 grid((unsigned)g.nb, (unsigned)g.S);
   XregHot h;
   if (!xreg_hot<NORM>(p, (unsigned)g.nb, &h)) return HX_ERR_SHAPE;
+  hx::launcher(kernel, dim3((unsigned)g.nb, (unsigned)g.S), 256, g.lds, stream)(h.p0, h.p1, h.p2, h.p3, h.p4, h.a, h.b, h.c, h.ldx, p);
+  return check_launch();
+}
+
+template <typename T, int MB, int KW, int EPI, int NORM>
+int launch_kw(const XregParams& p, const XregGrid& g, hipStream_t stream) {
   if (NORM && g.S != 1) return HX_ERR_SHAPE;
-#define HX_XREG_LAUNCH(...) hx::launcher(gemm_xreg_kernel<__VA_ARGS__>, grid, 256, lds, stream)(h.p0, h.p1, h.p2, h.p3, h.p4, h.a, h.b, h.c, h.ldx, p)
   if constexpr (EPI == 0 && NORM == 0 && MB == 2 && (KW == 32 || KW == 29)) if (g_dbg) {   // ablation variants (tools/bench_gemm_xreg.py OPTS=xreg_dbg=..)
-    if (g_dbg == 1) HX_XREG_LAUNCH(T, MB, KW, 0, 1);
-    else if (g_dbg == 2) HX_XREG_LAUNCH(T, MB, KW, 0, 2);
-    else HX_XREG_LAUNCH(T, MB, KW, 0, 3);
-    return check_launch();
+    if (g_dbg == 1) return launch_hot<0>(gemm_xreg_kernel<T, MB, KW, 0, 1>, p, g, stream);
+    if (g_dbg == 2) return launch_hot<0>(gemm_xreg_kernel<T, MB, KW, 0, 2>, p, g, stream);
+    return launch_hot<0>(gemm_xreg_kernel<T, MB, KW, 0, 3>, p, g, stream);
   }
 #if HX_EXPERIMENTS
   // measured and not taken (round 6, profiles/rejected.md): the same kernel over the ROW-MAJOR tensor — one weight copy
   // on a collocated node — streams 16 x 64-byte pieces per wave instruction and is 10-30 % slower (7B, 32 rows)
-  if constexpr (MB == 2 && (KW == 32 || KW == 22 || KW == 29)) if (p.stagger & 16) {
-    HX_XREG_LAUNCH(T, MB, KW, EPI, 0, NORM, 1);
-    return check_launch();
-  }
+  if constexpr (MB == 2 && (KW == 32 || KW == 22 || KW == 29))
+    if (p.stagger & 16) return launch_hot<NORM>(gemm_xreg_kernel<T, MB, KW, EPI, 0, NORM, 1>, p, g, stream);
 #endif
-  HX_XREG_LAUNCH(T, MB, KW, EPI, 0, NORM);
-#undef HX_XREG_LAUNCH
-  return check_launch();
-}
-
-template <typename T, int KW, int EPI, int NORM>
-int launch_wide_kw(const XregParams& p, const XregGrid& g, hipStream_t stream) {
-  constexpr int RG = wide_rg(KW);
-  {   // up to 64 KiB (EPI: + 8 KiB per unit) of dynamic LDS: above the default limit (per device, so not cached in a static)
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_xreg_wide_kernel<T, KW, NORM, RG, EPI>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds);
-    if (e != hipSuccess) return hip_rc(e);
-  }
-  XregHot h;
-  if (!xreg_hot<NORM>(p, (unsigned)g.nb, &h)) return HX_ERR_SHAPE;
-  hx::launcher(gemm_xreg_wide_kernel<T, KW, NORM, RG, EPI>, dim3((unsigned)g.nb, (unsigned)g.S), 256, g.lds, stream)(
-      h.p0, h.p1, h.p2, h.p3, h.p4, h.a, h.b, h.c, h.ldx, p);
-  return check_launch();
+  return launch_hot<NORM>(gemm_xreg_kernel<T, MB, KW, EPI, 0, NORM>, p, g, stream);
 }
 
 // f(integral_constant<i>) for the row i of `table` whose k-step count is kw; HX_ERR_SHAPE when there is none
@@ -1032,7 +836,7 @@ int launch_t(const XregParams& p, const XregPlan& pl, const XregGrid& g, hipStre
   if (pl.wide)
     return with_built_row(kWideBuilt, pl.KW, [&](auto i) -> int {
       constexpr XregBuilt r = kWideBuilt[decltype(i)::value];
-      if constexpr (is_built(r, true, EPI, NORM)) return launch_wide_kw<T, r.kw, EPI, NORM>(p, g, stream);
+      if constexpr (is_built(r, true, EPI, NORM)) return launch_hot<NORM>(gemm_xreg_wide_kernel<T, r.kw, NORM, wide_rg(r.kw), EPI>, p, g, stream);
       else return HX_ERR_SHAPE;
     });
   return with_built_row(kNarrowBuilt, pl.KW, [&](auto i) -> int {
