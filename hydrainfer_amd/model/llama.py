@@ -215,15 +215,26 @@ class LlamaForCausalLM:
                 and hip_gemm.xreg_supported(n, 2 * inter, hid, self.dtype) and hip_gemm.xreg_supported(n, hid, inter, self.dtype)
                 and all(self.state[f"l0.{k}"].stride(1) == 1 for k in ("wgu", "wdown")))
 
+    def _gu_interleaved(self) -> bool:
+        """Whether the packed gate|up weight has its halves interleaved: the descriptor's answer once packed, before
+        that the predicate hx_decode_weight_plan decides by (the 32-row launch has the silu*mul epilogue)."""
+        dw = self.dw.get("l0.wgu")
+        if dw is not None:
+            return dw.interleaved
+        return hip_gemm.gate_up_silu_supported(32, self.shape.intermediate_size, self.shape.hidden_size, self.dtype)
+
     def _wide_ok(self, n: int) -> bool:
         """Batches of 33 .. 64 rows on the activations-in-registers layout (the wide kernel reads the <= 32-row packing:
         no second copy): gate|up, down and qkv of this shape must all be supported (LLaVA-1.5-7B, and since round 5
         LLaVA-1.5-13B: its k-steps per wave, 40 and 27, halve to 20 and 14 + 13; other shapes stay on LDS-slice copies)."""
         hid, inter = self.shape.hidden_size, self.shape.intermediate_size
         qkv_n = self.q_size + 2 * self.kv_size
+        # gate|up: hx_gate_up_xreg reads the INTERLEAVED packing; a shape whose 32-row launch has no silu epilogue is
+        # packed with its halves in order (gemm.DecodeWeight.interleaved) and takes the plain wide product
+        gu_ok = (hip_gemm.gate_up_xreg_supported(n, inter, hid, self.dtype) if self._gu_interleaved()
+                 else hip_gemm.xreg_supported(n, 2 * inter, hid, self.dtype))
         return (32 < n <= 64 and self.use_wide and self.use_xreg and self.xreg_qkv and self.dtype in (torch.float16, torch.bfloat16)
-                and inter % 32 == 0 and hid % 32 == 0 and self._xreg_mlp_ok(32)
-                and hip_gemm.gate_up_xreg_supported(n, inter, hid, self.dtype)
+                and inter % 32 == 0 and hid % 32 == 0 and self._xreg_mlp_ok(32) and gu_ok
                 and hip_gemm.xreg_supported(n, hid, inter, self.dtype) and hip_gemm.xreg_supported(n, qkv_n, hid, self.dtype)
                 and hip_gemm.xreg_supported(32, qkv_n, hid, self.dtype))
 
@@ -327,7 +338,8 @@ class LlamaForCausalLM:
         wide = bool(xreg and n > 32)       # 33 .. 64 rows: two K splits per product; 6 launches per layer, 5 where wide_silu
         fused = xreg and not wide and hip_gemm.gate_up_silu_supported(n, inter, hid, dtype)
         if wide:
-            nf_gu = bool(self.fuse_norm and hip_gemm.gate_up_xreg_supported(n, inter, hid, dtype, with_norm=True))
+            nf_gu = bool(self.fuse_norm and self._gu_interleaved()
+                         and hip_gemm.gate_up_xreg_supported(n, inter, hid, dtype, with_norm=True))
         else:
             nf_gu = bool(xreg and self.fuse_norm and fused and hip_gemm.norm_xreg_supported(n, 2 * inter, hid, dtype, gate_up=True))
         nf_qkv = bool(xreg and self.fuse_norm and f"l{L - 1}.wqkv" in self.packed_x
@@ -350,7 +362,10 @@ class LlamaForCausalLM:
         eps, L = sh.rms_norm_eps, sh.num_hidden_layers
         ws_n = max(hip_gemm.workspace_floats(n, q_size + 2 * kv_size, hid), hip_gemm.workspace_floats(n, hid, q_size),
                    hip_gemm.workspace_floats(n, 2 * inter, hid), hip_gemm.workspace_floats(n, hid, inter),
-                   hip_gemm.xreg_workspace_floats(n, hid, inter))
+                   hip_gemm.xreg_workspace_floats(n, hid, inter),
+                   # qkv and an un-fused gate|up on the activations-in-registers kernel also land in ws where no
+                   # norm-fused launch gives them a buffer of their own (two slabs each at 33 .. 64 rows)
+                   hip_gemm.xreg_workspace_floats(n, q_size + 2 * kv_size, hid), hip_gemm.xreg_workspace_floats(n, 2 * inter, hid))
         ws = torch.empty(ws_n, dtype=torch.float32, device=h.device)
         x = torch.empty_like(h)
         if n > self.decode_rows_prepared and not self.decode_only:
@@ -379,7 +394,9 @@ class LlamaForCausalLM:
                                    dtype=torch.float32, device=h.device)
             wide_silu = bool(wide and nf_gu and dp["wide_silu"])
             if wide and not wide_silu:     # gate|up slabs of the wide product (the norm-fused form reads the o slabs in ws meanwhile)
-                ws_gu = torch.empty(hip_gemm.gate_up_xreg_workspace_floats(n, inter, hid), dtype=torch.float32, device=h.device)
+                gu_interleaved = self._gu_interleaved()
+                ws_gu = torch.empty(hip_gemm.gate_up_xreg_workspace_floats(n, inter, hid) if gu_interleaved
+                                    else hip_gemm.xreg_workspace_floats(n, 2 * inter, hid), dtype=torch.float32, device=h.device)
             actf_w = torch.empty(hip_gemm.fragment_major_elems(n, inter), dtype=h.dtype, device=h.device) if wide_silu else None
         if x0 is not None:
             x = x0          # the first layer's norm came with the embedding gather
@@ -418,7 +435,10 @@ class LlamaForCausalLM:
                             s_gu = hip_gemm.norm_gate_up_xreg(h, ws, s_o, st[f"l{l}.norm2"], eps, xf, pgu, inter, ws_gu, sync[l, 0])
                         else:
                             add_rms_norm_slabs(xf, h, ws, s_o, st[f"l{l}.norm2"], eps, fragment_major=True)
-                            s_gu = hip_gemm.gate_up_xreg(xf, pgu, inter, ws_gu, frag_shape=(n, hid))
+                            if gu_interleaved:
+                                s_gu = hip_gemm.gate_up_xreg(xf, pgu, inter, ws_gu, frag_shape=(n, hid))
+                            else:   # halves in order: the plain wide product already gives [gate | up] columns
+                                s_gu = hip_gemm.linear_decode_partial_xreg(xf, pgu, 2 * inter, ws_gu, frag_shape=(n, hid))
                         a_f = silu_and_mul_slabs(ws_gu, s_gu, n, inter, h.dtype, fragment_major=True)
                 elif nf_gu:
                     hip_gemm.norm_gate_up_silu_xreg(h, ws, s_o, st[f"l{l}.norm2"], eps, xf, pgu, inter, actf, sync[l, 0])
