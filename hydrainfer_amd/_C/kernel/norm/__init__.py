@@ -240,3 +240,63 @@ def logprob_rows(logits: Tensor, top_k: int = 0, out: Optional[Tensor] = None):
                                           logits.stride(0), top_k, _lib.dtype_code(logits), _lib.current_stream()),
                "logprob_rows")
     return ids, lp, top_ids, top_lp
+
+
+def token_logprob_rows_bytes(rows: int, top_k: int) -> int:
+    """Size of the packed result of token_logprob_rows: [logprobs fp32 x rows | ranks int32 x rows | top_ids int32 x
+    rows*K | top_logprobs fp32 x rows*K], one uint8 allocation — a step's prompt scores reach the host in ONE copy."""
+    return rows * (8 + 8 * top_k)
+
+
+def token_logprob_rows_views(packed: Tensor, rows: int, top_k: int):
+    """The four results inside a packed buffer (device or host): (logprobs, ranks, top_ids, top_logprobs)."""
+    if packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous() \
+            or packed.numel() != token_logprob_rows_bytes(rows, top_k):
+        raise _lib.HydraHipError(f"token_logprob_rows: packed buffer must be contiguous uint8 "
+                                 f"[{token_logprob_rows_bytes(rows, top_k)}]")
+    a, b, c = 4 * rows, 8 * rows, 8 * rows + 4 * rows * top_k
+    return (packed[:a].view(torch.float32), packed[a:b].view(torch.int32),
+            packed[b:c].view(torch.int32).view(rows, top_k), packed[c:].view(torch.float32).view(rows, top_k))
+
+
+def token_logprob_rows_packed(logprobs: Tensor, top_k: int) -> Tensor:
+    """The packed buffer behind the results of token_logprob_rows, from its first result: what one copy brings to the
+    host (`token_logprob_rows_views(token_logprob_rows_packed(lp, k).cpu(), rows, k)`)."""
+    n = token_logprob_rows_bytes(logprobs.shape[0], top_k)
+    return torch.empty(0, dtype=torch.uint8, device=logprobs.device).set_(logprobs.untyped_storage(),
+                                                                         logprobs.storage_offset() * 4, (n,))
+
+
+def token_logprob_rows(logits: Tensor, targets: Tensor, top_k: int = 0, out: Optional[Tensor] = None, form: int = 0):
+    """Extension: the log-softmax value of a GIVEN token per row of fp16 / bf16 logits [rows, n] — prompt
+    log-probabilities — its rank and the row's top_k (0..20) most likely entries, one launch (hx_token_logprob_rows:
+    fp32 arithmetic) instead of torch.log_softmax(logits.float(), -1).gather + a comparison count + torch.topk.
+    targets: int32 [rows] on the logits' device.  Returns (logprobs fp32 [rows], ranks int32 [rows] — the number of
+    entries before the target in logprob_rows' order, 0: the target is argmax_rows' id —, top_ids int32 [rows, K],
+    top_logprobs fp32 [rows, K] exactly as logprob_rows gives them).  A row whose target is outside 0..n-1 is not
+    scored and not read: NaN, -1, -1, -inf.  The four are views of one uint8 buffer (`out`, or a new one:
+    token_logprob_rows_bytes / token_logprob_rows_views), which goes to the host in one copy
+    (token_logprob_rows_packed).  form: a measurement hook with no stability promise (hx_token_logprob_rows_ex: the
+    bench tool and the tests name the kernel form with it); callers leave it 0."""
+    _lib.require_gpu(logits, targets, out)
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.dtype not in (torch.float16, torch.bfloat16) \
+            or logits.shape[0] < 1 or logits.shape[1] < 1 or logits.stride(0) < logits.shape[1]:
+        raise _lib.HydraHipError("token_logprob_rows: logits must be fp16 / bf16 [rows, n] (rows, n >= 1) with contiguous rows")
+    rows = logits.shape[0]
+    if targets.dtype != torch.int32 or targets.shape != (rows,) or not targets.is_contiguous() or targets.device != logits.device:
+        raise _lib.HydraHipError("token_logprob_rows: targets must be a contiguous int32 [rows] tensor on the logits' device")
+    if not isinstance(top_k, int) or isinstance(top_k, bool) or not 0 <= top_k <= LOGPROB_MAX_TOP_K:
+        raise _lib.HydraHipError(f"token_logprob_rows: top_k {top_k!r} outside 0..{LOGPROB_MAX_TOP_K}")
+    if out is None:
+        out = torch.empty(token_logprob_rows_bytes(rows, top_k), dtype=torch.uint8, device=logits.device)
+    elif out.device != logits.device or out.data_ptr() % 4:
+        raise _lib.HydraHipError("token_logprob_rows: out must be a 4-byte aligned buffer on the logits' device")
+    lp, ranks, top_ids, top_lp = token_logprob_rows_views(out, rows, top_k)
+    args = (lp.data_ptr(), ranks.data_ptr(), top_ids.data_ptr() if top_k else None, top_lp.data_ptr() if top_k else None,
+            logits.data_ptr(), targets.data_ptr(), rows, logits.shape[1], logits.stride(0), top_k, _lib.dtype_code(logits))
+    if form:
+        rc = _lib.lib().hx_token_logprob_rows_ex(*args, int(form), _lib.current_stream())
+    else:
+        rc = _lib.lib().hx_token_logprob_rows(*args, _lib.current_stream())
+    _lib.check(rc, "token_logprob_rows")
+    return lp, ranks, top_ids, top_lp

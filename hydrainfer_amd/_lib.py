@@ -109,6 +109,8 @@ _SIGNATURES = {
     "hx_embed_rms_norm": (c_int, [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_float, c_int64, c_int64, c_int64, c_int, c_void_p]),
     "hx_argmax_rows": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p]),
     "hx_logprob_rows": (c_int, [c_void_p] * 5 + [c_int64] * 3 + [c_int, c_int, c_void_p]),
+    "hx_token_logprob_rows": (c_int, [c_void_p] * 6 + [c_int64] * 3 + [c_int, c_int, c_void_p]),
+    "hx_token_logprob_rows_ex": (c_int, [c_void_p] * 6 + [c_int64] * 3 + [c_int, c_int, c_int, c_void_p]),
     "hx_penalized_argmax_rows": (c_int, [c_void_p] * 3 + [c_int64] * 3 + [c_void_p] * 3 + [c_int64, c_void_p, c_int, c_void_p]),
     "hx_sample_rows": (c_int, [c_void_p] * 4 + [c_int64] * 3 + [c_void_p] * 3 + [c_int64, c_void_p, c_void_p, c_int, c_void_p]),
     "hx_norm_xreg_supported": (c_int, [c_int64] * 3 + [c_int]),

@@ -202,6 +202,205 @@ __global__ __launch_bounds__(LP_THREADS) void logprob_rows_kernel(int64_t* __res
   }
 }
 
+// ---- hx_token_logprob_rows: the score of a GIVEN id per row (prompt log-probabilities) ------------------------------
+// The same order, the same selection rounds; in place of the argmax the row's target t = targets[row] is looked up (one
+// load) and the rank — the number of elements before (z[t], t) — is counted in the pass that sums the exponentials.
+//   top_k == 0 (perplexity, lm-eval): nothing needs the row twice.  ONE pass gives the maximum, the sum (an online
+//     (max, sum) pair per thread, merged across the workgroup) and the rank; it reads global memory directly (LDS =
+//     false) or the staged row (LDS = true) — profiles/token_logprob_rows.md has both, the launcher keeps the faster.
+//   top_k > 0: the row is staged, round 0 finds the maximum, and the sum is logprob_rows_kernel's term for term, so the
+//     top list equals its bit for bit; then the same rounds.
+// A row whose target lies outside 0 .. n-1 is not scored: sentinels, and the workgroup leaves before reading the row.
+
+// (m, s) += one element: m the largest value so far (-inf: none), s = sum exp(v - m) over the values > -inf.  One
+// exponential per element; never (-inf) - (-inf): a -inf adds nothing.  A NaN element makes s NaN for good; a +inf leaves
+// m = +inf, which the caller turns into s = NaN (exp(inf - inf)), as the two-pass form gives.
+__device__ __forceinline__ void tlp_take(float& m, float& s, float v) {
+  const float e = __expf(-fabsf(v - m));
+  const bool bigger = v > m;
+  s = bigger ? s * e + 1.f : s + (v == -INFINITY ? 0.f : e);
+  m = bigger ? v : m;
+}
+
+// (m, s) += another pair
+__device__ __forceinline__ void tlp_merge(float& m, float& s, float om, float os) {
+  const float nm = fmaxf(m, om);
+  const float ref = nm == -INFINITY ? 0.f : nm;     // both empty: exp(-inf - 0) = 0 twice
+  s = s * __expf(m - ref) + os * __expf(om - ref);
+  m = nm;
+}
+
+template <typename T, bool LDS>
+__global__ __launch_bounds__(LP_THREADS) void token_logprob_rows_kernel(float* __restrict__ logprobs, int32_t* __restrict__ ranks,
+                                                                        int32_t* __restrict__ top_ids,
+                                                                        float* __restrict__ top_logprobs,
+                                                                        const u16* __restrict__ logits,
+                                                                        const int32_t* __restrict__ targets, int32_t n,
+                                                                        int64_t ld, int32_t top_k) {
+  extern __shared__ __attribute__((aligned(16))) u16 staged[];      // LDS: the row, n elements (rounded up to 8)
+  __shared__ float part_v[2][LP_THREADS / 64];
+  __shared__ int part_i[2][LP_THREADS / 64];
+  __shared__ float part_m[LP_THREADS / 64], part_s[LP_THREADS / 64];
+  __shared__ int part_c[LP_THREADS / 64];
+  const int64_t row = blockIdx.x;
+  const int t = targets[row];
+  if (t < 0 || t >= n) {                                             // a row that only samples: nothing of it is read
+    if (threadIdx.x == 0) {
+      logprobs[row] = __builtin_nanf("");
+      ranks[row] = -1;
+    }
+    if ((int)threadIdx.x < top_k) {
+      top_ids[row * top_k + threadIdx.x] = -1;
+      top_logprobs[row * top_k + threadIdx.x] = -INFINITY;
+    }
+    return;
+  }
+  const u16* p = logits + row * ld;
+  const bool gvec = (ld % 8 == 0) && ((reinterpret_cast<uintptr_t>(logits) & 15) == 0);
+  const float zt = T::to_float(p[t]);
+
+  const u16* src = p;
+  bool vec = gvec;
+  if (LDS) {
+    // (logprob_rows_kernel's staging loop, word for word: as a shared function it changes that kernel's code)
+    if (gvec) {
+      const int nvec = n >> 3;
+      for (int i0 = threadIdx.x; i0 < nvec; i0 += 4 * LP_THREADS) {
+        u16x8 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const u16x8*>(p + (int64_t)min(i0 + LP_THREADS * u, nvec - 1) * 8);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int i = i0 + LP_THREADS * u;
+          if (i < nvec) *reinterpret_cast<u16x8*>(staged + i * 8) = v[u];
+        }
+      }
+      for (int i = nvec * 8 + threadIdx.x; i < n; i += LP_THREADS) staged[i] = p[i];
+    } else {
+      for (int i = threadIdx.x; i < n; i += LP_THREADS) staged[i] = p[i];
+    }
+    __syncthreads();
+    src = staged;
+    vec = true;
+  }
+
+  float m, s = 0.f;
+  int before = 0;
+  float cv = 0.f;                               // this thread's candidate and round 0's winner, for the rounds
+  int ci = LP_NONE, bi = LP_NONE;
+  if (top_k == 0) {
+    // the one pass: maximum, sum of exponentials, rank
+    m = -INFINITY;
+    auto take = [&](float v, int i) {
+      tlp_take(m, s, v);
+      before += lp_before(v, i, zt, t) ? 1 : 0;
+    };
+    if (!LDS && vec) {
+      // from global memory: four independent 16-byte loads per thread in flight, as in the staging loop (which
+      // elements a thread takes does not matter here: no selection round follows)
+      const int nvec = n >> 3;
+      for (int i0 = threadIdx.x; i0 < nvec; i0 += 4 * LP_THREADS) {
+        u16x8 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const u16x8*>(p + (int64_t)min(i0 + LP_THREADS * u, nvec - 1) * 8);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int i = i0 + LP_THREADS * u;
+          if (i < nvec) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) take(T::to_float(v[u][e]), i * 8 + e);
+          }
+        }
+      }
+      const int i = nvec * 8 + (int)threadIdx.x;
+      if (i < n) take(T::to_float(p[i]), i);
+    } else {
+      lp_for_own<T>(src, n, vec, take);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const float om = __shfl_xor(m, off, 64);
+      const float os = __shfl_xor(s, off, 64);
+      tlp_merge(m, s, om, os);
+      before += __shfl_xor(before, off, 64);
+    }
+    // sixteen partials, merged in order by every thread
+    if ((threadIdx.x & 63) == 0) {
+      part_m[threadIdx.x >> 6] = m;
+      part_s[threadIdx.x >> 6] = s;
+      part_c[threadIdx.x >> 6] = before;
+    }
+    __syncthreads();
+    m = part_m[0];
+    s = part_s[0];
+    before = part_c[0];
+#pragma unroll
+    for (int k = 1; k < LP_THREADS / 64; ++k) {
+      tlp_merge(m, s, part_m[k], part_s[k]);
+      before += part_c[k];
+    }
+    if (m == INFINITY) s = __builtin_nanf("");
+  } else {
+    // round 0 (the greedy id) and logprob_rows_kernel's sum, term for term — the top list comes out bit-identical to
+    // its — with the rank counted in the same pass over the staged row
+    lp_candidate<T>(src, n, vec, __builtin_nanf(""), -1, cv, ci);
+    m = cv;
+    bi = ci;
+    lp_block_first(m, bi, part_v[0], part_i[0]);
+    const float best = m;
+    lp_for_own<T>(src, n, vec, [&](float v, int i) {
+      s += expf(v - best);
+      before += lp_before(v, i, zt, t) ? 1 : 0;
+    });
+    s = wave_sum(s);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) before += __shfl_xor(before, off, 64);
+    if ((threadIdx.x & 63) == 0) {
+      part_s[threadIdx.x >> 6] = s;
+      part_c[threadIdx.x >> 6] = before;
+    }
+    __syncthreads();
+    s = part_s[0];
+    before = part_c[0];
+#pragma unroll
+    for (int k = 1; k < LP_THREADS / 64; ++k) {
+      s += part_s[k];
+      before += part_c[k];
+    }
+  }
+  const float log_sum = logf(s);
+  if (threadIdx.x == 0) {
+    logprobs[row] = (zt - m) - log_sum;
+    ranks[row] = before;
+  }
+  if (top_k == 0) return;
+
+  // the rounds (logprob_rows_kernel's loop, word for word: as a shared function it changes that kernel's code)
+  const float best = m;
+  float wv = best;
+  int wi = bi;
+  for (int r = 0; r < top_k; ++r) {
+    if (r > 0) {
+      const int nvec8 = (n >> 3) * 8;
+      const int owner = vec ? (wi < nvec8 ? (wi >> 3) & (LP_THREADS - 1) : wi - nvec8) : wi & (LP_THREADS - 1);
+      if (wi != LP_NONE && (owner >> 6) == (int)(threadIdx.x >> 6)) {
+        float nv;
+        int ni;
+        lp_candidate_of<T>(src, n, vec, owner, wv, wi, nv, ni);
+        if ((int)threadIdx.x == owner) { cv = nv; ci = ni; }
+      }
+      wv = cv;
+      wi = ci;
+      lp_block_first(wv, wi, part_v[r & 1], part_i[r & 1]);
+    }
+    if (threadIdx.x == 0) {
+      const bool none = wi == LP_NONE;                                    // K > n: the row is used up
+      top_ids[row * top_k + r] = none ? -1 : wi;
+      top_logprobs[row * top_k + r] = none ? -INFINITY : (wv - best) - log_sum;
+    }
+  }
+}
+
 }  // namespace hx
 
 using namespace hx;
@@ -234,4 +433,45 @@ extern "C" int hx_logprob_rows(int64_t* ids, float* logprobs, int32_t* top_ids, 
   hipStream_t s = (hipStream_t)stream;
   if (dtype == HX_F16) return launch_logprob_rows<F16>(ids, logprobs, top_ids, top_logprobs, logits, rows, n, ld, top_k, s);
   return launch_logprob_rows<BF16>(ids, logprobs, top_ids, top_logprobs, logits, rows, n, ld, top_k, s);
+}
+
+// form: 0 — the form kept per top_k class (profiles/token_logprob_rows.md); 1 — the pass straight from global memory;
+// 2 — the row staged in LDS (rows wider than LP_LDS_ELEMS: form 1 whatever is asked)
+template <typename T>
+static int launch_token_logprob_rows(float* logprobs, int32_t* ranks, int32_t* top_ids, float* top_logprobs, const void* logits,
+                                     const int32_t* targets, int64_t rows, int64_t n, int64_t ld, int top_k, int form,
+                                     hipStream_t s) {
+  if (n <= LP_LDS_ELEMS && (form == 2 || (form == 0 && top_k > 0))) {
+    const size_t lds = (size_t)((n + 7) / 8 * 8) * sizeof(u16);
+    if (lds > 48 * 1024) {
+      hipError_t e = hipFuncSetAttribute((const void*)token_logprob_rows_kernel<T, true>,
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return hip_rc(e);
+    }
+    hx::launcher(token_logprob_rows_kernel<T, true>, (unsigned)rows, LP_THREADS, lds, s)(
+        logprobs, ranks, top_ids, top_logprobs, (const u16*)logits, targets, (int32_t)n, ld, top_k);
+  } else {
+    hx::launcher(token_logprob_rows_kernel<T, false>, (unsigned)rows, LP_THREADS, 0, s)(
+        logprobs, ranks, top_ids, top_logprobs, (const u16*)logits, targets, (int32_t)n, ld, top_k);
+  }
+  return check_launch();
+}
+
+extern "C" int hx_token_logprob_rows_ex(float* logprobs, int32_t* ranks, int32_t* top_ids, float* top_logprobs,
+                                        const void* logits, const int32_t* targets, int64_t rows, int64_t n, int64_t ld,
+                                        int top_k, int dtype, int form, hx_stream stream) {
+  if (rows < 1 || n < 1 || ld < n || n > 0x7ffffff0 || rows > 0x7fffffff) return HX_ERR_SHAPE;
+  if (top_k < 0 || top_k > LP_MAX_K || form < 0 || form > 2) return HX_ERR_SHAPE;
+  if (dtype != HX_F16 && dtype != HX_BF16) return HX_ERR_DTYPE;
+  if (!logprobs || !ranks || !logits || !targets || (top_k > 0 && (!top_ids || !top_logprobs))) return HX_ERR_NULL;
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == HX_F16)
+    return launch_token_logprob_rows<F16>(logprobs, ranks, top_ids, top_logprobs, logits, targets, rows, n, ld, top_k, form, s);
+  return launch_token_logprob_rows<BF16>(logprobs, ranks, top_ids, top_logprobs, logits, targets, rows, n, ld, top_k, form, s);
+}
+
+extern "C" int hx_token_logprob_rows(float* logprobs, int32_t* ranks, int32_t* top_ids, float* top_logprobs,
+                                     const void* logits, const int32_t* targets, int64_t rows, int64_t n, int64_t ld,
+                                     int top_k, int dtype, hx_stream stream) {
+  return hx_token_logprob_rows_ex(logprobs, ranks, top_ids, top_logprobs, logits, targets, rows, n, ld, top_k, dtype, 0, stream);
 }

@@ -67,6 +67,16 @@ def refuse_sampling(request) -> None:
                          "offline engine")
 
 
+def refuse_prompt_logprobs(request) -> None:
+    """Nor prompt log-probabilities: the wire format carries neither a Fill's score lists nor the scores a request has
+    gathered so far (rcb_to_wire), and they would have to follow it from the prefill rank to the rank that streams.  A
+    one-process LocalCluster — separate E, P and D nodes included — has them: the request is one object there."""
+    sp = getattr(request, "sampling_params", None)
+    if sp is not None and getattr(sp, "prompt_logprobs", None) is not None:
+        raise ValueError(f"request {request.request_id}: prompt_logprobs are not available in multi-process serving "
+                         "(one engine process per GPU); use the single-process server or the offline engine")
+
+
 def rcb_to_wire(rcb: RequestControlBlock) -> dict:
     """Everything the next stage needs: the instructions from the current one on (a flat list —
     the linked chain would pickle recursively), the block tables + IPC handles of the caches, the
@@ -319,6 +329,7 @@ class RankEngine:
         refuse_logprobs(request)
         refuse_penalties(request)
         refuse_sampling(request)
+        refuse_prompt_logprobs(request)
         self.token_handlers[request.request_id] = processor
         has_image = request.pixel_values is not None
         dst = entry_rank(self._n_submitted[has_image], self.roles, has_image, self.dead)

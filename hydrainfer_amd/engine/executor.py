@@ -12,13 +12,14 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from hydrainfer_amd._C.kernel.norm import logprob_rows, logprob_rows_packed, logprob_rows_views
+from hydrainfer_amd._C.kernel.norm import (argmax_rows, logprob_rows, logprob_rows_packed, logprob_rows_views,
+                                           token_logprob_rows, token_logprob_rows_packed, token_logprob_rows_views)
 from hydrainfer_amd._lib import HydraHipError
 
 from hydrainfer_amd.engine import rcb as rcb_module
 from hydrainfer_amd.engine.isa import Fill, TextFill
 from hydrainfer_amd.engine.parameters_builder import LanguageModelParametersBuilder
-from hydrainfer_amd.engine.rcb import BatchRequest, TokenLogprob
+from hydrainfer_amd.engine.rcb import BatchRequest, PromptTokenLogprob, TokenLogprob
 from hydrainfer_amd.model.llama import LanguageModelParameters
 from hydrainfer_amd.sampling import (GREEDY_RECORD, NO_PENALTIES, pack_penalty_step, pack_sample_step, penalized_argmax_rows,
                                      sample_rows)
@@ -89,9 +90,11 @@ class BatchFillExecutor:
         pending_launch = self.pending[0] if self.pending is not None else None
         for rcb, inst in batch:
             if (len(inst.token_ids) != 1 or not inst.sample or rcb.sampling_params.logprobs
-                    or rcb.penalty_history is not None or rcb.sampling_params.temperature > 0):
+                    or rcb.penalty_history is not None or rcb.sampling_params.temperature > 0
+                    or inst.score_targets is not None):
                 return None                    # (a request that wants log-probabilities, one under sampling penalties
-                                               # or a sampled one decodes eagerly: execute())
+                                               # or a sampled one decodes eagerly: execute(); so does a one-token piece
+                                               # of a prompt that is being scored — decode Fills carry no score list)
             token = inst.token_ids[0]
             if isinstance(token, PendingToken):
                 if token.launch != pending_launch:
@@ -282,6 +285,9 @@ class BatchFillExecutor:
                 continue                       # already ended by a token that was read back late
             entry = None
             if not inst.is_chunked:
+                if rcb.sampling_params.prompt_logprobs is not None and not rcb.output_token_ids:
+                    for p in rcb.output_token_processors:       # the prompt's scores, complete with this step's, once
+                        p.set_prompt_logprobs(rcb.prompt_logprobs)
                 rcb.metric.token_times.append(now)
                 rcb.output_token_ids.append(token)
                 if rcb.penalty_history is not None:
@@ -300,11 +306,17 @@ class BatchFillExecutor:
                     p.append_token_id(token, last)
         batch.step()
 
-    def _sample_with_logprobs(self, inputs, params, top_k: int):
+    def _sample_with_logprobs(self, inputs, params, top_k: int, logits=None):
         """The eager step of a batch in which some request asked for log-probabilities: the same logits, ids by the same
-        rule, and the scores beside them — one launch (hx_logprob_rows), one packed buffer, ONE device-to-host copy."""
-        ids = self.language_model.forward_logprobs(inputs.input_ids, inputs.image_features, inputs.position_ids,
-                                                   params, top_k)[0]
+        rule, and the scores beside them — one launch (hx_logprob_rows), one packed buffer, ONE device-to-host copy.
+        logits (here and in the two methods below): None, or the ready logits of the step's sampling rows, one row per
+        entry of inputs.selected_token_ids (a step that also scores prompts: _execute_scoring) — the forward is not run
+        again, the same kernels follow."""
+        if logits is None:
+            ids = self.language_model.forward_logprobs(inputs.input_ids, inputs.image_features, inputs.position_ids,
+                                                       params, top_k)[0]
+        else:
+            ids = logprob_rows(logits, top_k)[0]
         rows = ids.shape[0]
         host = logprob_rows_packed(ids, top_k).cpu()                                   # the step's only device sync
         ids, lp, top_ids, top_lp = logprob_rows_views(host, rows, top_k)
@@ -314,14 +326,14 @@ class BatchFillExecutor:
             sampled, scores = [sampled[j] for j in sel], tuple([col[j] for j in sel] for col in scores)
         return sampled, scores
 
-    def _sample_penalized(self, batch: BatchRequest, inputs, params, top_k: Optional[int]):
+    def _sample_penalized(self, batch: BatchRequest, inputs, params, top_k: Optional[int], logits=None):
         """The eager step of a batch in which some request is under frequency / presence / repetition penalties: the same
         logits, then hx_penalized_argmax_rows in place of the argmax — ONE launch for the whole batch; the rows of
         unpenalised requests ride along with an empty history and (0, 0, 1) and get the id they would have got.  The
         step's (token, count) tables reach the device as one pinned buffer in one copy.  top_k: None, or the largest
         top_logprobs of the batch's OTHER requests that asked for log-probabilities (no request has both): their scores
         come from hx_logprob_rows over the same logits."""
-        sel, decode = inputs.selected_token_ids, inputs.all_sequences_decode
+        sel, decode = inputs.selected_token_ids, inputs.all_sequences_decode and logits is None
         n_rows = inputs.input_ids.shape[0] if decode else len(sel)        # the rows of the logits
         entries = [(None, NO_PENALTIES)] * n_rows
         i = 0
@@ -335,11 +347,14 @@ class BatchFillExecutor:
             i += 1
         tables = pack_penalty_step(entries).to_device(self.device)
         lm, scores = self.language_model, None
-        if top_k is None:
+        if top_k is None and logits is None:
             sampled = lm.forward_penalized(inputs.input_ids, inputs.image_features, inputs.position_ids, params,
                                            *tables).tolist()                       # the step's only device sync
+        elif top_k is None:
+            sampled = penalized_argmax_rows(logits, *tables).tolist()
         else:
-            logits = lm.forward_logits(inputs.input_ids, inputs.image_features, inputs.position_ids, params)
+            if logits is None:
+                logits = lm.forward_logits(inputs.input_ids, inputs.image_features, inputs.position_ids, params)
             packed = logprob_rows_packed(logprob_rows(logits, top_k)[0], top_k)
             sampled = penalized_argmax_rows(logits, *tables).tolist()
             _, lp, top_ids, top_lp = logprob_rows_views(packed.cpu(), n_rows, top_k)
@@ -349,14 +364,14 @@ class BatchFillExecutor:
             scores = scores and tuple([col[j] for j in sel] for col in scores)
         return sampled, scores
 
-    def _sample_drawn(self, batch: BatchRequest, inputs, params, top_k: Optional[int]):
+    def _sample_drawn(self, batch: BatchRequest, inputs, params, top_k: Optional[int], logits=None):
         """The eager step of a batch in which some request is SAMPLED (temperature > 0): the same logits, then
         hx_sample_rows — ONE launch for the whole batch.  Greedy requests ride along with temperature 0 and get the id
         they would have got, penalised ones (greedy or sampled) ride along with their history.  A request's offset is the
         number of tokens it has generated so far (the eager path has every token on the host).  The step's sampling
         records and (token, count) tables reach the device as one pinned buffer in one copy.  top_k: as in
         _sample_penalized, for the batch's OTHER requests that asked for log-probabilities."""
-        sel, decode = inputs.selected_token_ids, inputs.all_sequences_decode
+        sel, decode = inputs.selected_token_ids, inputs.all_sequences_decode and logits is None
         n_rows = inputs.input_ids.shape[0] if decode else len(sel)        # the rows of the logits
         entries = [(None, NO_PENALTIES, GREEDY_RECORD)] * n_rows
         i = 0
@@ -371,11 +386,14 @@ class BatchFillExecutor:
             i += 1
         tables = pack_sample_step(entries).to_device(self.device)
         lm, scores = self.language_model, None
-        if top_k is None:
+        if top_k is None and logits is None:
             sampled = lm.forward_sampled(inputs.input_ids, inputs.image_features, inputs.position_ids, params,
                                          *tables).tolist()                         # the step's only device sync
+        elif top_k is None:
+            sampled = sample_rows(logits, *tables).tolist()
         else:
-            logits = lm.forward_logits(inputs.input_ids, inputs.image_features, inputs.position_ids, params)
+            if logits is None:
+                logits = lm.forward_logits(inputs.input_ids, inputs.image_features, inputs.position_ids, params)
             packed = logprob_rows_packed(logprob_rows(logits, top_k)[0], top_k)
             sampled = sample_rows(logits, *tables).tolist()
             _, lp, top_ids, top_lp = logprob_rows_views(packed.cpu(), n_rows, top_k)
@@ -384,6 +402,46 @@ class BatchFillExecutor:
             sampled = [sampled[j] for j in sel]
             scores = scores and tuple([col[j] for j in sel] for col in scores)
         return sampled, scores
+
+    def _execute_scoring(self, batch: BatchRequest, inputs) -> None:
+        """The eager step of a batch in which some request scores its prompt (sampling_params.prompt_logprobs): ONE forward
+        whose last layer is narrowed to the union of the sampling and the scoring rows (inputs.score_plan), ONE
+        hx_token_logprob_rows launch over all of them — target -1 on the rows that only sample: those workgroups leave at
+        once, and nothing is gathered for scoring — then the step's sampling rows (a few) are picked out of the logits and
+        go through the kernels the step would have run without scoring.  The scores reach the host in one copy, the
+        step's only one beside the sampling's."""
+        plan = inputs.score_plan
+        params = LanguageModelParameters(inputs.attention_params, inputs.all_sequences_decode, plan.rows_tensor,
+                                         inputs.image_row_index)
+        logits = self.language_model.forward_logits(inputs.input_ids, inputs.image_features, inputs.position_ids, params)
+        k = plan.top_k
+        packed = token_logprob_rows_packed(token_logprob_rows(logits, plan.targets_tensor, k)[0], k)
+        sampled = scores = None
+        if inputs.selected_token_ids:
+            rows = logits.index_select(0, plan.sample_pos_tensor)
+            sampling = [(rcb, inst) for rcb, inst in batch if isinstance(inst, Fill) and inst.sample]
+            asking = [rcb.sampling_params.top_logprobs for rcb, inst in sampling
+                      if rcb.sampling_params.logprobs and not inst.is_chunked]
+            top_k = max(asking) if asking else None
+            if any(rcb.sampling_params.temperature > 0 for rcb, _ in sampling):
+                sampled, scores = self._sample_drawn(batch, inputs, params, top_k, rows)
+            elif any(rcb.penalty_history is not None for rcb, _ in sampling):
+                sampled, scores = self._sample_penalized(batch, inputs, params, top_k, rows)
+            elif asking:
+                sampled, scores = self._sample_with_logprobs(inputs, params, top_k, rows)
+            else:
+                sampled = argmax_rows(rows).tolist()
+        lp, ranks, top_ids, top_lp = (t.tolist() for t in token_logprob_rows_views(packed.cpu(), len(plan.rows), k))
+        for u, dst in enumerate(plan.dst):
+            if dst is not None:
+                rcb, index = dst
+                own = rcb.sampling_params.prompt_logprobs       # this request's own count out of the step's largest
+                rcb.prompt_logprobs[index] = PromptTokenLogprob(plan.targets[u], lp[u], ranks[u],
+                                                                list(zip(top_ids[u][:own], top_lp[u][:own])))
+        if sampled is None:
+            batch.step()                       # nothing samples: the forward ran for its cache writes and its scores
+        else:
+            self._deliver(batch, sampled, scores)
 
     def _publish_prefix_blocks(self, batch: BatchRequest) -> None:
         """A block's hash enters the prefix cache in the step that computes its last token
@@ -417,6 +475,9 @@ class BatchFillExecutor:
             raise HydraHipError(f"position {max(builder.position_ids)} outside the rotary table "
                                 f"(max_position_embeddings = {max_pos})")
         inputs = builder.build_language_model_parameters()
+        if inputs.score_plan is not None:
+            self._execute_scoring(batch, inputs)
+            return
         params = LanguageModelParameters(inputs.attention_params, inputs.all_sequences_decode,
                                          inputs.selected_token_ids_tensor, inputs.image_row_index)
         if not inputs.selected_token_ids:

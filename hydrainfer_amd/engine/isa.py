@@ -36,9 +36,19 @@ class Fill(Instruction):
         self.sample_dst = sample_dst
         self.hashes = hashes
         self.is_chunked = False   # a chunk's sampled token is discarded (executor.py:163-165)
+        # prompt log-probabilities (only the prompt Fill of a request that asked; else None): parallel to token_ids,
+        # score_targets[j] = the id of the NEXT prompt token if the row of token j is to score it, else -1 (an image
+        # placeholder comes next, or nothing: the last position's next token is the generated one); score_index[j] = the
+        # index of that next token in the request's own token_ids.  Sliced with the other lists by chunk_prefill, so a
+        # chunk's last row already knows the first token of the next chunk.
+        self.score_targets: Optional[List[int]] = None
+        self.score_index: Optional[List[int]] = None
 
     def _split_common(self, rest: "Fill", chunk_size: int) -> None:
         self.insert_next(rest)
+        if self.score_targets is not None:
+            rest.score_targets, rest.score_index = self.score_targets[chunk_size:], self.score_index[chunk_size:]
+            self.score_targets, self.score_index = self.score_targets[:chunk_size], self.score_index[:chunk_size]
         self.token_ids = self.token_ids[:chunk_size]
         self.position_ids = self.position_ids[:chunk_size]
         self.cache_ids = self.cache_ids[:chunk_size]

@@ -8,7 +8,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from hydrainfer_amd.engine.node import LocalCluster
-from hydrainfer_amd.engine.rcb import SamplingParameters, TokenLogprob, TokenParameters
+from hydrainfer_amd.engine.rcb import PromptTokenLogprob, SamplingParameters, TokenLogprob, TokenParameters
 from hydrainfer_amd.engine.request_processor import InstructionCreator, TokenRequest
 from hydrainfer_amd.engine.scheduler import BatchSchedulerConfig
 from hydrainfer_amd.engine.serve import build_node, quiet_gc, warm_library_gemms
@@ -25,6 +25,9 @@ class OfflineInferenceOutput:
     ttft: float = -1.0
     tpot: List[float] = field(default_factory=list)
     output_logprobs: List[TokenLogprob] = field(default_factory=list)    # one per output token if the request asked, else empty
+    # one per token of the request's own token_ids if it asked for prompt_logprobs (None for token 0 and for an image
+    # placeholder), else empty
+    prompt_logprobs: List[Optional[PromptTokenLogprob]] = field(default_factory=list)
 
 
 @dataclass
@@ -43,6 +46,8 @@ class OfflineRequest:
     top_p: float = 1.0                  # a sampled request decodes eagerly
     top_k: int = 0
     seed: Optional[int] = None          # None: the engine assigns one (it is in the request's sampling_params afterwards)
+    prompt_logprobs: Optional[int] = None   # 0..20: the log-probability of every prompt token given what stands before it,
+                                            # with that many alternatives per position; combinable with everything above
 
 
 class OfflineInferenceEngine:
@@ -90,7 +95,8 @@ class OfflineInferenceEngine:
                                    sampling_params=SamplingParameters(r.max_tokens, list(r.eos_token_ids), r.logprobs,
                                                                       r.top_logprobs, r.frequency_penalty,
                                                                       r.presence_penalty, r.repetition_penalty,
-                                                                      r.temperature, r.top_p, r.top_k, r.seed),
+                                                                      r.temperature, r.top_p, r.top_k, r.seed,
+                                                                      prompt_logprobs=r.prompt_logprobs),
                                    token_params=r.token_params)
                 rcb = self.creator.process(req)
                 rcb.metric.arrival_time = time.perf_counter()
@@ -107,5 +113,6 @@ class OfflineInferenceEngine:
                 output_token_ids=list(rcb.output_token_ids), arrival_time=rcb.metric.arrival_time,
                 finished_time=rcb.metric.finished_time, token_times=list(t),
                 ttft=t[0] - rcb.metric.arrival_time if t else -1.0,
-                tpot=[b - a for a, b in zip(t, t[1:])], output_logprobs=list(rcb.output_logprobs)))
+                tpot=[b - a for a, b in zip(t, t[1:])], output_logprobs=list(rcb.output_logprobs),
+                prompt_logprobs=list(rcb.prompt_logprobs)))
         return outs

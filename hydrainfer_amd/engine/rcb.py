@@ -28,6 +28,11 @@ class SamplingParameters:
     top_p: float = 1.0                  # (0, 1]: the smallest set of most likely tokens holding this much probability
     top_k: int = 0                      # >= 0: only the k most likely tokens (ties at the cut are all kept); 0: off
     seed: Optional[int] = None          # 0 .. 2^63 - 1; a sampled request without one is given one at admission
+    # the log-probability of every PROMPT token given what stands before it (vLLM's `prompt_logprobs`;
+    # hx_token_logprob_rows over the prefill's logits): None = off, 0..20 = score, with that many alternatives per position.
+    # Independent of `logprobs` and of the sampling mode: scoring reads the prompt's rows, sampling the last one.  Such a
+    # request's prefill takes no prefix-cache hit (a skipped token has no logits); it decodes like any other.
+    prompt_logprobs: Optional[int] = None
 
 
 MAX_TOP_LOGPROBS = 20
@@ -39,6 +44,17 @@ class TokenLogprob:
     request's top_logprobs most likely (token id, log-probability) pairs, most likely first (ties: lower id first)."""
     token_id: int
     logprob: float
+    top: List[Tuple[int, float]] = field(default_factory=list)
+
+
+@dataclass
+class PromptTokenLogprob:
+    """One prompt token's score: its log-probability given everything before it (image included) under the model's
+    softmax (fp32, hx_token_logprob_rows), its rank — the number of tokens the model ranks before it, 0: it is the greedy
+    choice — and the request's prompt_logprobs most likely (token id, log-probability) pairs at that position."""
+    token_id: int
+    logprob: float
+    rank: int
     top: List[Tuple[int, float]] = field(default_factory=list)
 
 
@@ -103,6 +119,10 @@ class OutputTokenProcessor:
         """The score of the token the next append_token_id call delivers (only for requests with
         sampling_params.logprobs).  Processors that do not care ignore it."""
 
+    def set_prompt_logprobs(self, entries: list) -> None:
+        """The scores of the request's prompt (rcb.prompt_logprobs; only for requests with sampling_params.prompt_logprobs):
+        called once, before the request's first append_token_id.  Processors that do not care ignore it."""
+
     def fail(self, exc: BaseException) -> None:
         """The request was terminated by the engine (a migration that failed twice, a node that died): the reference
         pushes a None token to the stream (hydrainfer/cluster/epdnode.py:440-442, `(request_id, None)`)."""
@@ -129,6 +149,10 @@ class RequestControlBlock:
         self.output_token_processors: List[OutputTokenProcessor] = []
         self.output_token_ids: List[int] = []
         self.output_logprobs: List[TokenLogprob] = []     # parallel to output_token_ids when sampling_params.logprobs, else empty
+        # a request with sampling_params.prompt_logprobs: one entry per token of the request's OWN token_ids (not of the
+        # prompt with its image expanded) — None for token 0 (no context) and for an image placeholder, else a
+        # PromptTokenLogprob, filled in as the prefill's chunks complete; [] for a request that did not ask
+        self.prompt_logprobs: List[Optional[PromptTokenLogprob]] = []
         self.penalty_history = None      # sampling.PenaltyHistory of a penalised request (its delivered tokens), else None
         self.scenario_type: Optional[ScenarioType] = None
         self.metric = RequestMetric()

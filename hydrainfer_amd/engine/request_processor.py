@@ -91,6 +91,20 @@ class InstructionCreator:
             to_hash.append(t)
         return compute_hash(token_ids=to_hash, block_size=self.block_size, prefix=-1), out, total
 
+    def _score_plan(self, own: List[int], expanded: List[int], n_per_image: int):
+        """(score_targets, score_index) of the prompt Fill (engine/isa.py) — own: the request's token_ids, expanded: the
+        prompt with every image placeholder repeated n_per_image times.  Row j of the prefill predicts expanded token
+        j + 1; it scores it unless that token is an image placeholder; the last row's next token is the generated one."""
+        own_index = []                                # expanded position -> index in `own`
+        for i, t in enumerate(own):
+            own_index += [i] * (n_per_image if t == self.image_token_id else 1)
+        assert len(own_index) == len(expanded), "the expanded prompt does not follow the request's tokens"
+        targets, index = [-1] * len(expanded), [-1] * len(expanded)
+        for j in range(len(expanded) - 1):
+            if expanded[j + 1] != self.image_token_id:
+                targets[j], index[j] = expanded[j + 1], own_index[j + 1]
+        return targets, index
+
     def process(self, request: TokenRequest) -> RequestControlBlock:
         rcb = RequestControlBlock()
         rcb.request_id = request.request_id
@@ -102,13 +116,17 @@ class InstructionCreator:
             raise ValueError(f"request {request.request_id}: top_logprobs {top!r} outside 0..{MAX_TOP_LOGPROBS}")
         if top > 0 and not sp.logprobs:
             raise ValueError(f"request {request.request_id}: top_logprobs = {top} needs logprobs = True")
+        ask = sp.prompt_logprobs
+        if ask is not None and (not isinstance(ask, int) or isinstance(ask, bool) or not 0 <= ask <= MAX_TOP_LOGPROBS):
+            raise ValueError(f"request {request.request_id}: prompt_logprobs {ask!r} must be None or an integer "
+                             f"0..{MAX_TOP_LOGPROBS}")
         try:
             penalties = check_penalties(sp.frequency_penalty, sp.presence_penalty, sp.repetition_penalty)
             sampling = check_sampling(sp.temperature, sp.top_p, sp.top_k, sp.seed)
         except ValueError as e:
             raise ValueError(f"request {request.request_id}: {e}") from None
         rcb.sampling_params = SamplingParameters(sp.max_tokens, list(sp.eos_token_ids), sp.logprobs, top, *penalties,
-                                                 *sampling)
+                                                 *sampling, prompt_logprobs=ask)
         if is_sampled(rcb.sampling_params):
             if sp.logprobs:
                 raise ValueError(f"request {request.request_id}: temperature > 0 cannot be combined with logprobs yet: "
@@ -157,6 +175,13 @@ class InstructionCreator:
                                      ids[:n_prompt], True, None, hashes)
         else:
             prefill = TextFill(token_ids[:n_prompt], ids[:n_prompt], ids[:n_prompt], True, None, hashes)
+        if ask is not None:
+            # a skipped token has no logits: the prompt neither matches nor publishes prefix-cache blocks (the image
+            # cache's hashes, ImageEmbed.hashes, are another matter and stay)
+            prefill.hashes = None
+            prefill.score_targets, prefill.score_index = self._score_plan(
+                request.token_ids, token_ids[:n_prompt], self.n_image_tokens_per_image if n_keep is None else n_keep)
+            rcb.prompt_logprobs = [None] * len(request.token_ids)
         b.append(prefill)
         b.append(PDMigrate())
         b.append(PullCache())

@@ -39,6 +39,8 @@ class ChatRequest:
     top_p: float = 1.0              # OpenAI's `top_p`, (0, 1]
     top_k: int = 0                  # extension (the reference's process_logits step 4): integer >= 0, 0 = off
     seed: Optional[int] = None      # OpenAI's `seed`, 0..2^63-1; absent: the engine assigns one
+    prompt_logprobs: Optional[int] = None   # extension (vLLM's name; OpenAI's chat API has no `echo`): 0..20 — the stream's
+                                            # first chunk carries the score of every prompt token, with that many alternatives
 
 
 def parse_chat_completion_request(body: dict) -> ChatRequest:
@@ -137,12 +139,17 @@ def parse_chat_completion_request(body: dict) -> ChatRequest:
     sampling["seed"] = v
     if logprobs and sampling["temperature"] > 0:
         raise ProtocolError("logprobs cannot be combined with temperature > 0 yet")
+    prompt_logprobs = body.get("prompt_logprobs")
+    if prompt_logprobs is not None and (isinstance(prompt_logprobs, bool) or not isinstance(prompt_logprobs, int)
+                                        or not 0 <= prompt_logprobs <= MAX_TOP_LOGPROBS):
+        raise ProtocolError(f"prompt_logprobs: integer 0..{MAX_TOP_LOGPROBS} required")
     try:
         png = base64.b64decode(images[0], validate=True) if images else None
     except Exception:
         raise ProtocolError("image_url: invalid base64")
     return ChatRequest(model=model, role=role, text=text, image_png=png, max_tokens=max_tokens,
-                       stream=bool(body.get("stream", False)), logprobs=logprobs, top_logprobs=top_logprobs, **penalties, **sampling)
+                       stream=bool(body.get("stream", False)), logprobs=logprobs, top_logprobs=top_logprobs, **penalties, **sampling,
+                       prompt_logprobs=prompt_logprobs)
 
 
 def render_llava_chat_prompt(role: str, content: str, bos_token: str = "<s>", eos_token: str = "</s>") -> str:
@@ -178,18 +185,38 @@ def chat_logprobs(token: str, logprob: float, alternatives) -> dict:
     return {"content": [entry]}
 
 
+def chat_prompt_logprobs(entries) -> list:
+    """The `prompt_logprobs` array of a stream's first chunk, one element per token of the prompt: null (the first token:
+    no context; an image placeholder), or {token, logprob, rank, bytes, top_logprobs: [{token, logprob, bytes}, ...]}.
+    entries: None or (token text, logprob, rank, [(token text, logprob), ...]) per token; -inf / NaN -> null as in
+    chat_logprobs."""
+    out = []
+    for e in entries:
+        if e is None:
+            out.append(None)
+            continue
+        token, logprob, rank, alternatives = e
+        out.append({"token": token, "logprob": _finite_or_none(logprob), "rank": int(rank),
+                    "bytes": list(token.encode("utf-8")),
+                    "top_logprobs": [_token_logprob(t, lp) for t, lp in alternatives]})
+    return out
+
+
 def chat_stream_chunk(request_id: str, created: int, model: str, content: Optional[str], first: bool = False,
-                      logprobs: Optional[dict] = None) -> str:
+                      logprobs: Optional[dict] = None, prompt_logprobs: Optional[list] = None) -> str:
     """One `data:` line of the stream (api_server.py:119-146): the first chunk of a choice carries
     delta = {role: assistant, content: ""}, every other one delta = {content: text}; key order and `exclude_unset`
     as pydantic emits them.  logprobs: the chat_logprobs object of a request that asked for them (an extension: the
-    reference has no such field); without it the chunk is byte for byte what it always was."""
+    reference has no such field); without it the chunk is byte for byte what it always was.  prompt_logprobs: the
+    chat_prompt_logprobs array of a request that asked for it, on its first chunk (top level); the same holds."""
     delta = {"role": "assistant", "content": ""} if first else {"content": content}
     choice = {"index": 0, "delta": delta}
     if logprobs is not None:
         choice["logprobs"] = logprobs
-    return "data: " + _dumps({"id": request_id, "object": CHUNK_OBJECT, "created": created, "model": model,
-                              "choices": [choice]}) + "\n\n"
+    chunk = {"id": request_id, "object": CHUNK_OBJECT, "created": created, "model": model, "choices": [choice]}
+    if prompt_logprobs is not None:         # top level, vLLM's place for it; only the first chunk of a request that asked
+        chunk["prompt_logprobs"] = prompt_logprobs
+    return "data: " + _dumps(chunk) + "\n\n"
 
 
 DONE = "data: [DONE]\n\n"

@@ -67,10 +67,25 @@ class StreamOutputTokenProcessor(OutputTokenProcessor):
     def append_logprobs(self, entry) -> None:
         self.scores = entry
 
+    def set_prompt_logprobs(self, entries) -> None:
+        """The prompt's scores, ahead of the first token: the stream's role chunk carries them (proto.chat_prompt_logprobs)."""
+        decode = self.tokenizer.decode
+        self._put(PromptScores(proto.chat_prompt_logprobs(
+            [None if e is None else (decode(e.token_id), e.logprob, e.rank,
+                                     [(decode(t) if t >= 0 else "", lp) for t, lp in e.top]) for e in entries])))
+
     def fail(self, exc: BaseException) -> None:
         if not self.ended:
             self._put(exc)
         self._end()
+
+
+class PromptScores:
+    """A stream item in front of the first token: the `prompt_logprobs` array of the role chunk."""
+    __slots__ = ("array",)
+
+    def __init__(self, array):
+        self.array = array
 
 
 class EngineFrontend:
@@ -200,10 +215,12 @@ class RankEngineFrontend(EngineFrontend):
         self._index = 0
 
     def _start(self, request: TokenRequest, processor: StreamOutputTokenProcessor) -> None:
-        from hydrainfer_amd.engine.distributed import refuse_logprobs, refuse_penalties, refuse_sampling
+        from hydrainfer_amd.engine.distributed import (refuse_logprobs, refuse_penalties, refuse_prompt_logprobs,
+                                                       refuse_sampling)
         refuse_logprobs(request)                      # ValueError: the rank protocol carries no log-probabilities
         refuse_penalties(request)                     # nor sampling penalties
         refuse_sampling(request)                      # nor sampled decoding
+        refuse_prompt_logprobs(request)               # nor prompt log-probabilities
         self.engine.submit(request, processor, self.creator, self._index)
         self._index += 1
 
@@ -258,7 +275,8 @@ class ApiServer:
                                                                presence_penalty=req.presence_penalty,
                                                                repetition_penalty=req.repetition_penalty,
                                                                temperature=req.temperature, top_p=req.top_p,
-                                                               top_k=req.top_k, seed=req.seed))
+                                                               top_k=req.top_k, seed=req.seed,
+                                                               prompt_logprobs=req.prompt_logprobs))
 
     # ------------------------------------------------------------------ HTTP
     @staticmethod
@@ -344,6 +362,7 @@ class ApiServer:
         await writer.drain()
         self.n_streams_open += 1
         first_sent = False
+        prompt_scores = None             # a request that asked for prompt_logprobs: the array its role chunk carries
         try:
             while True:
                 item = await processor.queue.get()
@@ -354,8 +373,12 @@ class ApiServer:
                     # the connection close without [DONE]; here the reason travels in a last event first
                     await self._chunk(writer, "data: " + json.dumps({"error": {"message": str(item), "type": type(item).__name__}}) + "\n\n")
                     return
+                if isinstance(item, PromptScores):
+                    prompt_scores = item.array
+                    continue
                 if not first_sent:       # api_server.py:119-134: role chunk in front of the first text
-                    await self._chunk(writer, proto.chat_stream_chunk(request_id, created, req.model, None, first=True))
+                    await self._chunk(writer, proto.chat_stream_chunk(request_id, created, req.model, None, first=True,
+                                                                      prompt_logprobs=prompt_scores))
                     first_sent = True
                 if isinstance(item, tuple):      # a request that asked for logprobs: every token has a chunk, its scores inside
                     await self._chunk(writer, proto.chat_stream_chunk(request_id, created, req.model, item[0], logprobs=item[1]))

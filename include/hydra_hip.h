@@ -239,6 +239,35 @@ int hx_argmax_rows(int64_t* out, const void* logits, int64_t rows, int64_t n, in
  * fp32: HX_ERR_DTYPE; a missing pointer: HX_ERR_NULL — nothing is launched. */
 int hx_logprob_rows(int64_t* ids, float* logprobs, int32_t* top_ids, float* top_logprobs, const void* logits,
                     int64_t rows, int64_t n, int64_t ld, int top_k, int dtype, hx_stream stream);
+/* hx_token_logprob_rows: the log-probability of a GIVEN token per row — prompt log-probabilities, one launch over the
+ * logits of a prefill chunk (extension; added WITHOUT raising HX_ABI_VERSION: nothing that existed changed).  Replaces no
+ * reference interface: the reference's models end in torch.argmax (hydrainfer/model/llama.py:99-104) and score nothing;
+ * it stands in for torch.log_softmax(logits.float(), -1).gather(-1, targets), a comparison count and torch.topk.
+ * logits: fp16 / bf16 [rows, n], row stride ld elements; targets: int32 [rows] on the device.  Per row with
+ * t = targets[r] in 0 .. n-1:
+ *   logprobs[r]       logits[r, t] - logsumexp(logits[r, :n]), all arithmetic in fp32 (the model's raw softmax);
+ *   ranks[r]          the number of entries that come before (logits[r, t], t) in hx_logprob_rows' order (a NaN first,
+ *                     then the larger value, then the lower index): exact; 0 means t is hx_argmax_rows' id;
+ *   top_ids[r, :K], top_logprobs[r, :K]  exactly what hx_logprob_rows writes, entries past n included.
+ * A row with t < 0 or t >= n is not scored and not read: logprobs NaN, ranks -1, top_ids -1, top_logprobs -inf — rows
+ * that only sample ride along in the same logits at no cost.  A -inf target has logprob -inf; a row that holds a NaN or
+ * a +inf, or nothing but -inf, has every logprob NaN (as log_softmax gives).  top_ids / top_logprobs may be NULL when
+ * top_k == 0.  rows < 1, n < 1, ld < n, top_k outside 0..20: HX_ERR_SHAPE; fp32: HX_ERR_DTYPE; a missing pointer
+ * (targets and ranks included): HX_ERR_NULL — nothing is launched.
+ * hx_token_logprob_rows_ex: A MEASUREMENT HOOK, NO STABILITY PROMISE — the same with the kernel form named, so that
+ * tools/bench_token_logprobs.py and the tests can run both; products call hx_token_logprob_rows, and the forms or this
+ * entry may go when the choice is settled.  form: 0 — the form kept per top_k class, what hx_token_logprob_rows runs;
+ * 1 — one pass straight from global memory; 2 — the row staged in LDS first (rows wider than 65536 elements: form 1).
+ * Another value: HX_ERR_SHAPE.  Results of the forms agree in ranks and ids bit for bit.  With top_k > 0 forms 0 and 2
+ * repeat hx_logprob_rows' sum term for term in its order, so every log-probability equals its bit for bit (tested); form
+ * 1 too where the logits are 16-byte aligned with ld % 8 == 0 (elsewhere its threads own other elements and the order
+ * of the sum differs).  With top_k == 0 the forms agree to fp32 rounding of the sum. */
+int hx_token_logprob_rows(float* logprobs, int32_t* ranks, int32_t* top_ids, float* top_logprobs, const void* logits,
+                          const int32_t* targets, int64_t rows, int64_t n, int64_t ld, int top_k, int dtype,
+                          hx_stream stream);
+int hx_token_logprob_rows_ex(float* logprobs, int32_t* ranks, int32_t* top_ids, float* top_logprobs, const void* logits,
+                             const int32_t* targets, int64_t rows, int64_t n, int64_t ld, int top_k, int dtype, int form,
+                             hx_stream stream);
 /* hx_penalized_argmax_rows: greedy sampling under frequency, presence and repetition penalties, one launch and one read
  * of the logits (extension; added WITHOUT raising HX_ABI_VERSION: nothing that existed changed).  Steps 1-2 of
  * hydrainfer/sampling/logits_processor.py:65-72 followed by the argmax of hydrainfer/model/llama.py:99-104; steps 3-5
