@@ -77,6 +77,17 @@ def refuse_prompt_logprobs(request) -> None:
                          "(one engine process per GPU); use the single-process server or the offline engine")
 
 
+def refuse_constraints(request) -> None:
+    """Nor token constraints (logit_bias, min_tokens, min_p): the wire format carries none of the three, and the bias
+    table would have to follow the request from rank to rank.  A request that sets none of them passes."""
+    sp = getattr(request, "sampling_params", None)
+    if sp is not None and (getattr(sp, "logit_bias", None) or getattr(sp, "min_tokens", 0) > 0
+                           or getattr(sp, "min_p", 0) > 0):
+        raise ValueError(f"request {request.request_id}: logit_bias / min_tokens / min_p are not available in "
+                         "multi-process serving (one engine process per GPU); use the single-process server or the "
+                         "offline engine")
+
+
 def rcb_to_wire(rcb: RequestControlBlock) -> dict:
     """Everything the next stage needs: the instructions from the current one on (a flat list —
     the linked chain would pickle recursively), the block tables + IPC handles of the caches, the
@@ -330,6 +341,7 @@ class RankEngine:
         refuse_penalties(request)
         refuse_sampling(request)
         refuse_prompt_logprobs(request)
+        refuse_constraints(request)
         self.token_handlers[request.request_id] = processor
         has_image = request.pixel_values is not None
         dst = entry_rank(self._n_submitted[has_image], self.roles, has_image, self.dead)

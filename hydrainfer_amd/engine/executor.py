@@ -21,8 +21,8 @@ from hydrainfer_amd.engine.isa import Fill, TextFill
 from hydrainfer_amd.engine.parameters_builder import LanguageModelParametersBuilder
 from hydrainfer_amd.engine.rcb import BatchRequest, PromptTokenLogprob, TokenLogprob
 from hydrainfer_amd.model.llama import LanguageModelParameters
-from hydrainfer_amd.sampling import (GREEDY_RECORD, NO_PENALTIES, pack_penalty_step, pack_sample_step, penalized_argmax_rows,
-                                     sample_rows)
+from hydrainfer_amd.sampling import (GREEDY_RECORD, NO_PENALTIES, pack_constrained_step, pack_penalty_step, pack_sample_step,
+                                     penalized_argmax_rows, sample_rows, sample_rows_constrained)
 
 
 class PendingToken:
@@ -91,9 +91,9 @@ class BatchFillExecutor:
         for rcb, inst in batch:
             if (len(inst.token_ids) != 1 or not inst.sample or rcb.sampling_params.logprobs
                     or rcb.penalty_history is not None or rcb.sampling_params.temperature > 0
-                    or inst.score_targets is not None):
-                return None                    # (a request that wants log-probabilities, one under sampling penalties
-                                               # or a sampled one decodes eagerly: execute(); so does a one-token piece
+                    or inst.score_targets is not None or rcb.token_constraints is not None):
+                return None                    # (a request that wants log-probabilities, one under sampling penalties,
+                                               # a sampled or a constrained one decodes eagerly: execute(); so does a one-token piece
                                                # of a prompt that is being scored — decode Fills carry no score list)
             token = inst.token_ids[0]
             if isinstance(token, PendingToken):
@@ -403,6 +403,48 @@ class BatchFillExecutor:
             scores = scores and tuple([col[j] for j in sel] for col in scores)
         return sampled, scores
 
+    def _sample_constrained(self, batch: BatchRequest, inputs, params, top_k: Optional[int], logits=None):
+        """The eager step of a batch in which some request is CONSTRAINED (logit_bias, min_tokens, min_p): the same
+        logits, then hx_sample_rows_constrained — ONE launch for the whole batch, _sample_drawn with each row's bias table
+        for THIS step (TokenConstraints.step_entries: the end-of-sequence ids banned while the request has generated
+        fewer than min_tokens) and its min_p in the record.  Unconstrained requests ride along with an empty table and
+        min_p 0 and get the id they would have got; a greedy constrained request rides with temperature 0.  Records,
+        (token, count) tables and bias tables reach the device as one pinned buffer in one copy.  top_k: as in
+        _sample_penalized, for the batch's OTHER requests that asked for log-probabilities (raw logits: no request has
+        both)."""
+        sel, decode = inputs.selected_token_ids, inputs.all_sequences_decode and logits is None
+        n_rows = inputs.input_ids.shape[0] if decode else len(sel)        # the rows of the logits
+        entries = [(None, NO_PENALTIES, GREEDY_RECORD, None)] * n_rows
+        i = 0
+        for rcb, inst in batch:
+            if not isinstance(inst, Fill) or not inst.sample:
+                continue
+            sp, n_out = rcb.sampling_params, len(rcb.output_token_ids)
+            record = (sp.temperature, sp.top_p, sp.top_k, sp.seed, n_out, sp.min_p) if sp.temperature > 0 else GREEDY_RECORD
+            bias = rcb.token_constraints.step_entries(n_out) if rcb.token_constraints is not None else None
+            entries[sel[i] if decode else i] = (rcb.penalty_history,
+                                                (sp.frequency_penalty, sp.presence_penalty, sp.repetition_penalty), record,
+                                                bias)
+            i += 1
+        tables = pack_constrained_step(entries).to_device(self.device)
+        lm, scores = self.language_model, None
+        if top_k is None and logits is None:
+            sampled = lm.forward_constrained(inputs.input_ids, inputs.image_features, inputs.position_ids, params,
+                                             *tables).tolist()                     # the step's only device sync
+        elif top_k is None:
+            sampled = sample_rows_constrained(logits, *tables).tolist()
+        else:
+            if logits is None:
+                logits = lm.forward_logits(inputs.input_ids, inputs.image_features, inputs.position_ids, params)
+            packed = logprob_rows_packed(logprob_rows(logits, top_k)[0], top_k)
+            sampled = sample_rows_constrained(logits, *tables).tolist()
+            _, lp, top_ids, top_lp = logprob_rows_views(packed.cpu(), n_rows, top_k)
+            scores = (lp.tolist(), top_ids.tolist(), top_lp.tolist())
+        if decode and n_rows != len(sel):
+            sampled = [sampled[j] for j in sel]
+            scores = scores and tuple([col[j] for j in sel] for col in scores)
+        return sampled, scores
+
     def _execute_scoring(self, batch: BatchRequest, inputs) -> None:
         """The eager step of a batch in which some request scores its prompt (sampling_params.prompt_logprobs): ONE forward
         whose last layer is narrowed to the union of the sampling and the scoring rows (inputs.score_plan), ONE
@@ -423,7 +465,9 @@ class BatchFillExecutor:
             asking = [rcb.sampling_params.top_logprobs for rcb, inst in sampling
                       if rcb.sampling_params.logprobs and not inst.is_chunked]
             top_k = max(asking) if asking else None
-            if any(rcb.sampling_params.temperature > 0 for rcb, _ in sampling):
+            if any(rcb.token_constraints is not None for rcb, _ in sampling):
+                sampled, scores = self._sample_constrained(batch, inputs, params, top_k, rows)
+            elif any(rcb.sampling_params.temperature > 0 for rcb, _ in sampling):
                 sampled, scores = self._sample_drawn(batch, inputs, params, top_k, rows)
             elif any(rcb.penalty_history is not None for rcb, _ in sampling):
                 sampled, scores = self._sample_penalized(batch, inputs, params, top_k, rows)
@@ -489,6 +533,9 @@ class BatchFillExecutor:
             return
         asking = [rcb.sampling_params.top_logprobs for rcb, inst in batch
                   if rcb.sampling_params.logprobs and isinstance(inst, Fill) and inst.sample and not inst.is_chunked]
+        if any(rcb.token_constraints is not None for rcb, inst in batch if isinstance(inst, Fill) and inst.sample):
+            self._deliver(batch, *self._sample_constrained(batch, inputs, params, max(asking) if asking else None))
+            return
         if any(rcb.sampling_params.temperature > 0 for rcb, inst in batch if isinstance(inst, Fill) and inst.sample):
             self._deliver(batch, *self._sample_drawn(batch, inputs, params, max(asking) if asking else None))
             return

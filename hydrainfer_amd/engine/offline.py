@@ -3,7 +3,7 @@ ids and their timing out — the collocated EPD node of engine/node.py behind a 
 Mirrors what the reference's offline path hands back (hydrainfer/request/offline_inference_output.py:5-12);
 prompts are token ids (one image placeholder id where the image goes): there is no tokenizer offline."""
 from dataclasses import dataclass, field
-from typing import List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence
 
 import torch
 
@@ -46,6 +46,13 @@ class OfflineRequest:
     top_p: float = 1.0                  # a sampled request decodes eagerly
     top_k: int = 0
     seed: Optional[int] = None          # None: the engine assigns one (it is in the request's sampling_params afterwards)
+    # token constraints — keyword-only, declared ahead of prompt_logprobs (which stays the last field).  logit_bias: token
+    # id -> bias in -100 .. 100, added to the logit before the penalties; min_tokens: no eos_token_ids entry is emitted
+    # before this many tokens are generated; min_p in [0, 1]: sampled requests keep only tokens with p >= min_p * p_max.
+    # A constrained request decodes eagerly and cannot ask for logprobs
+    logit_bias: Optional[Dict[int, float]] = field(default=None, kw_only=True)
+    min_tokens: int = field(default=0, kw_only=True)
+    min_p: float = field(default=0.0, kw_only=True)
     prompt_logprobs: Optional[int] = None   # 0..20: the log-probability of every prompt token given what stands before it,
                                             # with that many alternatives per position; combinable with everything above
 
@@ -71,6 +78,7 @@ class OfflineInferenceEngine:
                                           n_image_tokens_per_image=self.n_image_tokens, block_size=16, ignore_eos=True,
                                           max_position_embeddings=shape.max_position_embeddings)
         self.processor = ClipImageProcessor(size=vision_model.shape.image_size)
+        self.vocab_size = getattr(shape, "vocab_size", None)      # logit_bias ids are checked against it
         if warm_up:
             warm_library_gemms(language_model, token_budgets, max_running_requests)
             size = vision_model.shape.image_size
@@ -96,9 +104,11 @@ class OfflineInferenceEngine:
                                                                       r.top_logprobs, r.frequency_penalty,
                                                                       r.presence_penalty, r.repetition_penalty,
                                                                       r.temperature, r.top_p, r.top_k, r.seed,
-                                                                      prompt_logprobs=r.prompt_logprobs),
+                                                                      prompt_logprobs=r.prompt_logprobs,
+                                                                      logit_bias=r.logit_bias, min_tokens=r.min_tokens,
+                                                                      min_p=r.min_p),
                                    token_params=r.token_params)
-                rcb = self.creator.process(req)
+                rcb = self.creator.process(req, vocab_size=self.vocab_size)
                 rcb.metric.arrival_time = time.perf_counter()
                 rcbs.append(rcb)
                 self.cluster.add_request(rcb)

@@ -3,7 +3,7 @@ hydrainfer/request/request.py:6-39, hydrainfer/engine/metric.py:5-19 and
 hydrainfer/engine/scenario.py:3-16."""
 from dataclasses import dataclass, field
 from enum import IntEnum
-from typing import List, Optional, Tuple
+from typing import Dict, List, Optional, Tuple
 
 from hydrainfer_amd.engine.isa import Instruction, InstructionList
 from hydrainfer_amd.memory.token_cache import VirtualTokenCache
@@ -28,6 +28,16 @@ class SamplingParameters:
     top_p: float = 1.0                  # (0, 1]: the smallest set of most likely tokens holding this much probability
     top_k: int = 0                      # >= 0: only the k most likely tokens (ties at the cut are all kept); 0: off
     seed: Optional[int] = None          # 0 .. 2^63 - 1; a sampled request without one is given one at admission
+    # token constraints (hx_sample_rows_constrained, include/hydra_hip.h): edits of the logits ahead of the choice, greedy
+    # or sampled.  A constrained request decodes eagerly and cannot ask for logprobs (hx_logprob_rows scores the raw
+    # logits and names the raw argmax); prompt_logprobs stays combinable.  The three are keyword-only — positional
+    # construction is what it was — and declared AHEAD of prompt_logprobs, which stays the last field.
+    # logit_bias: token id -> a bias in -100 .. 100 added to its logit BEFORE the penalties; min_tokens: every
+    # eos_token_ids entry is banned until this many tokens are generated; min_p in [0, 1]: only tokens at least this
+    # likely relative to the most likely one, 0: off
+    logit_bias: Optional[Dict[int, float]] = field(default=None, kw_only=True)
+    min_tokens: int = field(default=0, kw_only=True)
+    min_p: float = field(default=0.0, kw_only=True)
     # the log-probability of every PROMPT token given what stands before it (vLLM's `prompt_logprobs`;
     # hx_token_logprob_rows over the prefill's logits): None = off, 0..20 = score, with that many alternatives per position.
     # Independent of `logprobs` and of the sampling mode: scoring reads the prompt's rows, sampling the last one.  Such a
@@ -154,6 +164,7 @@ class RequestControlBlock:
         # PromptTokenLogprob, filled in as the prefill's chunks complete; [] for a request that did not ask
         self.prompt_logprobs: List[Optional[PromptTokenLogprob]] = []
         self.penalty_history = None      # sampling.PenaltyHistory of a penalised request (its delivered tokens), else None
+        self.token_constraints = None    # sampling.TokenConstraints of a constrained request (logit_bias, min_tokens, min_p), else None
         self.scenario_type: Optional[ScenarioType] = None
         self.metric = RequestMetric()
         self.eos_hit = False      # set when a token read back late (decode look-ahead) was end-of-sequence

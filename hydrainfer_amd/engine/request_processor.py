@@ -12,7 +12,8 @@ from hydrainfer_amd.engine.isa import (EPMigrate, ImageEmbed, ImageEmbedFill, In
 from hydrainfer_amd.engine.rcb import (MAX_TOP_LOGPROBS, RequestControlBlock, RequestMetaData, SamplingParameters,
                                        ScenarioClassifier, TokenParameters)
 from hydrainfer_amd.memory.shared_cache import compute_hash
-from hydrainfer_amd.sampling import PenaltyHistory, check_penalties, check_sampling, is_penalized, is_sampled
+from hydrainfer_amd.sampling import (PenaltyHistory, TokenConstraints, check_constraints, check_penalties, check_sampling,
+                                     is_constrained, is_penalized, is_sampled)
 
 
 @dataclass
@@ -105,7 +106,9 @@ class InstructionCreator:
                 targets[j], index[j] = expanded[j + 1], own_index[j + 1]
         return targets, index
 
-    def process(self, request: TokenRequest) -> RequestControlBlock:
+    def process(self, request: TokenRequest, vocab_size: Optional[int] = None) -> RequestControlBlock:
+        """vocab_size: None (unchecked), or the number of tokens the model scores: a logit_bias id at or above it is
+        refused (the kernel would ignore it: the client would never learn that the bias did nothing)."""
         rcb = RequestControlBlock()
         rcb.request_id = request.request_id
         sp = request.sampling_params or SamplingParameters()
@@ -123,10 +126,22 @@ class InstructionCreator:
         try:
             penalties = check_penalties(sp.frequency_penalty, sp.presence_penalty, sp.repetition_penalty)
             sampling = check_sampling(sp.temperature, sp.top_p, sp.top_k, sp.seed)
+            logit_bias, min_tokens, min_p = check_constraints(sp.logit_bias, sp.min_tokens, sp.min_p)
         except ValueError as e:
             raise ValueError(f"request {request.request_id}: {e}") from None
         rcb.sampling_params = SamplingParameters(sp.max_tokens, list(sp.eos_token_ids), sp.logprobs, top, *penalties,
-                                                 *sampling, prompt_logprobs=ask)
+                                                 *sampling, prompt_logprobs=ask, logit_bias=logit_bias,
+                                                 min_tokens=min_tokens, min_p=min_p)
+        if vocab_size is not None and logit_bias and max(logit_bias) >= vocab_size:
+            raise ValueError(f"request {request.request_id}: logit_bias names token {max(logit_bias)}, the vocabulary has "
+                             f"{vocab_size}")
+        if min_tokens > sp.max_tokens:
+            raise ValueError(f"request {request.request_id}: min_tokens {min_tokens} exceeds max_tokens {sp.max_tokens}")
+        if sp.logprobs and (logit_bias or min_tokens > 0 or min_p > 0):
+            raise ValueError(f"request {request.request_id}: logit_bias / min_tokens / min_p cannot be combined with "
+                             "logprobs yet: hx_logprob_rows scores the raw logits and names the raw argmax, not the "
+                             "constrained choice (prompt_logprobs, which scores the prompt from raw logits by "
+                             "definition, can be)")
         if is_sampled(rcb.sampling_params):
             if sp.logprobs:
                 raise ValueError(f"request {request.request_id}: temperature > 0 cannot be combined with logprobs yet: "
@@ -143,6 +158,8 @@ class InstructionCreator:
             rcb.penalty_history = PenaltyHistory()
         if not self.ignore_eos:
             rcb.sampling_params.eos_token_ids.append(self.eos_token_id)
+        if is_constrained(rcb.sampling_params):       # (after the server's own end-of-sequence id: min_tokens holds it back too)
+            rcb.token_constraints = TokenConstraints(logit_bias, rcb.sampling_params.eos_token_ids, min_tokens)
 
         has_image = request.pixel_values is not None
         n_keep = self._pruned_count(request)

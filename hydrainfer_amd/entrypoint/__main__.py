@@ -53,7 +53,7 @@ def main():
         print("library GEMMs tuned:", tune_library_gemms(lm, rows=tuple(int(r) for r in a.tune_rows.split(","))), flush=True)
     creator = InstructionCreator(image_token_id=itid, n_image_tokens_per_image=576, block_size=16,
                                  max_position_embeddings=shape.max_position_embeddings)
-    tok = HFTokenizer(a.tokenizer) if a.tokenizer else SyntheticTokenizer(image_token_id=itid)
+    tok = HFTokenizer(a.tokenizer) if a.tokenizer else SyntheticTokenizer(image_token_id=itid, vocab_size=shape.vocab_size)
     front = EngineFrontend(LocalCluster([node]), creator, device=dev)
     print(f"serving {a.model} ({a.dtype}, random weights) on http://{a.host}:{a.port}/v1/chat/completions", flush=True)
     ApiServer(front, tok, ClipImageProcessor(), host=a.host, port=a.port).run()

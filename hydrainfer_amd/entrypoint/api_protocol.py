@@ -10,12 +10,13 @@ container by tests/golden/generate_goldens.py."""
 import base64
 import json
 import math
-from dataclasses import dataclass
-from typing import List, Optional
+from dataclasses import dataclass, field
+from typing import Dict, List, Optional
 
 IMAGE_TOKEN = "<image>"            # hydrainfer/model/llava.py:195
 CHUNK_OBJECT = "chat.completion.chunk"
 MAX_TOP_LOGPROBS = 20              # OpenAI's limit
+MAX_STOP_TOKEN_IDS = 16
 
 
 class ProtocolError(ValueError):
@@ -39,6 +40,14 @@ class ChatRequest:
     top_p: float = 1.0              # OpenAI's `top_p`, (0, 1]
     top_k: int = 0                  # extension (the reference's process_logits step 4): integer >= 0, 0 = off
     seed: Optional[int] = None      # OpenAI's `seed`, 0..2^63-1; absent: the engine assigns one
+    # token constraints — keyword-only, declared ahead of prompt_logprobs (which stays the last field).  logit_bias:
+    # OpenAI's, {"<token id>": bias in -100..100}, at most 300 entries; the other three are extensions under vLLM's names:
+    # min_tokens (no end-of-sequence / stop token before this many tokens), min_p (0..1, sampled tokens have
+    # p >= min_p * p_max; 0 = off), stop_token_ids (at most 16 ids that end the generation)
+    logit_bias: Optional[Dict[int, float]] = field(default=None, kw_only=True)
+    min_tokens: int = field(default=0, kw_only=True)
+    min_p: float = field(default=0.0, kw_only=True)
+    stop_token_ids: Optional[List[int]] = field(default=None, kw_only=True)
     prompt_logprobs: Optional[int] = None   # extension (vLLM's name; OpenAI's chat API has no `echo`): 0..20 — the stream's
                                             # first chunk carries the score of every prompt token, with that many alternatives
 
@@ -143,13 +152,57 @@ def parse_chat_completion_request(body: dict) -> ChatRequest:
     if prompt_logprobs is not None and (isinstance(prompt_logprobs, bool) or not isinstance(prompt_logprobs, int)
                                         or not 0 <= prompt_logprobs <= MAX_TOP_LOGPROBS):
         raise ProtocolError(f"prompt_logprobs: integer 0..{MAX_TOP_LOGPROBS} required")
+    constraints = _parse_constraints(body)
+    if logprobs and (constraints["logit_bias"] or constraints["min_tokens"] > 0 or constraints["min_p"] > 0):
+        raise ProtocolError("logprobs cannot be combined with logit_bias / min_tokens / min_p yet")
     try:
         png = base64.b64decode(images[0], validate=True) if images else None
     except Exception:
         raise ProtocolError("image_url: invalid base64")
     return ChatRequest(model=model, role=role, text=text, image_png=png, max_tokens=max_tokens,
                        stream=bool(body.get("stream", False)), logprobs=logprobs, top_logprobs=top_logprobs, **penalties, **sampling,
-                       prompt_logprobs=prompt_logprobs)
+                       prompt_logprobs=prompt_logprobs, **constraints)
+
+
+def _parse_constraints(body: dict) -> dict:
+    """logit_bias, min_tokens, min_p and stop_token_ids of a request body, as ChatRequest's fields."""
+    from hydrainfer_amd.sampling import MAX_LOGIT_BIAS
+    logit_bias = body.get("logit_bias")
+    if logit_bias is not None:
+        if not isinstance(logit_bias, dict):
+            raise ProtocolError("logit_bias: object of token id -> bias required")
+        if len(logit_bias) > MAX_LOGIT_BIAS:
+            raise ProtocolError(f"logit_bias: at most {MAX_LOGIT_BIAS} entries")
+        table = {}
+        for key, b in logit_bias.items():
+            # (JSON keys are strings; OpenAI writes the token id in decimal.  isdecimal + isascii: no sign, no blank)
+            if not isinstance(key, str) or not (key.isascii() and key.isdecimal()) or int(key) > 0x7fffffff:
+                raise ProtocolError(f"logit_bias: key {key!r} is no token id (a non-negative integer as a decimal string)")
+            if isinstance(b, bool) or not isinstance(b, (int, float)) or not -100.0 <= b <= 100.0:      # (a NaN fails the range)
+                raise ProtocolError(f"logit_bias[{key!r}]: number in -100..100 required")
+            table[int(key)] = float(b)
+        if len(table) != len(logit_bias):
+            raise ProtocolError("logit_bias: two keys name the same token id")
+        logit_bias = table or None
+    min_tokens = body.get("min_tokens")
+    if min_tokens is None:
+        min_tokens = 0
+    if isinstance(min_tokens, bool) or not isinstance(min_tokens, int) or min_tokens < 0:
+        raise ProtocolError("min_tokens: integer >= 0 required")
+    min_p = body.get("min_p")
+    if min_p is None:
+        min_p = 0.0
+    if isinstance(min_p, bool) or not isinstance(min_p, (int, float)) or not 0.0 <= min_p <= 1.0:       # (a NaN fails the range)
+        raise ProtocolError("min_p: number in 0..1 required")
+    stop = body.get("stop_token_ids")
+    if stop is not None:
+        if not isinstance(stop, list) or len(stop) > MAX_STOP_TOKEN_IDS:
+            raise ProtocolError(f"stop_token_ids: list of at most {MAX_STOP_TOKEN_IDS} token ids required")
+        for t in stop:
+            if isinstance(t, bool) or not isinstance(t, int) or not 0 <= t <= 0x7fffffff:
+                raise ProtocolError("stop_token_ids: integers >= 0 required")
+        stop = list(stop) or None
+    return {"logit_bias": logit_bias, "min_tokens": min_tokens, "min_p": float(min_p), "stop_token_ids": stop}
 
 
 def render_llava_chat_prompt(role: str, content: str, bos_token: str = "<s>", eos_token: str = "</s>") -> str:

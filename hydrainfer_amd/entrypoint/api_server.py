@@ -104,6 +104,7 @@ class EngineFrontend:
         self.live: dict = {}
         self.live_lock = threading.Lock()
         self.rcb_of: dict = {}          # processor id -> its request (local engine): what a cancelled stream ends
+        self.vocab_size: Optional[int] = None     # the tokenizer's (ApiServer sets it): a logit_bias id at or above it is refused
 
     def _forget(self, processor) -> None:
         with self.live_lock:
@@ -154,7 +155,7 @@ class EngineFrontend:
         return n
 
     def _start(self, request: TokenRequest, processor: StreamOutputTokenProcessor) -> None:
-        rcb = self.creator.process(request)           # ValueError: prompt + max_tokens past the rotary table
+        rcb = self.creator.process(request, vocab_size=self.vocab_size)    # ValueError: prompt + max_tokens past the rotary table
         rcb.register_output_token_processor(processor)
         self.rcb_of[id(processor)] = rcb
         self.cluster.add_request(rcb)
@@ -215,12 +216,13 @@ class RankEngineFrontend(EngineFrontend):
         self._index = 0
 
     def _start(self, request: TokenRequest, processor: StreamOutputTokenProcessor) -> None:
-        from hydrainfer_amd.engine.distributed import (refuse_logprobs, refuse_penalties, refuse_prompt_logprobs,
-                                                       refuse_sampling)
+        from hydrainfer_amd.engine.distributed import (refuse_constraints, refuse_logprobs, refuse_penalties,
+                                                       refuse_prompt_logprobs, refuse_sampling)
         refuse_logprobs(request)                      # ValueError: the rank protocol carries no log-probabilities
         refuse_penalties(request)                     # nor sampling penalties
         refuse_sampling(request)                      # nor sampled decoding
         refuse_prompt_logprobs(request)               # nor prompt log-probabilities
+        refuse_constraints(request)                   # nor logit_bias / min_tokens / min_p
         self.engine.submit(request, processor, self.creator, self._index)
         self._index += 1
 
@@ -248,11 +250,17 @@ class ApiServer:
         self.server: Optional[asyncio.base_events.Server] = None
         self._ids = itertools.count(1)          # (request ids are drawn on executor threads)
         self.n_streams_open = 0
+        if frontend is not None and getattr(frontend, "vocab_size", None) is None:
+            frontend.vocab_size = getattr(tokenizer, "vocab_size", None)
 
     # ------------------------------------------------------------------ request -> engine
     def _token_request(self, req: proto.ChatRequest) -> TokenRequest:
         prompt = self.tokenizer.apply_chat_template(req.role, req.text)          # api_server.py:99
         token_ids = self.tokenizer.encode(prompt)
+        vocab_size = getattr(self.tokenizer, "vocab_size", None)
+        if req.logit_bias and vocab_size is not None and max(req.logit_bias) >= vocab_size:
+            # (the creator refuses it as well, but by then the stream is open: here the answer is still a 400)
+            raise proto.ProtocolError(f"logit_bias: token id {max(req.logit_bias)} outside the vocabulary ({vocab_size})")
         pixels, image_hash, size = None, 0, tuple(self.image_size)
         if req.image_png is not None:
             from PIL import Image
@@ -276,7 +284,10 @@ class ApiServer:
                                                                repetition_penalty=req.repetition_penalty,
                                                                temperature=req.temperature, top_p=req.top_p,
                                                                top_k=req.top_k, seed=req.seed,
-                                                               prompt_logprobs=req.prompt_logprobs))
+                                                               prompt_logprobs=req.prompt_logprobs,
+                                                               eos_token_ids=list(req.stop_token_ids or ()),
+                                                               logit_bias=req.logit_bias, min_tokens=req.min_tokens,
+                                                               min_p=req.min_p))
 
     # ------------------------------------------------------------------ HTTP
     @staticmethod

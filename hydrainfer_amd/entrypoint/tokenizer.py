@@ -5,7 +5,7 @@ There are no tokenizer files offline, so two implementations: HFTokenizer wraps 
 the reference's LlavaTokenizer does (used when a checkpoint directory exists), SyntheticTokenizer is a deterministic
 stand-in for benchmarks on random weights: words hash to ids, ids print as `<id>` pieces."""
 import re
-from typing import List
+from typing import List, Optional
 
 from hydrainfer_amd.entrypoint.api_protocol import IMAGE_TOKEN, render_llava_chat_prompt
 
@@ -14,8 +14,11 @@ class SyntheticTokenizer:
     """text -> ids: `<image>` -> image_token_id, `<s>` -> bos id, every other whitespace-separated piece -> a stable
     64-bit FNV-1a hash folded into [lo, hi).  ids -> text: ' <id>'.  Same interface as the reference's Tokenizer."""
 
-    def __init__(self, image_token_id: int = 32000, lo: int = 1000, hi: int = 31999, bos_token_id: int = 1, eos_token_id: int = 2):
+    def __init__(self, image_token_id: int = 32000, lo: int = 1000, hi: int = 31999, bos_token_id: int = 1, eos_token_id: int = 2,
+                 vocab_size: Optional[int] = None):
         self.image_token_id, self.lo, self.hi = image_token_id, lo, hi
+        # what a request's logit_bias ids are checked against; default: the smallest vocabulary that holds every id encode() gives
+        self.vocab_size = vocab_size if vocab_size is not None else max(hi, image_token_id + 1)
         self.bos_token, self.eos_token = "<s>", "</s>"
         self.bos_token_id, self.eos_token_id = bos_token_id, eos_token_id
 
@@ -54,6 +57,7 @@ class HFTokenizer:
         self.tokenizer = AutoTokenizer.from_pretrained(path)
         self.bos_token, self.eos_token = self.tokenizer.bos_token, self.tokenizer.eos_token
         self.eos_token_id = self.tokenizer.eos_token_id
+        self.vocab_size = len(self.tokenizer)         # added tokens included
 
     def encode(self, prompt: str) -> List[int]:
         return self.tokenizer.encode(prompt, add_special_tokens=False)

@@ -606,4 +606,14 @@ class LlamaForCausalLM:
         logits = self.forward_logits(input_ids_or_embeds, position_ids, model_params)
         return sample_rows(logits, sample_params, hist_ids, hist_counts, cu_hist, penalties, out)
 
+    def forward_constrained(self, input_ids_or_embeds, position_ids, model_params, sample_params, bias_ids, bias_values,
+                            cu_bias, hist_ids=None, hist_counts=None, cu_hist=None, penalties=None, out=None):
+        """forward() for a step with a constrained request (logit_bias, min_tokens, min_p): the same logits, then ONE
+        launch (sampling.sample_rows_constrained) — forward_sampled() with the rows' bias tables added ahead of the
+        penalties and min_p in the records.  Eager only: not part of the launch plan or the captured graphs."""
+        from hydrainfer_amd.sampling import sample_rows_constrained
+        logits = self.forward_logits(input_ids_or_embeds, position_ids, model_params)
+        return sample_rows_constrained(logits, sample_params, bias_ids, bias_values, cu_bias, hist_ids, hist_counts, cu_hist,
+                                       penalties, out)
+
     __call__ = forward

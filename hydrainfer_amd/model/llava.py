@@ -62,4 +62,16 @@ class LlavaLanguageModel:
         return sample_rows(self.forward_logits(input_ids, image_features, position_ids, model_params), sample_params,
                            hist_ids, hist_counts, cu_hist, penalties, out)
 
+    def forward_constrained(self, input_ids: Tensor, image_features: Optional[Tensor], position_ids: Tensor,
+                            model_params: LanguageModelParameters, sample_params: Tensor, bias_ids: Tensor,
+                            bias_values: Tensor, cu_bias: Tensor, hist_ids: Optional[Tensor] = None,
+                            hist_counts: Optional[Tensor] = None, cu_hist: Optional[Tensor] = None,
+                            penalties: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+        """forward() under token constraints: one launch behind the logits (hx_sample_rows_constrained) with the rows'
+        sampling records (min_p in word 3), their (token, bias) tables and, optionally, their (token, count) tables."""
+        from hydrainfer_amd.sampling import sample_rows_constrained
+        return sample_rows_constrained(self.forward_logits(input_ids, image_features, position_ids, model_params),
+                                       sample_params, bias_ids, bias_values, cu_bias, hist_ids, hist_counts, cu_hist,
+                                       penalties, out)
+
     __call__ = forward

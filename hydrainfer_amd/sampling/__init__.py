@@ -16,7 +16,12 @@ it.  Here it holds the GENERATED tokens only, for all three penalties: prompts c
 copies of one id) and chat-template tokens, which a prompt-inclusive repetition penalty would push down; OpenAI's
 frequency / presence penalties are defined over the sampled text as well.  The first generated token therefore sees an
 empty history.  `PenaltyHistory` is that table on the host, `pack_penalty_step` turns a step's tables into the kernel's
-CSR, `pack_sample_step` does the same with the rows' sampling records in front — one buffer, one host-to-device copy."""
+CSR, `pack_sample_step` does the same with the rows' sampling records in front — one buffer, one host-to-device copy.
+
+Token constraints (`logit_bias`, `min_tokens`, `min_p`): `sample_rows_constrained` (hx_sample_rows_constrained) is
+`sample_rows` with a per-row (token, bias) table added ahead of the penalties and a min_p cut; `TokenConstraints` is a
+request's table on the host (min_tokens: its end-of-sequence ids banned while too few tokens stand), and
+`pack_constrained_step` appends the step's bias CSR to `pack_sample_step`'s buffer."""
 import math
 from array import array
 from typing import Optional, Sequence, Tuple
@@ -153,6 +158,39 @@ def pack_penalty_step(entries) -> PenaltyStep:
     return PenaltyStep(buf, rows, total)
 
 
+def _check_sample_arguments(what: str, logits, sample_params, hist_ids, hist_counts, cu_hist, penalties, out, cut_out, u_out):
+    """The argument checks sample_rows and sample_rows_constrained share -> (rows, total, out)."""
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.dtype not in (torch.float16, torch.bfloat16) \
+            or logits.shape[0] < 1 or not 1 <= logits.shape[1] <= SAMPLE_MAX_N or logits.stride(0) < logits.shape[1]:
+        raise _lib.HydraHipError(f"{what}: logits must be fp16 / bf16 [rows, n] (rows >= 1, 1 <= n <= {SAMPLE_MAX_N}) "
+                                 "with contiguous rows")
+    rows = logits.shape[0]
+    if sample_params.dtype != torch.int32 or tuple(sample_params.shape) != (rows, SAMPLE_RECORD_WORDS) \
+            or not sample_params.is_contiguous():
+        raise _lib.HydraHipError(f"{what}: sample_params must be a contiguous int32 tensor of shape "
+                                 f"[{rows}, {SAMPLE_RECORD_WORDS}]")
+    tables = (hist_ids, hist_counts, cu_hist, penalties)
+    total = 0
+    if any(t is not None for t in tables):
+        if any(t is None for t in tables):
+            raise _lib.HydraHipError(f"{what}: hist_ids, hist_counts, cu_hist and penalties come together or not at all")
+        total = hist_ids.numel()
+        for name, t, shape in (("hist_ids", hist_ids, (total,)), ("hist_counts", hist_counts, (total,)),
+                               ("cu_hist", cu_hist, (rows + 1,))):
+            if t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous():
+                raise _lib.HydraHipError(f"{what}: {name} must be a contiguous int32 tensor of shape {list(shape)}")
+        if penalties.dtype != torch.float32 or tuple(penalties.shape) != (rows, 3) or not penalties.is_contiguous():
+            raise _lib.HydraHipError(f"{what}: penalties must be a contiguous fp32 tensor of shape [{rows}, 3]")
+    if out is None:
+        out = torch.empty(rows, dtype=torch.int64, device=logits.device)
+    elif out.dtype != torch.int64 or out.shape != (rows,) or not out.is_contiguous() or out.device != logits.device:
+        raise _lib.HydraHipError(f"{what}: out must be a contiguous int64 [rows] tensor on the logits' device")
+    for name, t in (("cut_out", cut_out), ("u_out", u_out)):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (rows,) or not t.is_contiguous()):
+            raise _lib.HydraHipError(f"{what}: {name} must be a contiguous fp32 tensor of shape [{rows}]")
+    return rows, total, out
+
+
 def sample_rows(logits: Tensor, sample_params: Tensor, hist_ids: Optional[Tensor] = None,
                 hist_counts: Optional[Tensor] = None, cu_hist: Optional[Tensor] = None,
                 penalties: Optional[Tensor] = None, out: Optional[Tensor] = None, cut_out: Optional[Tensor] = None,
@@ -164,34 +202,8 @@ def sample_rows(logits: Tensor, sample_params: Tensor, hist_ids: Optional[Tensor
     cut_out / u_out: fp32 [rows] tensors that receive each row's top-p cut v* (NaN for a greedy or degenerate row) and
     its uniform number u."""
     _lib.require_gpu(logits, sample_params, hist_ids, hist_counts, cu_hist, penalties, out, cut_out, u_out)
-    if logits.dim() != 2 or logits.stride(1) != 1 or logits.dtype not in (torch.float16, torch.bfloat16) \
-            or logits.shape[0] < 1 or not 1 <= logits.shape[1] <= SAMPLE_MAX_N or logits.stride(0) < logits.shape[1]:
-        raise _lib.HydraHipError(f"sample_rows: logits must be fp16 / bf16 [rows, n] (rows >= 1, 1 <= n <= {SAMPLE_MAX_N}) "
-                                 "with contiguous rows")
-    rows = logits.shape[0]
-    if sample_params.dtype != torch.int32 or tuple(sample_params.shape) != (rows, SAMPLE_RECORD_WORDS) \
-            or not sample_params.is_contiguous():
-        raise _lib.HydraHipError(f"sample_rows: sample_params must be a contiguous int32 tensor of shape "
-                                 f"[{rows}, {SAMPLE_RECORD_WORDS}]")
-    tables = (hist_ids, hist_counts, cu_hist, penalties)
-    total = 0
-    if any(t is not None for t in tables):
-        if any(t is None for t in tables):
-            raise _lib.HydraHipError("sample_rows: hist_ids, hist_counts, cu_hist and penalties come together or not at all")
-        total = hist_ids.numel()
-        for name, t, shape in (("hist_ids", hist_ids, (total,)), ("hist_counts", hist_counts, (total,)),
-                               ("cu_hist", cu_hist, (rows + 1,))):
-            if t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous():
-                raise _lib.HydraHipError(f"sample_rows: {name} must be a contiguous int32 tensor of shape {list(shape)}")
-        if penalties.dtype != torch.float32 or tuple(penalties.shape) != (rows, 3) or not penalties.is_contiguous():
-            raise _lib.HydraHipError(f"sample_rows: penalties must be a contiguous fp32 tensor of shape [{rows}, 3]")
-    if out is None:
-        out = torch.empty(rows, dtype=torch.int64, device=logits.device)
-    elif out.dtype != torch.int64 or out.shape != (rows,) or not out.is_contiguous() or out.device != logits.device:
-        raise _lib.HydraHipError("sample_rows: out must be a contiguous int64 [rows] tensor on the logits' device")
-    for name, t in (("cut_out", cut_out), ("u_out", u_out)):
-        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (rows,) or not t.is_contiguous()):
-            raise _lib.HydraHipError(f"sample_rows: {name} must be a contiguous fp32 tensor of shape [{rows}]")
+    rows, total, out = _check_sample_arguments("sample_rows", logits, sample_params, hist_ids, hist_counts, cu_hist, penalties,
+                                               out, cut_out, u_out)
     ptr = (lambda t: t.data_ptr()) if total else (lambda t: None)
     _lib.check(_lib.lib().hx_sample_rows(
         out.data_ptr(), cut_out.data_ptr() if cut_out is not None else None, u_out.data_ptr() if u_out is not None else None,
@@ -224,13 +236,14 @@ def is_sampled(sampling_params) -> bool:
 
 def pack_sample_records(records, out: Optional[np.ndarray] = None) -> np.ndarray:
     """records: one (temperature, top_p, top_k, seed, offset) per logits row -> int32 [rows, 8], the layout of
-    include/hydra_hip.h (into `out` if given)."""
+    include/hydra_hip.h (into `out` if given).  A sixth element is the row's min_p (word 3, fp32 bits: read by
+    hx_sample_rows_constrained only); a five-element record packs it as 0."""
     rows = len(records)
     if out is None:
         out = np.zeros((rows, SAMPLE_RECORD_WORDS), dtype=np.int32)
     out[:, :2] = np.asarray([(r[0], r[1]) for r in records], dtype=np.float32).reshape(rows, 2).view(np.int32)
     out[:, 2] = [r[2] for r in records]
-    out[:, 3] = 0
+    out[:, 3] = np.asarray([r[5] if len(r) > 5 else 0.0 for r in records], dtype=np.float32).view(np.int32)
     out[:, 4:].view(np.uint64)[:] = np.asarray([(r[3], r[4]) for r in records], dtype=np.uint64).reshape(rows, 2)
     return out
 
@@ -273,3 +286,152 @@ def pack_sample_step(entries) -> SampleStep:
     pack_sample_records([rec for _, _, rec in entries], buf[:r].reshape(rows, SAMPLE_RECORD_WORDS))
     buf[r:] = tables.buffer
     return SampleStep(buf, rows, tables.total)
+
+
+# ---- token constraints: logit_bias, min_tokens, min_p (hx_sample_rows_constrained, include/hydra_hip.h) ----
+MAX_LOGIT_BIAS = 300            # entries of one request's logit_bias (OpenAI's limit)
+LOGIT_BIAS_RANGE = 100.0        # |bias| at most this (OpenAI's range)
+
+
+def sample_rows_constrained(logits: Tensor, sample_params: Tensor, bias_ids: Tensor, bias_values: Tensor, cu_bias: Tensor,
+                            hist_ids: Optional[Tensor] = None, hist_counts: Optional[Tensor] = None,
+                            cu_hist: Optional[Tensor] = None, penalties: Optional[Tensor] = None,
+                            out: Optional[Tensor] = None, cut_out: Optional[Tensor] = None,
+                            u_out: Optional[Tensor] = None) -> Tensor:
+    """`sample_rows` under per-row token constraints, still one launch (include/hydra_hip.h: hx_sample_rows_constrained).
+    bias_ids int32 [bias_total], bias_values fp32 [bias_total], cu_bias int32 [rows + 1]: the rows' (token, bias) tables
+    as a CSR, ids within a row pairwise distinct; a bias is added to the fp32 logit BEFORE the penalties, -inf bans the
+    token.  Word 3 of a row's record is its min_p (`pack_sample_records` with six-element records).  Everything else is
+    `sample_rows`': a row with an empty table and min_p 0 gets its id, cut and u bit for bit."""
+    _lib.require_gpu(logits, sample_params, bias_ids, bias_values, cu_bias, hist_ids, hist_counts, cu_hist, penalties, out,
+                     cut_out, u_out)
+    rows, total, out = _check_sample_arguments("sample_rows_constrained", logits, sample_params, hist_ids, hist_counts, cu_hist,
+                                               penalties, out, cut_out, u_out)
+    bias_total = bias_ids.numel()
+    for name, t, dtype, shape in (("bias_ids", bias_ids, torch.int32, (bias_total,)),
+                                  ("bias_values", bias_values, torch.float32, (bias_total,)),
+                                  ("cu_bias", cu_bias, torch.int32, (rows + 1,))):
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != logits.device:
+            raise _lib.HydraHipError(f"sample_rows_constrained: {name} must be a contiguous {str(dtype)[6:]} tensor of shape "
+                                     f"{list(shape)} on the logits' device")
+    ptr = (lambda t: t.data_ptr()) if total else (lambda t: None)
+    bptr = (lambda t: t.data_ptr()) if bias_total else (lambda t: None)
+    _lib.check(_lib.lib().hx_sample_rows_constrained(
+        out.data_ptr(), cut_out.data_ptr() if cut_out is not None else None, u_out.data_ptr() if u_out is not None else None,
+        logits.data_ptr(), rows, logits.shape[1], logits.stride(0), ptr(hist_ids), ptr(hist_counts), ptr(cu_hist), total,
+        ptr(penalties), bptr(bias_ids), bptr(bias_values), bptr(cu_bias), bias_total, sample_params.data_ptr(),
+        _lib.dtype_code(logits), _lib.current_stream()), "sample_rows_constrained")
+    return out
+
+
+def check_constraints(logit_bias, min_tokens, min_p):
+    """(logit_bias, min_tokens, min_p) checked, or ValueError.  logit_bias: None or a mapping from int token id >= 0 to
+    a finite number in -100 .. 100, at most MAX_LOGIT_BIAS entries (returned as a {int: float} dict, None when empty);
+    min_tokens an integer >= 0; min_p a number in [0, 1].  A bool is no number."""
+    bias = None
+    if logit_bias is not None:
+        if not hasattr(logit_bias, "items"):
+            raise ValueError(f"logit_bias {logit_bias!r} must be a mapping from token id to bias")
+        if len(logit_bias) > MAX_LOGIT_BIAS:
+            raise ValueError(f"logit_bias has {len(logit_bias)} entries, at most {MAX_LOGIT_BIAS} are taken")
+        bias = {}
+        for t, b in logit_bias.items():
+            if isinstance(t, bool) or not isinstance(t, int) or not 0 <= t <= 0x7fffffff:
+                raise ValueError(f"logit_bias: token id {t!r} must be an integer >= 0")
+            if isinstance(b, bool) or not isinstance(b, (int, float)) or not math.isfinite(b) or abs(b) > LOGIT_BIAS_RANGE:
+                raise ValueError(f"logit_bias: the bias {b!r} of token {t} must be a finite number in "
+                                 f"-{LOGIT_BIAS_RANGE:g} .. {LOGIT_BIAS_RANGE:g}")
+            bias[t] = float(b)
+        bias = bias or None
+    if isinstance(min_tokens, bool) or not isinstance(min_tokens, int) or min_tokens < 0:
+        raise ValueError(f"min_tokens {min_tokens!r} must be an integer >= 0")
+    if isinstance(min_p, bool) or not isinstance(min_p, (int, float)) or not 0 <= min_p <= 1:      # (a NaN fails both)
+        raise ValueError(f"min_p {min_p!r} must be a number in [0, 1]")
+    return bias, min_tokens, float(min_p)
+
+
+def is_constrained(sampling_params) -> bool:
+    """True when one of logit_bias, min_tokens, min_p changes what the request may emit: a non-empty logit_bias, min_p > 0
+    on a sampled request (a greedy row ignores it), min_tokens > 0 with an end-of-sequence id to hold back.  False: the
+    request takes exactly the paths it took before these fields existed."""
+    sp = sampling_params
+    return bool(sp.logit_bias) or (sp.min_p > 0 and sp.temperature > 0) or (sp.min_tokens > 0 and bool(sp.eos_token_ids))
+
+
+class TokenConstraints:
+    """A request's constraints on the host.  `ids` / `values`: its static bias table as sorted, pairwise distinct int32 /
+    fp32 arrays; `eos_ids`: its end-of-sequence ids (sorted, distinct); `min_tokens`: while fewer tokens have been
+    generated, every one of them is banned (a bias of -inf)."""
+    __slots__ = ("ids", "values", "eos_ids", "min_tokens", "_held")
+
+    def __init__(self, logit_bias=None, eos_token_ids: Sequence[int] = (), min_tokens: int = 0):
+        items = sorted((logit_bias or {}).items())
+        self.ids = np.asarray([t for t, _ in items], dtype=np.int32)
+        self.values = np.asarray([b for _, b in items], dtype=np.float32)
+        self.eos_ids = sorted(set(int(t) for t in eos_token_ids))
+        self.min_tokens = min_tokens
+        self._held = None         # the table with the bans merged in, built on first use
+
+    def step_entries(self, n_generated: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(ids, values) of the row for the step that generates token number n_generated (0: the first).  While
+        n_generated < min_tokens the ban of an end-of-sequence id REPLACES a finite bias on the same id: ids stay
+        distinct (and sorted)."""
+        if n_generated >= self.min_tokens or not self.eos_ids:
+            return self.ids, self.values
+        if self._held is None:
+            table = dict(zip(self.ids.tolist(), self.values.tolist()))
+            table.update((t, -math.inf) for t in self.eos_ids)
+            items = sorted(table.items())
+            self._held = (np.asarray([t for t, _ in items], dtype=np.int32),
+                          np.asarray([b for _, b in items], dtype=np.float32))
+        return self._held
+
+
+class ConstrainedStep:
+    """A constrained step's packed tables: SampleStep's buffer with [cu_bias (rows + 1) | bias_ids (bias_total) |
+    bias_values (bias_total, fp32 bits)] appended — `views` cuts it (on the host or on the device) into
+    sample_rows_constrained's eight table arguments."""
+    __slots__ = ("buffer", "rows", "total", "bias_total")
+
+    def __init__(self, buffer: np.ndarray, rows: int, total: int, bias_total: int):
+        self.buffer, self.rows, self.total, self.bias_total = buffer, rows, total, bias_total
+
+    def views(self, t: Optional[Tensor] = None):
+        """(sample_params, bias_ids, bias_values, cu_bias, hist_ids, hist_counts, cu_hist, penalties) inside `t`, a tensor
+        holding the buffer (default: a host copy)."""
+        if t is None:
+            t = torch.from_numpy(self.buffer)
+        c = (SAMPLE_RECORD_WORDS + 4) * self.rows + 1 + 2 * self.total           # where SampleStep's layout ends
+        d = c + self.rows + 1
+        records, hist_ids, hist_counts, cu_hist, penalties = SampleStep(None, self.rows, self.total).views(t[:c])
+        return (records, t[d:d + self.bias_total], t[d + self.bias_total:d + 2 * self.bias_total].view(torch.float32),
+                t[c:d], hist_ids, hist_counts, cu_hist, penalties)
+
+    def to_device(self, device):
+        """The eight arguments on `device`: the buffer goes through pinned memory in ONE host-to-device copy."""
+        host = torch.from_numpy(self.buffer)
+        if torch.device(device).type == "cuda":
+            host = host.pin_memory()
+        return self.views(host.to(device, non_blocking=True))
+
+
+def pack_constrained_step(entries) -> ConstrainedStep:
+    """entries: one (PenaltyHistory or None, (frequency, presence, repetition), record, bias) per logits row, in row
+    order — record: (temperature, top_p, top_k, seed, offset[, min_p]); bias: None or the (ids, values) arrays of
+    `TokenConstraints.step_entries`."""
+    rows = len(entries)
+    step = pack_sample_step([(h, p, rec) for h, p, rec, _ in entries])
+    lens = [len(b[0]) if b is not None else 0 for _, _, _, b in entries]
+    bias_total = sum(lens)
+    c = step.buffer.size
+    buf = np.empty(c + rows + 1 + 2 * bias_total, dtype=np.int32)
+    buf[:c] = step.buffer
+    buf[c] = 0
+    np.cumsum(lens, out=buf[c + 1:c + rows + 1])
+    at = c + rows + 1
+    for (_, _, _, b), n in zip(entries, lens):
+        if n:
+            buf[at:at + n] = np.asarray(b[0], dtype=np.int32)
+            buf[at + bias_total:at + bias_total + n] = np.asarray(b[1], dtype=np.float32).view(np.int32)
+            at += n
+    return ConstrainedStep(buf, rows, step.total, bias_total)

@@ -319,6 +319,32 @@ int hx_penalized_argmax_rows(int64_t* ids, float* scores_out, const void* logits
 int hx_sample_rows(int64_t* ids, float* cut_out, float* u_out, const void* logits, int64_t rows, int64_t n, int64_t ld,
                    const int32_t* hist_ids, const int32_t* hist_counts, const int32_t* cu_hist, int64_t total,
                    const float* penalties, const void* sample_params, int dtype, hx_stream stream);
+/* hx_sample_rows_constrained: hx_sample_rows with a per-row logit bias table and a min_p cut, still one launch and one
+ * read of the logits (extension; added WITHOUT raising HX_ABI_VERSION: nothing that existed changed).  Everything
+ * hx_sample_rows documents holds word for word, with two additions.
+ * The bias table is a CSR like the history: row r owns (bias_ids[j], bias_values[j]) for cu_bias[r] <= j < cu_bias[r + 1]
+ * (cu_bias int32 [rows + 1], its values are held inside [0, bias_total] by the kernel; bias_values fp32), the ids of a
+ * row pairwise distinct.  For a bias entry (t, b) of row r, after the row is staged as fp32 and BEFORE the penalties:
+ *     x_t = (float)logits[r, t] + b          one fp32 addition
+ * and the penalised value s_t of a history entry, with everything downstream, is computed from that x_t (a token may be
+ * in both tables).  b = -inf bans the token: its value stays -inf through the penalties (r > 0) and it is in no kept
+ * set.  An entry with t < 0 or t >= n is ignored: nothing is read or written for it.  A token that appears twice in one
+ * row's table breaks the contract: the row uses one of the sums, nothing is read or written out of bounds.  A row whose
+ * every element is banned has a largest z that is not finite: hx_sample_rows' degenerate row (the greedy id — index 0 —
+ * and cut NaN).  bias_total == 0 is legal: bias_ids, bias_values and cu_bias may then be NULL.
+ * min_p is word [3] of the row's record, as fp32 (hx_sample_rows keeps ignoring that word).  Off when not > 0 (a NaN
+ * included); ignored on greedy and degenerate rows; a value above 1 acts as 1.  With m = max z and e_i = expf(z_i - m):
+ *     M = {i : e_i >= min_p},   v_M = min z over M,   v_K' = max(v_K, v_M)
+ * and top-p and the draw use v_K' wherever hx_sample_rows uses v_K: Z_K is the sum of e over {z >= v_K'}, v* >= v_K', and
+ * with top_p >= 1, v* = v_K'.  The kept set is a threshold set on z: tied values stand or fall together.
+ * A greedy row (T == 0) rides through: bias, then penalties, then the id in hx_argmax_rows' order.
+ * Errors: hx_sample_rows' rules; bias_total < 0 or > 0x7fffffff: HX_ERR_SHAPE; bias_ids, bias_values or cu_bias NULL
+ * with bias_total > 0: HX_ERR_NULL — nothing is launched. */
+int hx_sample_rows_constrained(int64_t* ids, float* cut_out, float* u_out, const void* logits, int64_t rows, int64_t n,
+                               int64_t ld, const int32_t* hist_ids, const int32_t* hist_counts, const int32_t* cu_hist,
+                               int64_t total, const float* penalties, const int32_t* bias_ids, const float* bias_values,
+                               const int32_t* cu_bias, int64_t bias_total, const void* sample_params, int dtype,
+                               hx_stream stream);
 /* The same product for M <= 32 with the activations held in REGISTERS (csrc/gemm_xreg.hip): a
  * workgroup spans the whole K of its split, so K <= 4096 needs ONE slab (no K split) and K = 11008
  * three instead of eleven — the fp32 slab traffic of a decode layer drops from 25 MB to 6.5 MB.
