@@ -166,6 +166,25 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// The order every row-wise pick follows (argmax, penalised argmax, a greedy sampling row, the logprob ids and top-K):
+// "a before b" is torch.argmax's rule — a NaN first, then the larger value, then the lower index.  A total order, so
+// the first element is the same whatever the reduction order.
+__device__ __forceinline__ bool arg_better(float a, int ia, float b, int ib) {
+  const bool an = a != a, bn = b != b;
+  if (an != bn) return an;
+  if (!an && a != b) return a > b;
+  return ia < ib;
+}
+
+// A logit under (frequency, presence, repetition) with count c, in the reference's order, every operation rounded to
+// fp32 on its own (contraction off: torch rounds the product before the subtraction; the division is the correctly
+// rounded one), so the value is the reference's bit for bit.
+__device__ __forceinline__ float penalized_value(float x, int32_t c, float f, float p, float r) {
+#pragma clang fp contract(off)
+  float s = x - (float)c * f;
+  s = s - (c > 0 ? p : 0.f);
+  return s < 0.f ? s * r : s / r;
+}
 
 // One decode step's metadata advance for `batch` sequences by ONE 256-thread workgroup (hx_decode_advance, and the
 // advance role of hx_decode_step_head): positions / kv lengths += stride, cu_seqlens_k = their prefix sum, the new

@@ -6,7 +6,7 @@
 // everything after that — the fp32 sum of exponentials and the K selection rounds — reads LDS.  Rows wider than
 // LP_LDS_ELEMS stay in global memory (L2) and run the same code from there.
 //
-// Order.  "a before b" is arg_better of norm_rope_act.hip: a NaN first, then the larger value, then the lower index — a
+// Order.  "a before b" is hx::arg_better: a NaN first, then the larger value, then the lower index — a
 // total order, so the first element is hx_argmax_rows' answer whatever the reduction order, and the top-K list (the
 // first K elements) has one defined answer even in rows full of exact 16-bit ties.
 // Selection.  Each thread owns a fixed subset of the row and keeps its best not-yet-taken element as its candidate.  A
@@ -22,14 +22,6 @@ namespace hx {
 #define LP_MAX_K 20
 #define LP_LDS_ELEMS 65536          // 128 KiB of LDS for the row; wider rows are read from global memory
 #define LP_NONE 0x7fffffff          // index of "no element": loses to every real element
-
-// (the rule of arg_better, norm_rope_act.hip)
-__device__ __forceinline__ bool lp_before(float a, int ia, float b, int ib) {
-  const bool an = a != a, bn = b != b;
-  if (an != bn) return an;
-  if (!an && a != b) return a > b;
-  return ia < ib;
-}
 
 // f(value, index) for every element this thread owns.  vec: the row is read in 16-byte pieces, thread t owns the pieces
 // t, t + 1024, ... and the element nvec * 8 + t of the n % 8 tail; otherwise it owns the elements t, t + 1024, ...
@@ -55,7 +47,7 @@ __device__ __forceinline__ void lp_candidate(const u16* src, int n, bool vec, fl
   float bv = -INFINITY;
   int bi = LP_NONE;
   lp_for_own<T>(src, n, vec, [&](float v, int i) {
-    if (lp_before(wv, wi, v, i) && lp_before(v, i, bv, bi)) { bv = v; bi = i; }
+    if (arg_better(wv, wi, v, i) && arg_better(v, i, bv, bi)) { bv = v; bi = i; }
   });
   cv = bv;
   ci = bi;
@@ -72,7 +64,7 @@ __device__ __forceinline__ void lp_candidate_of(const u16* src, int n, bool vec,
   int bi = LP_NONE;
   auto take = [&](int i) {
     const float v = T::to_float(src[i]);
-    if (lp_before(wv, wi, v, i) && lp_before(v, i, bv, bi)) { bv = v; bi = i; }
+    if (arg_better(wv, wi, v, i) && arg_better(v, i, bv, bi)) { bv = v; bi = i; }
   };
   if (vec) {
     const int nvec = n >> 3;
@@ -85,7 +77,7 @@ __device__ __forceinline__ void lp_candidate_of(const u16* src, int n, bool vec,
   for (int off = 32; off > 0; off >>= 1) {
     const float ov = __shfl_xor(bv, off, 64);
     const int oi = __shfl_xor(bi, off, 64);
-    if (lp_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    if (arg_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
   }
   cv = bv;
   ci = bi;
@@ -98,7 +90,7 @@ __device__ __forceinline__ void lp_block_first(float& v, int& i, float* part_v, 
   for (int off = 32; off > 0; off >>= 1) {
     const float ov = __shfl_xor(v, off, 64);
     const int oi = __shfl_xor(i, off, 64);
-    if (lp_before(ov, oi, v, i)) { v = ov; i = oi; }
+    if (arg_better(ov, oi, v, i)) { v = ov; i = oi; }
   }
   if ((threadIdx.x & 63) == 0) { part_v[threadIdx.x >> 6] = v; part_i[threadIdx.x >> 6] = i; }
   __syncthreads();
@@ -108,7 +100,7 @@ __device__ __forceinline__ void lp_block_first(float& v, int& i, float* part_v, 
   for (int k = 1; k < LP_THREADS / 64; ++k) {
     const float ov = part_v[k];
     const int oi = part_i[k];
-    if (lp_before(ov, oi, v, i)) { v = ov; i = oi; }
+    if (arg_better(ov, oi, v, i)) { v = ov; i = oi; }
   }
 }
 
@@ -293,7 +285,7 @@ __global__ __launch_bounds__(LP_THREADS) void token_logprob_rows_kernel(float* _
     m = -INFINITY;
     auto take = [&](float v, int i) {
       tlp_take(m, s, v);
-      before += lp_before(v, i, zt, t) ? 1 : 0;
+      before += arg_better(v, i, zt, t) ? 1 : 0;
     };
     if (!LDS && vec) {
       // from global memory: four independent 16-byte loads per thread in flight, as in the staging loop (which
@@ -350,7 +342,7 @@ __global__ __launch_bounds__(LP_THREADS) void token_logprob_rows_kernel(float* _
     const float best = m;
     lp_for_own<T>(src, n, vec, [&](float v, int i) {
       s += expf(v - best);
-      before += lp_before(v, i, zt, t) ? 1 : 0;
+      before += arg_better(v, i, zt, t) ? 1 : 0;
     });
     s = wave_sum(s);
 #pragma unroll

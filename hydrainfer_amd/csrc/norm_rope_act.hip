@@ -393,14 +393,7 @@ __global__ __launch_bounds__(256) void decode_step_head_kernel(const StepHeadPar
 
 // argmax over each row of logits [rows, n] (row stride ld): the greedy sampler
 // (hydrainfer/model/llama.py:99-104, torch.argmax).  torch's rule: the largest value, NaN counts as
-// larger than everything, ties go to the smallest index.
-__device__ __forceinline__ bool arg_better(float a, int ia, float b, int ib) {
-  const bool an = a != a, bn = b != b;
-  if (an != bn) return an;
-  if (!an && a != b) return a > b;
-  return ia < ib;
-}
-
+// larger than everything, ties go to the smallest index (hx::arg_better).
 template <typename T>
 __global__ __launch_bounds__(1024) void argmax_rows_kernel(int64_t* __restrict__ out,
                                                            const typename T::storage* __restrict__ logits,

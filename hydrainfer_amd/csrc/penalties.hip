@@ -11,13 +11,12 @@
 // element whose bit is set — the bits of a 16-byte piece are one byte of the bitmap, so an untouched piece costs one LDS
 // read more than the plain scan.  A workgroup reduction over the threads' candidates ends the row.
 //
-// Order: arg_better of norm_rope_act.hip (a NaN first, then the larger value, then the lower index) — a total order, so
+// Order: hx::arg_better (a NaN first, then the larger value, then the lower index) — a total order, so
 // a row with an empty history gives hx_argmax_rows' answer bit for bit, whatever the reduction order.  A row with an
 // empty history touches no LDS bitmap at all.
 //
-// Arithmetic: x - float(c) * f ; - (c > 0 ? p : 0) ; (s < 0) ? s * r : s / r — each operation rounded to fp32 on its own
-// (contraction off: torch rounds the product before the subtraction; the division is the correctly rounded one), so the
-// values are the reference's bit for bit.
+// Arithmetic: hx::penalized_value — x - float(c) * f ; - (c > 0 ? p : 0) ; (s < 0) ? s * r : s / r, the reference's
+// values bit for bit.
 #include <math.h>
 
 #include "hx_common.h"
@@ -26,21 +25,6 @@ namespace hx {
 
 #define PEN_THREADS 1024
 #define PEN_MAX_N (1 << 18)         // the widest row: a 32 KiB bitmap, the static LDS limit of a launch without attributes
-
-// (the rule of arg_better, norm_rope_act.hip)
-__device__ __forceinline__ bool pen_before(float a, int ia, float b, int ib) {
-  const bool an = a != a, bn = b != b;
-  if (an != bn) return an;
-  if (!an && a != b) return a > b;
-  return ia < ib;
-}
-
-__device__ __forceinline__ float penalized_value(float x, int32_t c, float f, float p, float r) {
-#pragma clang fp contract(off)
-  float s = x - (float)c * f;
-  s = s - (c > 0 ? p : 0.f);
-  return s < 0.f ? s * r : s / r;
-}
 
 template <typename T>
 __global__ __launch_bounds__(PEN_THREADS) void penalized_argmax_rows_kernel(
@@ -71,7 +55,7 @@ __global__ __launch_bounds__(PEN_THREADS) void penalized_argmax_rows_kernel(
       if (t >= 0 && t < n) {
         atomicOr(&bitmap[t >> 5], 1u << (t & 31));
         s = penalized_value(T::to_float(p[t]), hist_counts[j], f, pp, r);
-        if (pen_before(s, t, best, bi)) { best = s; bi = t; }
+        if (arg_better(s, t, best, bi)) { best = s; bi = t; }
       }
       if (scores_out) scores_out[j] = s;
     }
@@ -95,7 +79,7 @@ __global__ __launch_bounds__(PEN_THREADS) void penalized_argmax_rows_kernel(
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
             const float x = T::to_float(v[u][e]);
-            if (!((taken >> e) & 1u) && pen_before(x, i * 8 + e, best, bi)) { best = x; bi = i * 8 + e; }
+            if (!((taken >> e) & 1u) && arg_better(x, i * 8 + e, best, bi)) { best = x; bi = i * 8 + e; }
           }
         }
       }
@@ -103,26 +87,26 @@ __global__ __launch_bounds__(PEN_THREADS) void penalized_argmax_rows_kernel(
     for (int i = nvec * 8 + threadIdx.x; i < n; i += PEN_THREADS) {
       const float x = T::to_float(p[i]);
       const bool taken = masked && ((bitmap[i >> 5] >> (i & 31)) & 1u);
-      if (!taken && pen_before(x, i, best, bi)) { best = x; bi = i; }
+      if (!taken && arg_better(x, i, best, bi)) { best = x; bi = i; }
     }
   } else {
     for (int i = threadIdx.x; i < n; i += PEN_THREADS) {
       const float x = T::to_float(p[i]);
       const bool taken = masked && ((bitmap[i >> 5] >> (i & 31)) & 1u);
-      if (!taken && pen_before(x, i, best, bi)) { best = x; bi = i; }
+      if (!taken && arg_better(x, i, best, bi)) { best = x; bi = i; }
     }
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     const float ov = __shfl_xor(best, off, 64);
     const int oi = __shfl_xor(bi, off, 64);
-    if (pen_before(ov, oi, best, bi)) { best = ov; bi = oi; }
+    if (arg_better(ov, oi, best, bi)) { best = ov; bi = oi; }
   }
   if ((threadIdx.x & 63) == 0) { s_v[threadIdx.x >> 6] = best; s_i[threadIdx.x >> 6] = bi; }
   __syncthreads();
   if (threadIdx.x == 0) {
     for (int k = 1; k < PEN_THREADS / 64; ++k)
-      if (pen_before(s_v[k], s_i[k], best, bi)) { best = s_v[k]; bi = s_i[k]; }
+      if (arg_better(s_v[k], s_i[k], best, bi)) { best = s_v[k]; bi = s_i[k]; }
     ids[row] = bi;
   }
 }

@@ -3,7 +3,7 @@
 // never makes (its models end in torch.argmax), in one launch behind the logits.
 //
 // One workgroup of 1024 threads per row.  The row is read from HBM once, as fp32 into LDS; a row's history entries are
-// penalised there in place, one per thread (penalized_value of penalties.hip, so a T = 0 row gives
+// penalised there in place, one per thread (hx::penalized_value, so a T = 0 row gives
 // hx_penalized_argmax_rows' id bit for bit).  Thread t then OWNS the contiguous elements t * chunk .. t * chunk + chunk - 1
 // (chunk = ceil(n / 1024) made odd: the threads' LDS reads fall on different banks) and holds their z = s / T and
 // e = expf(z - m) in registers for the rest of the kernel: up to SMP_CHUNK of each.  Contiguous ownership is what makes
@@ -19,7 +19,7 @@
 // call could then give two tokens.  Measured, 64 rows x 32064: top-k by radix 12 us, by bisection over counts 27 us
 // ("Sampled decoding").  A row with top_k outside 1 .. n - 1 and top_p >= 1 runs neither search.
 //
-// Order of a greedy row: arg_better of norm_rope_act.hip (a NaN first, then the larger value, then the lower index).
+// Order of a greedy row: hx::arg_better (a NaN first, then the larger value, then the lower index).
 //
 // hx_sample_rows_constrained (logit_bias, min_tokens, min_p) is the same body — sampling_body.inc, included into both
 // kernels — with two more steps: a row's (token, bias) entries are added to the staged row ahead of the penalties (1b),
@@ -35,22 +35,6 @@ namespace hx {
 #define SAMPLE_MAX_N HX_SAMPLE_MAX_N                     // 35840: 140 KiB of fp32 in LDS
 static_assert(SAMPLE_MAX_N == SMP_THREADS * SMP_CHUNK, "the widest row is what 1024 threads own");
 #define SMP_WAVES (SMP_THREADS / 64)
-
-// (the rule of arg_better, norm_rope_act.hip)
-__device__ __forceinline__ bool smp_before(float a, int ia, float b, int ib) {
-  const bool an = a != a, bn = b != b;
-  if (an != bn) return an;
-  if (!an && a != b) return a > b;
-  return ia < ib;
-}
-
-// (penalized_value of penalties.hip: the reference's order, every operation rounded to fp32 on its own)
-__device__ __forceinline__ float smp_penalized_value(float x, int32_t c, float f, float p, float r) {
-#pragma clang fp contract(off)
-  float s = x - (float)c * f;
-  s = s - (c > 0 ? p : 0.f);
-  return s < 0.f ? s * r : s / r;
-}
 
 // ascending key of a non-NaN float (-0 and +0 share +0's key) and the value of a key
 __device__ __forceinline__ uint32_t smp_key(float z) {
@@ -119,58 +103,36 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_rows_constrained_kernel(
 
 using namespace hx;
 
+// One workgroup per row; a row wider than 12288 elements needs more dynamic LDS than a launch gets without the attribute.
 template <typename T>
-static int launch_sample_rows(int64_t* ids, float* cut_out, float* u_out, const void* logits, int64_t rows, int64_t n,
-                              int64_t ld, const int32_t* hist_ids, const int32_t* hist_counts, const int32_t* cu_hist,
-                              int64_t total, const float* penalties, const void* sample_params, hipStream_t s) {
+static int launch_sample_rows(bool constrained, int64_t* ids, float* cut_out, float* u_out, const void* logits, int64_t rows,
+                              int64_t n, int64_t ld, const int32_t* hist_ids, const int32_t* hist_counts,
+                              const int32_t* cu_hist, int64_t total, const float* penalties, const int32_t* bias_ids,
+                              const float* bias_values, const int32_t* cu_bias, int64_t bias_total, const void* sample_params,
+                              hipStream_t s) {
   const size_t lds = (size_t)((n + 7) / 8 * 8) * sizeof(float);
   if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)sample_rows_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const void* kernel = constrained ? (const void*)sample_rows_constrained_kernel<T> : (const void*)sample_rows_kernel<T>;
+    hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return hip_rc(e);
   }
-  hx::launcher(sample_rows_kernel<T>, (unsigned)rows, SMP_THREADS, lds, s)(
-      ids, cut_out, u_out, (const u16*)logits, (int32_t)n, ld, hist_ids, hist_counts, cu_hist, (int32_t)total, penalties,
-      (const uint32_t*)sample_params);
+  if (constrained)
+    hx::launcher(sample_rows_constrained_kernel<T>, (unsigned)rows, SMP_THREADS, lds, s)(
+        ids, cut_out, u_out, (const u16*)logits, (int32_t)n, ld, hist_ids, hist_counts, cu_hist, (int32_t)total, penalties,
+        (const uint32_t*)sample_params, bias_ids, bias_values, cu_bias, (int32_t)bias_total);
+  else
+    hx::launcher(sample_rows_kernel<T>, (unsigned)rows, SMP_THREADS, lds, s)(
+        ids, cut_out, u_out, (const u16*)logits, (int32_t)n, ld, hist_ids, hist_counts, cu_hist, (int32_t)total, penalties,
+        (const uint32_t*)sample_params);
   return check_launch();
 }
 
-extern "C" int hx_sample_rows(int64_t* ids, float* cut_out, float* u_out, const void* logits, int64_t rows, int64_t n,
-                              int64_t ld, const int32_t* hist_ids, const int32_t* hist_counts, const int32_t* cu_hist,
-                              int64_t total, const float* penalties, const void* sample_params, int dtype,
-                              hx_stream stream) {
-  if (rows < 1 || n < 1 || ld < n || n > SAMPLE_MAX_N || rows > 0x7fffffff || total < 0 || total > 0x7fffffff) return HX_ERR_SHAPE;
-  if (dtype != HX_F16 && dtype != HX_BF16) return HX_ERR_DTYPE;
-  if (!ids || !logits || !sample_params || (total > 0 && (!hist_ids || !hist_counts || !cu_hist || !penalties))) return HX_ERR_NULL;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == HX_F16)
-    return launch_sample_rows<F16>(ids, cut_out, u_out, logits, rows, n, ld, hist_ids, hist_counts, cu_hist, total, penalties,
-                                   sample_params, s);
-  return launch_sample_rows<BF16>(ids, cut_out, u_out, logits, rows, n, ld, hist_ids, hist_counts, cu_hist, total, penalties,
-                                  sample_params, s);
-}
-
-template <typename T>
-static int launch_sample_rows_constrained(int64_t* ids, float* cut_out, float* u_out, const void* logits, int64_t rows,
-                                          int64_t n, int64_t ld, const int32_t* hist_ids, const int32_t* hist_counts,
-                                          const int32_t* cu_hist, int64_t total, const float* penalties,
-                                          const int32_t* bias_ids, const float* bias_values, const int32_t* cu_bias,
-                                          int64_t bias_total, const void* sample_params, hipStream_t s) {
-  const size_t lds = (size_t)((n + 7) / 8 * 8) * sizeof(float);
-  if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)sample_rows_constrained_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return hip_rc(e);
-  }
-  hx::launcher(sample_rows_constrained_kernel<T>, (unsigned)rows, SMP_THREADS, lds, s)(
-      ids, cut_out, u_out, (const u16*)logits, (int32_t)n, ld, hist_ids, hist_counts, cu_hist, (int32_t)total, penalties,
-      (const uint32_t*)sample_params, bias_ids, bias_values, cu_bias, (int32_t)bias_total);
-  return check_launch();
-}
-
-extern "C" int hx_sample_rows_constrained(int64_t* ids, float* cut_out, float* u_out, const void* logits, int64_t rows,
-                                          int64_t n, int64_t ld, const int32_t* hist_ids, const int32_t* hist_counts,
-                                          const int32_t* cu_hist, int64_t total, const float* penalties,
-                                          const int32_t* bias_ids, const float* bias_values, const int32_t* cu_bias,
-                                          int64_t bias_total, const void* sample_params, int dtype, hx_stream stream) {
+// Both entries: the argument checks (hx_sample_rows comes with no bias table: bias_total 0), then the launch by dtype.
+static int sample_rows_entry(bool constrained, int64_t* ids, float* cut_out, float* u_out, const void* logits, int64_t rows,
+                             int64_t n, int64_t ld, const int32_t* hist_ids, const int32_t* hist_counts,
+                             const int32_t* cu_hist, int64_t total, const float* penalties, const int32_t* bias_ids,
+                             const float* bias_values, const int32_t* cu_bias, int64_t bias_total, const void* sample_params,
+                             int dtype, hx_stream stream) {
   if (rows < 1 || n < 1 || ld < n || n > SAMPLE_MAX_N || rows > 0x7fffffff || total < 0 || total > 0x7fffffff ||
       bias_total < 0 || bias_total > 0x7fffffff)
     return HX_ERR_SHAPE;
@@ -178,10 +140,24 @@ extern "C" int hx_sample_rows_constrained(int64_t* ids, float* cut_out, float* u
   if (!ids || !logits || !sample_params || (total > 0 && (!hist_ids || !hist_counts || !cu_hist || !penalties)) ||
       (bias_total > 0 && (!bias_ids || !bias_values || !cu_bias)))
     return HX_ERR_NULL;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == HX_F16)
-    return launch_sample_rows_constrained<F16>(ids, cut_out, u_out, logits, rows, n, ld, hist_ids, hist_counts, cu_hist, total,
-                                               penalties, bias_ids, bias_values, cu_bias, bias_total, sample_params, s);
-  return launch_sample_rows_constrained<BF16>(ids, cut_out, u_out, logits, rows, n, ld, hist_ids, hist_counts, cu_hist, total,
-                                              penalties, bias_ids, bias_values, cu_bias, bias_total, sample_params, s);
+  return (dtype == HX_F16 ? launch_sample_rows<F16> : launch_sample_rows<BF16>)(
+      constrained, ids, cut_out, u_out, logits, rows, n, ld, hist_ids, hist_counts, cu_hist, total, penalties, bias_ids,
+      bias_values, cu_bias, bias_total, sample_params, (hipStream_t)stream);
+}
+
+extern "C" int hx_sample_rows(int64_t* ids, float* cut_out, float* u_out, const void* logits, int64_t rows, int64_t n,
+                              int64_t ld, const int32_t* hist_ids, const int32_t* hist_counts, const int32_t* cu_hist,
+                              int64_t total, const float* penalties, const void* sample_params, int dtype,
+                              hx_stream stream) {
+  return sample_rows_entry(false, ids, cut_out, u_out, logits, rows, n, ld, hist_ids, hist_counts, cu_hist, total, penalties,
+                           nullptr, nullptr, nullptr, 0, sample_params, dtype, stream);
+}
+
+extern "C" int hx_sample_rows_constrained(int64_t* ids, float* cut_out, float* u_out, const void* logits, int64_t rows,
+                                          int64_t n, int64_t ld, const int32_t* hist_ids, const int32_t* hist_counts,
+                                          const int32_t* cu_hist, int64_t total, const float* penalties,
+                                          const int32_t* bias_ids, const float* bias_values, const int32_t* cu_bias,
+                                          int64_t bias_total, const void* sample_params, int dtype, hx_stream stream) {
+  return sample_rows_entry(true, ids, cut_out, u_out, logits, rows, n, ld, hist_ids, hist_counts, cu_hist, total, penalties,
+                           bias_ids, bias_values, cu_bias, bias_total, sample_params, dtype, stream);
 }

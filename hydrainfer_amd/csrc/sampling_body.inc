@@ -68,7 +68,7 @@
       const float f = penalties[row * 3], pp = penalties[row * 3 + 1], r = penalties[row * 3 + 2];
       for (int32_t j = h0 + tid; j < h1; j += SMP_THREADS) {
         const int32_t t = hist_ids[j];
-        if (t >= 0 && t < n) zs[t] = smp_penalized_value(zs[t], hist_counts[j], f, pp, r);   // (ids pairwise distinct)
+        if (t >= 0 && t < n) zs[t] = penalized_value(zs[t], hist_counts[j], f, pp, r);   // (ids pairwise distinct)
       }
       __syncthreads();
     }
@@ -85,13 +85,13 @@
   for (int j = 0; j < SMP_CHUNK; ++j) {
     const bool own = j < chunk && base + j < n;
     zr[j] = own ? zs[own ? base + j : 0] : __builtin_nanf("");
-    if (own && smp_before(zr[j], base + j, best, bi)) { best = zr[j]; bi = base + j; }
+    if (own && arg_better(zr[j], base + j, best, bi)) { best = zr[j]; bi = base + j; }
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     const float ov = __shfl_xor(best, off, 64);
     const int oi = __shfl_xor(bi, off, 64);
-    if (smp_before(ov, oi, best, bi)) { best = ov; bi = oi; }
+    if (arg_better(ov, oi, best, bi)) { best = ov; bi = oi; }
   }
   if (lane == 0) { part_f[0][wave] = best; part_i[0][wave] = bi; }
   if (tid == 0) { s_first = SMP_THREADS; s_last = -1; }
@@ -100,7 +100,7 @@
   bi = part_i[0][0];
 #pragma unroll
   for (int k = 1; k < SMP_WAVES; ++k)
-    if (smp_before(part_f[0][k], part_i[0][k], best, bi)) { best = part_f[0][k]; bi = part_i[0][k]; }
+    if (arg_better(part_f[0][k], part_i[0][k], best, bi)) { best = part_f[0][k]; bi = part_i[0][k]; }
 
   // z = s / T, one correctly rounded division; s -> s / T keeps the order, so the largest z is that of the greedy id
   const float m = best / temperature;

@@ -21,8 +21,43 @@ from hydrainfer_amd.engine.isa import Fill, TextFill
 from hydrainfer_amd.engine.parameters_builder import LanguageModelParametersBuilder
 from hydrainfer_amd.engine.rcb import BatchRequest, PromptTokenLogprob, TokenLogprob
 from hydrainfer_amd.model.llama import LanguageModelParameters
+# (the packers and kernels are reached by name: SAMPLING_MODES)
 from hydrainfer_amd.sampling import (GREEDY_RECORD, NO_PENALTIES, pack_constrained_step, pack_penalty_step, pack_sample_step,
                                      penalized_argmax_rows, sample_rows, sample_rows_constrained)
+
+
+# What the table-driven modes of the eager sampling step (BatchFillExecutor._sample) differ in: how many elements of a
+# row's (history, penalties, record, bias) entry the packer takes, the packer, the language model's entry point (logits
+# and launch in one call) and the kernel for logits that are already there.  NAMES, looked up when the step runs: tests
+# patch executor.<kernel>, and a stand-in for the language model implements only the entry points its test needs.
+SAMPLING_MODES = {
+    "constrained": (4, "pack_constrained_step", "forward_constrained", "sample_rows_constrained"),
+    "drawn": (3, "pack_sample_step", "forward_sampled", "sample_rows"),
+    "penalised": (2, "pack_penalty_step", "forward_penalized", "penalized_argmax_rows"),
+}
+
+
+def sampling_rows(batch):
+    """The (rcb, inst) pairs of a fill batch that sample a token, in the order of the step's sampled rows."""
+    return [(rcb, inst) for rcb, inst in batch if isinstance(inst, Fill) and inst.sample]
+
+
+def step_mode(rows):
+    """rows: the sampling (rcb, inst) pairs of an eager step -> (mode, top_k).  mode: the first that some request asks
+    for of "constrained" (logit_bias, min_tokens, min_p), "drawn" (temperature > 0), "penalised", "logprobs", else
+    "plain"; each of the first three serves the requests of the modes after it in the same launch.  top_k: the largest
+    top_logprobs among the requests that ask for log-probabilities and deliver a token this step (a chunk head's sample
+    is discarded), None when there is none."""
+    asking = [rcb.sampling_params.top_logprobs for rcb, inst in rows if rcb.sampling_params.logprobs and not inst.is_chunked]
+    if any(rcb.token_constraints is not None for rcb, _ in rows):
+        mode = "constrained"
+    elif any(rcb.sampling_params.temperature > 0 for rcb, _ in rows):
+        mode = "drawn"
+    elif any(rcb.penalty_history is not None for rcb, _ in rows):
+        mode = "penalised"
+    else:
+        mode = "logprobs" if asking else "plain"
+    return mode, max(asking) if asking else None
 
 
 class PendingToken:
@@ -275,12 +310,8 @@ class BatchFillExecutor:
     def _deliver(self, batch: BatchRequest, sampled: List[int], scores=None) -> None:
         """scores: None, or the step's (logprobs, top_ids, top_logprobs) as host lists, one entry per sampled row."""
         now = time.perf_counter()
-        i = 0
-        for rcb, inst in batch:
-            if not isinstance(inst, Fill) or not inst.sample:
-                continue
+        for i, (rcb, inst) in enumerate(sampling_rows(batch)):
             token = sampled[i]
-            i += 1
             if rcb.eos_hit:
                 continue                       # already ended by a token that was read back late
             entry = None
@@ -294,7 +325,7 @@ class BatchFillExecutor:
                     rcb.penalty_history.append(token)           # generated tokens only: a chunk head's sample never gets here
                 if scores is not None and rcb.sampling_params.logprobs:
                     k = rcb.sampling_params.top_logprobs        # this request's own count out of the batch's largest
-                    entry = TokenLogprob(token, scores[0][i - 1], list(zip(scores[1][i - 1][:k], scores[2][i - 1][:k])))
+                    entry = TokenLogprob(token, scores[0][i], list(zip(scores[1][i][:k], scores[2][i][:k])))
                     rcb.output_logprobs.append(entry)
             if inst.sample_dst is not None:
                 inst.sample_dst.token_ids = [token]
@@ -309,7 +340,7 @@ class BatchFillExecutor:
     def _sample_with_logprobs(self, inputs, params, top_k: int, logits=None):
         """The eager step of a batch in which some request asked for log-probabilities: the same logits, ids by the same
         rule, and the scores beside them — one launch (hx_logprob_rows), one packed buffer, ONE device-to-host copy.
-        logits (here and in the two methods below): None, or the ready logits of the step's sampling rows, one row per
+        logits (here and in _sample): None, or the ready logits of the step's sampling rows, one row per
         entry of inputs.selected_token_ids (a step that also scores prompts: _execute_scoring) — the forward is not run
         again, the same kernels follow."""
         if logits is None:
@@ -326,118 +357,43 @@ class BatchFillExecutor:
             sampled, scores = [sampled[j] for j in sel], tuple([col[j] for j in sel] for col in scores)
         return sampled, scores
 
-    def _sample_penalized(self, batch: BatchRequest, inputs, params, top_k: Optional[int], logits=None):
-        """The eager step of a batch in which some request is under frequency / presence / repetition penalties: the same
-        logits, then hx_penalized_argmax_rows in place of the argmax — ONE launch for the whole batch; the rows of
-        unpenalised requests ride along with an empty history and (0, 0, 1) and get the id they would have got.  The
-        step's (token, count) tables reach the device as one pinned buffer in one copy.  top_k: None, or the largest
-        top_logprobs of the batch's OTHER requests that asked for log-probabilities (no request has both): their scores
-        come from hx_logprob_rows over the same logits."""
-        sel, decode = inputs.selected_token_ids, inputs.all_sequences_decode and logits is None
-        n_rows = inputs.input_ids.shape[0] if decode else len(sel)        # the rows of the logits
-        entries = [(None, NO_PENALTIES)] * n_rows
-        i = 0
-        for rcb, inst in batch:
-            if not isinstance(inst, Fill) or not inst.sample:
-                continue
-            if rcb.penalty_history is not None:
-                sp = rcb.sampling_params
-                entries[sel[i] if decode else i] = (rcb.penalty_history,
-                                                    (sp.frequency_penalty, sp.presence_penalty, sp.repetition_penalty))
-            i += 1
-        tables = pack_penalty_step(entries).to_device(self.device)
-        lm, scores = self.language_model, None
-        if top_k is None and logits is None:
-            sampled = lm.forward_penalized(inputs.input_ids, inputs.image_features, inputs.position_ids, params,
-                                           *tables).tolist()                       # the step's only device sync
-        elif top_k is None:
-            sampled = penalized_argmax_rows(logits, *tables).tolist()
-        else:
-            if logits is None:
-                logits = lm.forward_logits(inputs.input_ids, inputs.image_features, inputs.position_ids, params)
-            packed = logprob_rows_packed(logprob_rows(logits, top_k)[0], top_k)
-            sampled = penalized_argmax_rows(logits, *tables).tolist()
-            _, lp, top_ids, top_lp = logprob_rows_views(packed.cpu(), n_rows, top_k)
-            scores = (lp.tolist(), top_ids.tolist(), top_lp.tolist())
-        if decode and n_rows != len(sel):
-            sampled = [sampled[j] for j in sel]
-            scores = scores and tuple([col[j] for j in sel] for col in scores)
-        return sampled, scores
-
-    def _sample_drawn(self, batch: BatchRequest, inputs, params, top_k: Optional[int], logits=None):
-        """The eager step of a batch in which some request is SAMPLED (temperature > 0): the same logits, then
-        hx_sample_rows — ONE launch for the whole batch.  Greedy requests ride along with temperature 0 and get the id
-        they would have got, penalised ones (greedy or sampled) ride along with their history.  A request's offset is the
-        number of tokens it has generated so far (the eager path has every token on the host).  The step's sampling
-        records and (token, count) tables reach the device as one pinned buffer in one copy.  top_k: as in
-        _sample_penalized, for the batch's OTHER requests that asked for log-probabilities."""
-        sel, decode = inputs.selected_token_ids, inputs.all_sequences_decode and logits is None
-        n_rows = inputs.input_ids.shape[0] if decode else len(sel)        # the rows of the logits
-        entries = [(None, NO_PENALTIES, GREEDY_RECORD)] * n_rows
-        i = 0
-        for rcb, inst in batch:
-            if not isinstance(inst, Fill) or not inst.sample:
-                continue
-            sp = rcb.sampling_params
-            record = (sp.temperature, sp.top_p, sp.top_k, sp.seed, len(rcb.output_token_ids)) if sp.temperature > 0 \
-                else GREEDY_RECORD
-            entries[sel[i] if decode else i] = (rcb.penalty_history,
-                                                (sp.frequency_penalty, sp.presence_penalty, sp.repetition_penalty), record)
-            i += 1
-        tables = pack_sample_step(entries).to_device(self.device)
-        lm, scores = self.language_model, None
-        if top_k is None and logits is None:
-            sampled = lm.forward_sampled(inputs.input_ids, inputs.image_features, inputs.position_ids, params,
-                                         *tables).tolist()                         # the step's only device sync
-        elif top_k is None:
-            sampled = sample_rows(logits, *tables).tolist()
-        else:
-            if logits is None:
-                logits = lm.forward_logits(inputs.input_ids, inputs.image_features, inputs.position_ids, params)
-            packed = logprob_rows_packed(logprob_rows(logits, top_k)[0], top_k)
-            sampled = sample_rows(logits, *tables).tolist()
-            _, lp, top_ids, top_lp = logprob_rows_views(packed.cpu(), n_rows, top_k)
-            scores = (lp.tolist(), top_ids.tolist(), top_lp.tolist())
-        if decode and n_rows != len(sel):
-            sampled = [sampled[j] for j in sel]
-            scores = scores and tuple([col[j] for j in sel] for col in scores)
-        return sampled, scores
-
-    def _sample_constrained(self, batch: BatchRequest, inputs, params, top_k: Optional[int], logits=None):
-        """The eager step of a batch in which some request is CONSTRAINED (logit_bias, min_tokens, min_p): the same
-        logits, then hx_sample_rows_constrained — ONE launch for the whole batch, _sample_drawn with each row's bias table
+    def _sample(self, mode: str, batch: BatchRequest, inputs, params, top_k: Optional[int], logits=None):
+        """The eager step of a batch that does not end in the plain argmax -> (sampled, scores).  Mode "logprobs" is
+        _sample_with_logprobs.  The others (SAMPLING_MODES) are the same logits, then ONE launch for the whole batch in
+        place of the argmax: a request the launch is not there for rides along with an empty history and (0, 0, 1),
+        temperature 0, an empty bias table and min_p 0, and gets the id it would have got.  A request's offset is the
+        number of tokens it has generated so far (the eager path has every token on the host), its bias table is the one
         for THIS step (TokenConstraints.step_entries: the end-of-sequence ids banned while the request has generated
-        fewer than min_tokens) and its min_p in the record.  Unconstrained requests ride along with an empty table and
-        min_p 0 and get the id they would have got; a greedy constrained request rides with temperature 0.  Records,
-        (token, count) tables and bias tables reach the device as one pinned buffer in one copy.  top_k: as in
-        _sample_penalized, for the batch's OTHER requests that asked for log-probabilities (raw logits: no request has
-        both)."""
+        fewer than min_tokens).  The step's tables reach the device as one pinned buffer in one copy.  top_k: None, or
+        the largest top_logprobs of the batch's OTHER requests that asked for log-probabilities (no request has both):
+        their scores come from hx_logprob_rows over the same, raw logits."""
+        if mode == "logprobs":
+            return self._sample_with_logprobs(inputs, params, top_k, logits)
+        take, packer, forward, kernel = SAMPLING_MODES[mode]
+        n_record = 6 if take == 4 else 5        # min_p (word 3 of a record) travels with the bias tables only
         sel, decode = inputs.selected_token_ids, inputs.all_sequences_decode and logits is None
         n_rows = inputs.input_ids.shape[0] if decode else len(sel)        # the rows of the logits
-        entries = [(None, NO_PENALTIES, GREEDY_RECORD, None)] * n_rows
-        i = 0
-        for rcb, inst in batch:
-            if not isinstance(inst, Fill) or not inst.sample:
-                continue
+        entries = [(None, NO_PENALTIES, GREEDY_RECORD, None)[:take]] * n_rows
+        for i, (rcb, _) in enumerate(sampling_rows(batch)):
             sp, n_out = rcb.sampling_params, len(rcb.output_token_ids)
-            record = (sp.temperature, sp.top_p, sp.top_k, sp.seed, n_out, sp.min_p) if sp.temperature > 0 else GREEDY_RECORD
+            record = (sp.temperature, sp.top_p, sp.top_k, sp.seed, n_out, sp.min_p)[:n_record] if sp.temperature > 0 \
+                else GREEDY_RECORD
             bias = rcb.token_constraints.step_entries(n_out) if rcb.token_constraints is not None else None
             entries[sel[i] if decode else i] = (rcb.penalty_history,
                                                 (sp.frequency_penalty, sp.presence_penalty, sp.repetition_penalty), record,
-                                                bias)
-            i += 1
-        tables = pack_constrained_step(entries).to_device(self.device)
+                                                bias)[:take]
+        tables = globals()[packer](entries).to_device(self.device)
         lm, scores = self.language_model, None
         if top_k is None and logits is None:
-            sampled = lm.forward_constrained(inputs.input_ids, inputs.image_features, inputs.position_ids, params,
-                                             *tables).tolist()                     # the step's only device sync
-        elif top_k is None:
-            sampled = sample_rows_constrained(logits, *tables).tolist()
+            sampled = getattr(lm, forward)(inputs.input_ids, inputs.image_features, inputs.position_ids, params, *tables)
         else:
             if logits is None:
                 logits = lm.forward_logits(inputs.input_ids, inputs.image_features, inputs.position_ids, params)
-            packed = logprob_rows_packed(logprob_rows(logits, top_k)[0], top_k)
-            sampled = sample_rows_constrained(logits, *tables).tolist()
+            if top_k is not None:
+                packed = logprob_rows_packed(logprob_rows(logits, top_k)[0], top_k)
+            sampled = globals()[kernel](logits, *tables)
+        sampled = sampled.tolist()                      # the step's only device sync beside the scores' copy
+        if top_k is not None:
             _, lp, top_ids, top_lp = logprob_rows_views(packed.cpu(), n_rows, top_k)
             scores = (lp.tolist(), top_ids.tolist(), top_lp.tolist())
         if decode and n_rows != len(sel):
@@ -461,20 +417,11 @@ class BatchFillExecutor:
         sampled = scores = None
         if inputs.selected_token_ids:
             rows = logits.index_select(0, plan.sample_pos_tensor)
-            sampling = [(rcb, inst) for rcb, inst in batch if isinstance(inst, Fill) and inst.sample]
-            asking = [rcb.sampling_params.top_logprobs for rcb, inst in sampling
-                      if rcb.sampling_params.logprobs and not inst.is_chunked]
-            top_k = max(asking) if asking else None
-            if any(rcb.token_constraints is not None for rcb, _ in sampling):
-                sampled, scores = self._sample_constrained(batch, inputs, params, top_k, rows)
-            elif any(rcb.sampling_params.temperature > 0 for rcb, _ in sampling):
-                sampled, scores = self._sample_drawn(batch, inputs, params, top_k, rows)
-            elif any(rcb.penalty_history is not None for rcb, _ in sampling):
-                sampled, scores = self._sample_penalized(batch, inputs, params, top_k, rows)
-            elif asking:
-                sampled, scores = self._sample_with_logprobs(inputs, params, top_k, rows)
-            else:
+            mode, top_k = step_mode(sampling_rows(batch))
+            if mode == "plain":
                 sampled = argmax_rows(rows).tolist()
+            else:
+                sampled, scores = self._sample(mode, batch, inputs, params, top_k, rows)
         lp, ranks, top_ids, top_lp = (t.tolist() for t in token_logprob_rows_views(packed.cpu(), len(plan.rows), k))
         for u, dst in enumerate(plan.dst):
             if dst is not None:
@@ -531,27 +478,15 @@ class BatchFillExecutor:
                 inputs.position_ids, params)
             batch.step()
             return
-        asking = [rcb.sampling_params.top_logprobs for rcb, inst in batch
-                  if rcb.sampling_params.logprobs and isinstance(inst, Fill) and inst.sample and not inst.is_chunked]
-        if any(rcb.token_constraints is not None for rcb, inst in batch if isinstance(inst, Fill) and inst.sample):
-            self._deliver(batch, *self._sample_constrained(batch, inputs, params, max(asking) if asking else None))
-            return
-        if any(rcb.sampling_params.temperature > 0 for rcb, inst in batch if isinstance(inst, Fill) and inst.sample):
-            self._deliver(batch, *self._sample_drawn(batch, inputs, params, max(asking) if asking else None))
-            return
-        if any(rcb.penalty_history is not None for rcb, inst in batch if isinstance(inst, Fill) and inst.sample):
-            self._deliver(batch, *self._sample_penalized(batch, inputs, params, max(asking) if asking else None))
-            return
-        if asking:
-            self._deliver(batch, *self._sample_with_logprobs(inputs, params, max(asking)))
+        mode, top_k = step_mode(sampling_rows(batch))
+        if mode != "plain":
+            self._deliver(batch, *self._sample(mode, batch, inputs, params, top_k))
             return
         sampled = self.language_model.forward(inputs.input_ids, inputs.image_features, inputs.position_ids,
                                               params)
         if inputs.all_sequences_decode and sampled.numel() != len(inputs.selected_token_ids):
             sampled = sampled[inputs.selected_token_ids_tensor]
-        sampled = sampled.tolist()                      # the step's only device sync
-
-        self._deliver(batch, sampled)
+        self._deliver(batch, sampled.tolist())          # the step's only device sync
 
 
 class BatchImageEmbedExecutor:

@@ -116,7 +116,19 @@ class PenaltyHistory:
         return len(self.ids)
 
 
-class PenaltyStep:
+class _PackedStep:
+    """A step's tables as one int32 host `buffer`, which the subclass's `views` cuts into a kernel's arguments."""
+    __slots__ = ()
+
+    def to_device(self, device):
+        """`views` on `device`: the buffer goes through pinned memory in ONE host-to-device copy."""
+        host = torch.from_numpy(self.buffer)
+        if torch.device(device).type == "cuda":
+            host = host.pin_memory()
+        return self.views(host.to(device, non_blocking=True))
+
+
+class PenaltyStep(_PackedStep):
     """A step's packed tables: one int32 host buffer [cu_hist (rows + 1) | penalties (3 rows, fp32 bits) | hist_ids
     (total) | hist_counts (total)] — `views` cuts it (on the host or on the device) into the kernel's four arguments."""
     __slots__ = ("buffer", "rows", "total")
@@ -131,13 +143,6 @@ class PenaltyStep:
         a, b = self.rows + 1, 4 * self.rows + 1
         return (t[b:b + self.total], t[b + self.total:b + 2 * self.total], t[:a],
                 t[a:b].view(torch.float32).view(self.rows, 3))
-
-    def to_device(self, device):
-        """The four arguments on `device`: the buffer goes through pinned memory in ONE host-to-device copy."""
-        host = torch.from_numpy(self.buffer)
-        if torch.device(device).type == "cuda":
-            host = host.pin_memory()
-        return self.views(host.to(device, non_blocking=True))
 
 
 def pack_penalty_step(entries) -> PenaltyStep:
@@ -248,7 +253,7 @@ def pack_sample_records(records, out: Optional[np.ndarray] = None) -> np.ndarray
     return out
 
 
-class SampleStep:
+class SampleStep(_PackedStep):
     """A sampled step's packed tables: one int32 host buffer [records (8 rows) | cu_hist (rows + 1) | penalties (3 rows,
     fp32 bits) | hist_ids (total) | hist_counts (total)] — `views` cuts it (on the host or on the device) into
     sample_rows' five table arguments."""
@@ -266,13 +271,6 @@ class SampleStep:
         a, b = r + self.rows + 1, r + 4 * self.rows + 1
         return (t[:r].view(self.rows, SAMPLE_RECORD_WORDS), t[b:b + self.total], t[b + self.total:b + 2 * self.total],
                 t[r:a], t[a:b].view(torch.float32).view(self.rows, 3))
-
-    def to_device(self, device):
-        """The five arguments on `device`: the buffer goes through pinned memory in ONE host-to-device copy."""
-        host = torch.from_numpy(self.buffer)
-        if torch.device(device).type == "cuda":
-            host = host.pin_memory()
-        return self.views(host.to(device, non_blocking=True))
 
 
 def pack_sample_step(entries) -> SampleStep:
@@ -387,7 +385,7 @@ class TokenConstraints:
         return self._held
 
 
-class ConstrainedStep:
+class ConstrainedStep(_PackedStep):
     """A constrained step's packed tables: SampleStep's buffer with [cu_bias (rows + 1) | bias_ids (bias_total) |
     bias_values (bias_total, fp32 bits)] appended — `views` cuts it (on the host or on the device) into
     sample_rows_constrained's eight table arguments."""
@@ -406,13 +404,6 @@ class ConstrainedStep:
         records, hist_ids, hist_counts, cu_hist, penalties = SampleStep(None, self.rows, self.total).views(t[:c])
         return (records, t[d:d + self.bias_total], t[d + self.bias_total:d + 2 * self.bias_total].view(torch.float32),
                 t[c:d], hist_ids, hist_counts, cu_hist, penalties)
-
-    def to_device(self, device):
-        """The eight arguments on `device`: the buffer goes through pinned memory in ONE host-to-device copy."""
-        host = torch.from_numpy(self.buffer)
-        if torch.device(device).type == "cuda":
-            host = host.pin_memory()
-        return self.views(host.to(device, non_blocking=True))
 
 
 def pack_constrained_step(entries) -> ConstrainedStep:
