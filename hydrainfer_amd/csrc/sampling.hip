@@ -24,6 +24,11 @@
 // hx_sample_rows_constrained (logit_bias, min_tokens, min_p) is the same body — sampling_body.inc, included into both
 // kernels — with two more steps: a row's (token, bias) entries are added to the staged row ahead of the penalties (1b),
 // and min_p raises the top-k cut to the smallest z whose e reaches it, by one more block minimum over the registers (4b).
+//
+// hx_sample_rows_logprobs is the constrained body with a seventh step: when the draw is done a thread still holds its z,
+// the block m, the cut and Z_S, so the log-probability of the chosen token under the distribution it was chosen from is
+// (z - m) - logf(Z_S), and the K most likely alternatives are K block-argmax rounds over the registers — no second read
+// of the row, no second launch.  A greedy row that is scored does not leave early: T' = 1 and S is the whole row.
 #include <math.h>
 
 #include "hx_common.h"
@@ -73,6 +78,13 @@ __device__ __forceinline__ float smp_block_sum(float s, float* part) {
   for (int off = SMP_WAVES / 2; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
   return s;
 }
+
+// what the body names for its scores, in the kernels that give none (SCORED false: no statement that reads them is compiled)
+#define SMP_NO_SCORES                                                                                  \
+  constexpr bool SCORED = false;                                                                       \
+  float* const logprobs = nullptr; int32_t* const top_ids = nullptr; float* const top_logprobs = nullptr; \
+  const int32_t score_k = 0; const int32_t* const want = nullptr;
+
 template <typename T>
 __global__ __launch_bounds__(SMP_THREADS) void sample_rows_kernel(
     int64_t* __restrict__ ids, float* __restrict__ cut_out, float* __restrict__ u_out, const u16* __restrict__ logits,
@@ -80,6 +92,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_rows_kernel(
     const int32_t* __restrict__ cu_hist, int32_t total, const float* __restrict__ penalties,
     const uint32_t* __restrict__ sample_params) {
   constexpr bool CONSTRAINED = false;
+  SMP_NO_SCORES
   const int32_t* const bias_ids = nullptr; const float* const bias_values = nullptr; const int32_t* const cu_bias = nullptr;
   const int32_t bias_total = 0;
 #include "sampling_body.inc"
@@ -96,6 +109,24 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_rows_constrained_kernel(
     const uint32_t* __restrict__ sample_params, const int32_t* __restrict__ bias_ids,
     const float* __restrict__ bias_values, const int32_t* __restrict__ cu_bias, int32_t bias_total) {
   constexpr bool CONSTRAINED = true;
+  SMP_NO_SCORES
+#include "sampling_body.inc"
+}
+
+// hx_sample_rows_logprobs: the constrained body with step 7 — the log-probability of the row's id under the distribution
+// it was chosen from, and the K most likely alternatives of that distribution, out of the z and Z_S the draw has in
+// registers.  SCORED is false in the two kernels above, which keep their device code byte for byte.
+template <typename T>
+__global__ __launch_bounds__(SMP_THREADS) void sample_rows_logprobs_kernel(
+    int64_t* __restrict__ ids, float* __restrict__ cut_out, float* __restrict__ u_out, const u16* __restrict__ logits,
+    int32_t n, int64_t ld, const int32_t* __restrict__ hist_ids, const int32_t* __restrict__ hist_counts,
+    const int32_t* __restrict__ cu_hist, int32_t total, const float* __restrict__ penalties,
+    const uint32_t* __restrict__ sample_params, const int32_t* __restrict__ bias_ids,
+    const float* __restrict__ bias_values, const int32_t* __restrict__ cu_bias, int32_t bias_total,
+    float* __restrict__ logprobs, int32_t* __restrict__ top_ids, float* __restrict__ top_logprobs, int32_t score_k,
+    const int32_t* __restrict__ want) {
+  constexpr bool CONSTRAINED = true;
+  constexpr bool SCORED = true;
 #include "sampling_body.inc"
 }
 
@@ -127,12 +158,31 @@ static int launch_sample_rows(bool constrained, int64_t* ids, float* cut_out, fl
   return check_launch();
 }
 
-// Both entries: the argument checks (hx_sample_rows comes with no bias table: bias_total 0), then the launch by dtype.
-static int sample_rows_entry(bool constrained, int64_t* ids, float* cut_out, float* u_out, const void* logits, int64_t rows,
-                             int64_t n, int64_t ld, const int32_t* hist_ids, const int32_t* hist_counts,
-                             const int32_t* cu_hist, int64_t total, const float* penalties, const int32_t* bias_ids,
-                             const float* bias_values, const int32_t* cu_bias, int64_t bias_total, const void* sample_params,
-                             int dtype, hx_stream stream) {
+template <typename T>
+static int launch_sample_rows_logprobs(int64_t* ids, float* cut_out, float* u_out, const void* logits, int64_t rows, int64_t n,
+                                       int64_t ld, const int32_t* hist_ids, const int32_t* hist_counts, const int32_t* cu_hist,
+                                       int64_t total, const float* penalties, const int32_t* bias_ids,
+                                       const float* bias_values, const int32_t* cu_bias, int64_t bias_total,
+                                       const void* sample_params, float* logprobs, int32_t* top_ids, float* top_logprobs,
+                                       int top_k, const int32_t* want, hipStream_t s) {
+  const size_t lds = (size_t)((n + 7) / 8 * 8) * sizeof(float);
+  if (lds > 48 * 1024) {
+    hipError_t e = hipFuncSetAttribute((const void*)sample_rows_logprobs_kernel<T>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return hip_rc(e);
+  }
+  hx::launcher(sample_rows_logprobs_kernel<T>, (unsigned)rows, SMP_THREADS, lds, s)(
+      ids, cut_out, u_out, (const u16*)logits, (int32_t)n, ld, hist_ids, hist_counts, cu_hist, (int32_t)total, penalties,
+      (const uint32_t*)sample_params, bias_ids, bias_values, cu_bias, (int32_t)bias_total, logprobs, top_ids, top_logprobs,
+      (int32_t)top_k, want);
+  return check_launch();
+}
+
+// hx_sample_rows_constrained's argument checks, which all three entries share
+static int sample_rows_check(const int64_t* ids, const void* logits, int64_t rows, int64_t n, int64_t ld,
+                             const int32_t* hist_ids, const int32_t* hist_counts, const int32_t* cu_hist, int64_t total,
+                             const float* penalties, const int32_t* bias_ids, const float* bias_values,
+                             const int32_t* cu_bias, int64_t bias_total, const void* sample_params, int dtype) {
   if (rows < 1 || n < 1 || ld < n || n > SAMPLE_MAX_N || rows > 0x7fffffff || total < 0 || total > 0x7fffffff ||
       bias_total < 0 || bias_total > 0x7fffffff)
     return HX_ERR_SHAPE;
@@ -140,6 +190,18 @@ static int sample_rows_entry(bool constrained, int64_t* ids, float* cut_out, flo
   if (!ids || !logits || !sample_params || (total > 0 && (!hist_ids || !hist_counts || !cu_hist || !penalties)) ||
       (bias_total > 0 && (!bias_ids || !bias_values || !cu_bias)))
     return HX_ERR_NULL;
+  return HX_OK;
+}
+
+// Both entries: the argument checks (hx_sample_rows comes with no bias table: bias_total 0), then the launch by dtype.
+static int sample_rows_entry(bool constrained, int64_t* ids, float* cut_out, float* u_out, const void* logits, int64_t rows,
+                             int64_t n, int64_t ld, const int32_t* hist_ids, const int32_t* hist_counts,
+                             const int32_t* cu_hist, int64_t total, const float* penalties, const int32_t* bias_ids,
+                             const float* bias_values, const int32_t* cu_bias, int64_t bias_total, const void* sample_params,
+                             int dtype, hx_stream stream) {
+  const int rc = sample_rows_check(ids, logits, rows, n, ld, hist_ids, hist_counts, cu_hist, total, penalties, bias_ids,
+                                   bias_values, cu_bias, bias_total, sample_params, dtype);
+  if (rc != HX_OK) return rc;
   return (dtype == HX_F16 ? launch_sample_rows<F16> : launch_sample_rows<BF16>)(
       constrained, ids, cut_out, u_out, logits, rows, n, ld, hist_ids, hist_counts, cu_hist, total, penalties, bias_ids,
       bias_values, cu_bias, bias_total, sample_params, (hipStream_t)stream);
@@ -160,4 +222,20 @@ extern "C" int hx_sample_rows_constrained(int64_t* ids, float* cut_out, float* u
                                           int64_t bias_total, const void* sample_params, int dtype, hx_stream stream) {
   return sample_rows_entry(true, ids, cut_out, u_out, logits, rows, n, ld, hist_ids, hist_counts, cu_hist, total, penalties,
                            bias_ids, bias_values, cu_bias, bias_total, sample_params, dtype, stream);
+}
+
+extern "C" int hx_sample_rows_logprobs(int64_t* ids, float* cut_out, float* u_out, const void* logits, int64_t rows, int64_t n,
+                                       int64_t ld, const int32_t* hist_ids, const int32_t* hist_counts,
+                                       const int32_t* cu_hist, int64_t total, const float* penalties,
+                                       const int32_t* bias_ids, const float* bias_values, const int32_t* cu_bias,
+                                       int64_t bias_total, const void* sample_params, float* logprobs, int32_t* top_ids,
+                                       float* top_logprobs, int top_k, const int32_t* want, int dtype, hx_stream stream) {
+  if (top_k < 0 || top_k > 20) return HX_ERR_SHAPE;
+  const int rc = sample_rows_check(ids, logits, rows, n, ld, hist_ids, hist_counts, cu_hist, total, penalties, bias_ids,
+                                   bias_values, cu_bias, bias_total, sample_params, dtype);
+  if (rc != HX_OK) return rc;
+  if (!logprobs || (top_k > 0 && (!top_ids || !top_logprobs))) return HX_ERR_NULL;
+  return (dtype == HX_F16 ? launch_sample_rows_logprobs<F16> : launch_sample_rows_logprobs<BF16>)(
+      ids, cut_out, u_out, logits, rows, n, ld, hist_ids, hist_counts, cu_hist, total, penalties, bias_ids, bias_values,
+      cu_bias, bias_total, sample_params, logprobs, top_ids, top_logprobs, top_k, want, (hipStream_t)stream);
 }

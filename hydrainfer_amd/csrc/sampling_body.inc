@@ -1,6 +1,8 @@
-// sampling_body.inc — the body of sampling.hip's kernel, included into sample_rows_kernel (CONSTRAINED = false) and
-// sample_rows_constrained_kernel (CONSTRAINED = true).  Expects the kernels' arguments (bias_ids, bias_values, cu_bias,
-// bias_total included: null and 0 in sample_rows_kernel, where no statement that names them is compiled), T and CONSTRAINED in scope.
+// sampling_body.inc — the body of sampling.hip's kernel, included into sample_rows_kernel (CONSTRAINED = false),
+// sample_rows_constrained_kernel (CONSTRAINED = true) and sample_rows_logprobs_kernel (CONSTRAINED and SCORED).  Expects the
+// kernels' arguments (bias_ids, bias_values, cu_bias, bias_total included: null and 0 in sample_rows_kernel, where no
+// statement that names them is compiled; logprobs, top_ids, top_logprobs, score_k, want likewise where SCORED is false),
+// T, CONSTRAINED and SCORED in scope.
   extern __shared__ __attribute__((aligned(16))) float zs[];      // the row as fp32, n elements (rounded up to 8)
   __shared__ float part_f[2][SMP_WAVES];
   __shared__ int part_i[2][SMP_WAVES];
@@ -17,6 +19,9 @@
   const int32_t top_k = (int32_t)rec[2];
   const float u = (float)(smp_philox0(rec[6], rec[7], rec[4], rec[5]) >> 8) * 0x1p-24f;
   const bool sampled = temperature > 0.f;                          // (a NaN or a negative temperature: greedy)
+  // SCORED: the row's scores are wanted (the same in every thread); a greedy row is then scored as T = 1 over all of it
+  const bool scored = SCORED && (want == nullptr || want[row] >= 0);
+  const float tdiv = SCORED && !sampled ? 1.f : temperature;
 
   // 1. the row into LDS as fp32: 16-byte loads, four in flight, like argmax_rows_kernel
   const bool gvec = (ld % 8 == 0) && ((reinterpret_cast<uintptr_t>(logits) & 15) == 0);
@@ -103,20 +108,31 @@
     if (arg_better(part_f[0][k], part_i[0][k], best, bi)) { best = part_f[0][k]; bi = part_i[0][k]; }
 
   // z = s / T, one correctly rounded division; s -> s / T keeps the order, so the largest z is that of the greedy id
-  const float m = best / temperature;
+  const float m = best / tdiv;
+  if (SCORED) {                                                    // no scores: the fill values, and on as without them
+    const bool degenerate = best != best || !(fabsf(m) < INFINITY);
+    if (!scored || degenerate) {
+      if (tid == 0) logprobs[row] = __builtin_nanf("");
+      if (tid < score_k) {
+        top_ids[row * score_k + tid] = -1;
+        top_logprobs[row * score_k + tid] = __builtin_nanf("");
+      }
+    }
+  }
   if (!sampled || best != best || !(fabsf(m) < INFINITY)) {        // greedy, or degenerate: a NaN, all -inf, a +inf
     if (tid == 0) {
       ids[row] = bi;
       if (cut_out) cut_out[row] = __builtin_nanf("");
       if (u_out) u_out[row] = u;
     }
-    return;
+    // (a scored greedy row that is not degenerate goes on: its Z_S is step 6's sum)
+    if (!SCORED || !scored || best != best || !(fabsf(m) < INFINITY)) return;
   }
   float er[SMP_CHUNK];
   float zmin = INFINITY;
 #pragma unroll
   for (int j = 0; j < SMP_CHUNK; ++j) {
-    zr[j] = zr[j] / temperature;
+    zr[j] = zr[j] / tdiv;
     er[j] = zr[j] == zr[j] ? expf(zr[j] - m) : 0.f;
     zmin = fminf(zmin, zr[j]);                                     // (fminf passes over the NaN of an element not owned)
   }
@@ -134,7 +150,7 @@
   // leaves a key of the row.  Integer atomics: the counts do not depend on the order of the additions.
   const uint32_t khi = smp_key(m);
   uint32_t kcut = smp_key(zmin);
-  if (top_k > 0 && top_k < n) {
+  if (top_k > 0 && top_k < n && (!SCORED || sampled)) {            // (a greedy row ignores the truncation fields)
     uint32_t prefix = 0u;
     int above = 0;
     for (int pass = 0; pass < 4; ++pass) {
@@ -178,7 +194,7 @@
   // minimum over the registers; the cut so far rises to it
   if (CONSTRAINED) {
     const float min_p = __uint_as_float(rec[3]);
-    if (min_p > 0.f) {                                             // (a NaN: off)
+    if (min_p > 0.f && (!SCORED || sampled)) {                     // (a NaN: off)
       float vm = INFINITY;
 #pragma unroll
       for (int j = 0; j < SMP_CHUNK; ++j) vm = er[j] >= min_p ? fminf(vm, zr[j]) : vm;
@@ -195,7 +211,7 @@
 
   // 5. top-p: the smallest key at or above v_K with A(v) = sum of e over {z > v} at most top_p * Z_K.  A only changes at
   // values of the row, so that key is one
-  if (top_p < 1.f) {
+  if (top_p < 1.f && (!SCORED || sampled)) {
     const float vk = smp_val(kcut);
     float s = 0.f;
 #pragma unroll
@@ -248,18 +264,83 @@
   }
   __syncthreads();
   const int walker = s_first < SMP_THREADS ? s_first : s_last;      // rounding left no crossing: the last element of S
-  if (tid == walker) {
+  if (tid == walker && (!SCORED || sampled)) {
     float run = before + excl;
     int pick = -1, last = 0;
+    float zpick = 0.f, zlast = 0.f;                                // (SCORED: z of the pick, without indexing the registers)
 #pragma unroll
     for (int j = 0; j < SMP_CHUNK; ++j) {
       if (zr[j] >= cut) {
         run += er[j];
         last = j;
-        if (pick < 0 && run > target) pick = j;
+        if (SCORED) zlast = zr[j];
+        if (pick < 0 && run > target) {
+          pick = j;
+          if (SCORED) zpick = zr[j];
+        }
       }
     }
     ids[row] = base + (pick < 0 ? last : pick);
     if (cut_out) cut_out[row] = cut;
     if (u_out) u_out[row] = u;
+    if (SCORED && scored) logprobs[row] = ((pick < 0 ? zlast : zpick) - m) - logf(zsum);
+  }
+
+  // 7. SCORED: lp_i = (z_i - m) - logf(Z_S) inside S, -inf outside, Z_S the sum the draw was made against (a greedy row:
+  // S is the whole row, and its id has z = m).  The K alternatives are the first K elements in arg_better's order (the
+  // row has no NaN here), named whether kept or not.  e is dead by now: z stays in the registers as its key (0, which no
+  // value has, for an element not owned), every thread holds the best of its keys, and a round is one block argmax over
+  // (key, then lower index).  The thread that owned a round's pick zeroes that key and looks through its registers
+  // again — within a thread the first of equal keys has the lower index — and only ITS wave redoes the wave's argmax:
+  // every other thread's and wave's candidate still stands.
+  if (SCORED) {
+    if (!scored) return;
+    const float logz = logf(zsum);
+    if (!sampled && tid == 0) logprobs[row] = -logz;
+    uint32_t kr[SMP_CHUNK];
+#pragma unroll
+    for (int j = 0; j < SMP_CHUNK; ++j) {                          // (a number's key lies in [-inf's, +inf's], a NaN's outside)
+      const uint32_t key = smp_key(zr[j]);
+      kr[j] = key - 0x007fffffu <= 0xff800000u - 0x007fffffu ? key : 0u;
+    }
+    uint32_t ck = 0u, wk = 0u;                                     // this thread's candidate; its wave's
+    int ci = 0x7fffffff, wi = 0x7fffffff, pi = -1;                 // (pi: the previous pick; 0x7fffffff: nothing is left)
+    for (int r = 0; r < score_k; ++r) {
+      if (r == 0 || __ballot(ci == pi) != 0ull) {                  // the same in every thread of the wave
+        if (r == 0 || ci == pi) {
+          ck = 0u;
+          ci = 0x7fffffff;
+#pragma unroll
+          for (int j = 0; j < SMP_CHUNK; ++j) {
+            if (base + j == pi) kr[j] = 0u;
+            if (kr[j] > ck) { ck = kr[j]; ci = base + j; }
+          }
+        }
+        wk = ck;
+        wi = ci;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+          const uint32_t ok = __shfl_xor(wk, off, 64);
+          const int oi = __shfl_xor(wi, off, 64);
+          if (ok > wk || (ok == wk && oi < wi)) { wk = ok; wi = oi; }
+        }
+      }
+      round ^= 1;
+      if (lane == 0) { part_f[round][wave] = __uint_as_float(wk); part_i[round][wave] = wi; }
+      __syncthreads();
+      uint32_t bk = __float_as_uint(part_f[round][lane & (SMP_WAVES - 1)]);   // a tree over the sixteen, as smp_block_sum's
+      int bj = part_i[round][lane & (SMP_WAVES - 1)];
+#pragma unroll
+      for (int off = SMP_WAVES / 2; off > 0; off >>= 1) {
+        const uint32_t ok = __shfl_xor(bk, off, 64);
+        const int oi = __shfl_xor(bj, off, 64);
+        if (ok > bk || (ok == bk && oi < bj)) { bk = ok; bj = oi; }
+      }
+      if (tid == 0) {
+        const float bz = smp_val(bk);
+        top_ids[row * score_k + r] = bj == 0x7fffffff ? -1 : bj;
+        top_logprobs[row * score_k + r] = bj != 0x7fffffff && bz >= cut ? (bz - m) - logz : -INFINITY;
+      }
+      pi = bj;
+    }
   }

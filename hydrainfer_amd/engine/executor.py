@@ -19,11 +19,11 @@ from hydrainfer_amd._lib import HydraHipError
 from hydrainfer_amd.engine import rcb as rcb_module
 from hydrainfer_amd.engine.isa import Fill, TextFill
 from hydrainfer_amd.engine.parameters_builder import LanguageModelParametersBuilder
-from hydrainfer_amd.engine.rcb import BatchRequest, PromptTokenLogprob, TokenLogprob
+from hydrainfer_amd.engine.rcb import PROCESSED_LOGPROBS, BatchRequest, PromptTokenLogprob, TokenLogprob
 from hydrainfer_amd.model.llama import LanguageModelParameters
 # (the packers and kernels are reached by name: SAMPLING_MODES)
 from hydrainfer_amd.sampling import (GREEDY_RECORD, NO_PENALTIES, pack_constrained_step, pack_penalty_step, pack_sample_step,
-                                     penalized_argmax_rows, sample_rows, sample_rows_constrained)
+                                     penalized_argmax_rows, sample_rows, sample_rows_constrained, sample_rows_logprobs)
 
 
 # What the table-driven modes of the eager sampling step (BatchFillExecutor._sample) differ in: how many elements of a
@@ -58,6 +58,21 @@ def step_mode(rows):
     else:
         mode = "logprobs" if asking else "plain"
     return mode, max(asking) if asking else None
+
+
+def asks_processed(rcb) -> bool:
+    """The request wants the scores of the distribution its tokens are chosen from (logprobs_mode =
+    "processed_logprobs").  Read with a default: a stand-in for the parameters need not carry the field."""
+    sp = rcb.sampling_params
+    return bool(sp.logprobs) and getattr(sp, "logprobs_mode", None) == PROCESSED_LOGPROBS
+
+
+def scored_rows(rows) -> bool:
+    """rows: the sampling (rcb, inst) pairs of an eager step.  True when some request asks for processed
+    log-probabilities and delivers a token this step (a chunk head's sample is discarded): the step then runs ONE
+    hx_sample_rows_logprobs launch for the whole batch (BatchFillExecutor._sample_scored), whatever step_mode says —
+    this decision is consulted first."""
+    return any(asks_processed(rcb) and not inst.is_chunked for rcb, inst in rows)
 
 
 class PendingToken:
@@ -370,18 +385,9 @@ class BatchFillExecutor:
         if mode == "logprobs":
             return self._sample_with_logprobs(inputs, params, top_k, logits)
         take, packer, forward, kernel = SAMPLING_MODES[mode]
-        n_record = 6 if take == 4 else 5        # min_p (word 3 of a record) travels with the bias tables only
         sel, decode = inputs.selected_token_ids, inputs.all_sequences_decode and logits is None
         n_rows = inputs.input_ids.shape[0] if decode else len(sel)        # the rows of the logits
-        entries = [(None, NO_PENALTIES, GREEDY_RECORD, None)[:take]] * n_rows
-        for i, (rcb, _) in enumerate(sampling_rows(batch)):
-            sp, n_out = rcb.sampling_params, len(rcb.output_token_ids)
-            record = (sp.temperature, sp.top_p, sp.top_k, sp.seed, n_out, sp.min_p)[:n_record] if sp.temperature > 0 \
-                else GREEDY_RECORD
-            bias = rcb.token_constraints.step_entries(n_out) if rcb.token_constraints is not None else None
-            entries[sel[i] if decode else i] = (rcb.penalty_history,
-                                                (sp.frequency_penalty, sp.presence_penalty, sp.repetition_penalty), record,
-                                                bias)[:take]
+        entries, _ = self._step_entries(batch, sel, decode, n_rows, take)
         tables = globals()[packer](entries).to_device(self.device)
         lm, scores = self.language_model, None
         if top_k is None and logits is None:
@@ -401,6 +407,77 @@ class BatchFillExecutor:
             scores = scores and tuple([col[j] for j in sel] for col in scores)
         return sampled, scores
 
+    @staticmethod
+    def _step_entries(batch: BatchRequest, sel, decode: bool, n_rows: int, take: int):
+        """(entries, at): the step's (history, penalties, record, bias)[:take] per logits row — a row that no request
+        samples from rides along as plain greedy — and the logits row of each sampling request, in sampling_rows' order."""
+        n_record = 6 if take == 4 else 5        # min_p (word 3 of a record) travels with the bias tables only
+        entries = [(None, NO_PENALTIES, GREEDY_RECORD, None)[:take]] * n_rows
+        at = []
+        for i, (rcb, _) in enumerate(sampling_rows(batch)):
+            sp, n_out = rcb.sampling_params, len(rcb.output_token_ids)
+            record = (sp.temperature, sp.top_p, sp.top_k, sp.seed, n_out, sp.min_p)[:n_record] if sp.temperature > 0 \
+                else GREEDY_RECORD
+            bias = rcb.token_constraints.step_entries(n_out) if rcb.token_constraints is not None else None
+            at.append(sel[i] if decode else i)
+            entries[at[-1]] = (rcb.penalty_history, (sp.frequency_penalty, sp.presence_penalty, sp.repetition_penalty),
+                               record, bias)[:take]
+        return entries, at
+
+    def _sample_scored(self, batch: BatchRequest, inputs, params, logits=None):
+        """The eager step of a batch in which some request asked for PROCESSED log-probabilities (scored_rows) ->
+        (sampled, scores).  The same logits, then ONE hx_sample_rows_logprobs launch for the whole batch in place of the
+        mode's kernel: the four-element entries of the constrained mode, so constrained, drawn, penalised and plain
+        requests ride along and get the ids they would have got; want = -1 on every row but those of the processed
+        requests that deliver a token, so only those pay for their scores.  K is the largest top_logprobs among them.
+        The tables and `want` reach the device as one pinned buffer in one copy, the ids and scores come back in one.
+        RAW-mode logprobs requests in the same batch (greedy, unpenalised, unconstrained by admission) keep getting their
+        scores from hx_logprob_rows over the raw logits, exactly as in _sample: a mixed batch is two launches and two
+        packed buffers."""
+        rows = sampling_rows(batch)
+        sel, decode = inputs.selected_token_ids, inputs.all_sequences_decode and logits is None
+        n_rows = inputs.input_ids.shape[0] if decode else len(sel)        # the rows of the logits
+        entries, at = self._step_entries(batch, sel, decode, n_rows, 4)
+        step = pack_constrained_step(entries)
+        size = step.buffer.size
+        host = np.empty(size + n_rows, dtype=np.int32)
+        host[:size] = step.buffer
+        host[size:] = -1
+        top_k, raw = 0, []                      # the processed requests' K; the raw-mode requests' top_logprobs
+        for row, (rcb, inst) in zip(at, rows):
+            sp = rcb.sampling_params
+            if inst.is_chunked or not sp.logprobs:
+                continue
+            if asks_processed(rcb):
+                host[size + row] = 0
+                top_k = max(top_k, sp.top_logprobs)
+            else:
+                raw.append(sp.top_logprobs)
+        host = torch.from_numpy(host)
+        if torch.device(self.device).type == "cuda":
+            host = host.pin_memory()
+        dev = host.to(self.device, non_blocking=True)
+        tables, want = step.views(dev[:size]), dev[size:]
+        lm = self.language_model
+        if not raw and logits is None:
+            ids = lm.forward_scored(inputs.input_ids, inputs.image_features, inputs.position_ids, params, *tables,
+                                    top_k=top_k, want=want)[0]
+        else:
+            if logits is None:
+                logits = lm.forward_logits(inputs.input_ids, inputs.image_features, inputs.position_ids, params)
+            if raw:
+                raw_packed = logprob_rows_packed(logprob_rows(logits, max(raw))[0], max(raw))
+            ids = sample_rows_logprobs(logits, *tables, top_k=top_k, want=want)[0]
+        ids, lp, top_ids, top_lp = logprob_rows_views(logprob_rows_packed(ids, top_k).cpu(), n_rows, top_k)
+        sampled, scores = ids.tolist(), [lp.tolist(), top_ids.tolist(), top_lp.tolist()]
+        if raw:
+            raw_scores = [t.tolist() for t in logprob_rows_views(raw_packed.cpu(), n_rows, max(raw))[1:]]
+            for row, (rcb, _) in zip(at, rows):
+                if rcb.sampling_params.logprobs and not asks_processed(rcb):
+                    for col, raw_col in zip(scores, raw_scores):
+                        col[row] = raw_col[row]
+        return [sampled[j] for j in at], tuple([col[j] for j in at] for col in scores)
+
     def _execute_scoring(self, batch: BatchRequest, inputs) -> None:
         """The eager step of a batch in which some request scores its prompt (sampling_params.prompt_logprobs): ONE forward
         whose last layer is narrowed to the union of the sampling and the scoring rows (inputs.score_plan), ONE
@@ -418,7 +495,9 @@ class BatchFillExecutor:
         if inputs.selected_token_ids:
             rows = logits.index_select(0, plan.sample_pos_tensor)
             mode, top_k = step_mode(sampling_rows(batch))
-            if mode == "plain":
+            if scored_rows(sampling_rows(batch)):
+                sampled, scores = self._sample_scored(batch, inputs, params, rows)
+            elif mode == "plain":
                 sampled = argmax_rows(rows).tolist()
             else:
                 sampled, scores = self._sample(mode, batch, inputs, params, top_k, rows)
@@ -477,6 +556,9 @@ class BatchFillExecutor:
                 self.language_model.embed(inputs.input_ids, inputs.image_features, inputs.image_row_index),
                 inputs.position_ids, params)
             batch.step()
+            return
+        if scored_rows(sampling_rows(batch)):
+            self._deliver(batch, *self._sample_scored(batch, inputs, params))
             return
         mode, top_k = step_mode(sampling_rows(batch))
         if mode != "plain":

@@ -14,6 +14,7 @@ from hydrainfer_amd.engine.scheduler import BatchSchedulerConfig
 from hydrainfer_amd.engine.serve import build_node, quiet_gc, warm_library_gemms
 from hydrainfer_amd.memory.shared_cache import compute_image_hash
 from hydrainfer_amd.model.processor import ClipImageProcessor
+from hydrainfer_amd.utils import keyword_argument
 
 
 @dataclass
@@ -30,6 +31,7 @@ class OfflineInferenceOutput:
     prompt_logprobs: List[Optional[PromptTokenLogprob]] = field(default_factory=list)
 
 
+@keyword_argument("logprobs_mode")
 @dataclass
 class OfflineRequest:
     token_ids: List[int]
@@ -49,10 +51,14 @@ class OfflineRequest:
     # token constraints — keyword-only, declared ahead of prompt_logprobs (which stays the last field).  logit_bias: token
     # id -> bias in -100 .. 100, added to the logit before the penalties; min_tokens: no eos_token_ids entry is emitted
     # before this many tokens are generated; min_p in [0, 1]: sampled requests keep only tokens with p >= min_p * p_max.
-    # A constrained request decodes eagerly and cannot ask for logprobs
+    # A constrained request decodes eagerly and can ask for logprobs only with logprobs_mode = "processed_logprobs"
     logit_bias: Optional[Dict[int, float]] = field(default=None, kw_only=True)
     min_tokens: int = field(default=0, kw_only=True)
     min_p: float = field(default=0.0, kw_only=True)
+    # None / "raw_logprobs": `logprobs` scores the model's raw softmax (not combinable with temperature > 0, penalties or
+    # constraints); "processed_logprobs": the distribution the token was chosen from, combinable with all of them
+    # (init=False and the class's keyword_argument decorator: taken by keyword only, the generated signature as it was)
+    logprobs_mode: Optional[str] = field(default=None, init=False)
     prompt_logprobs: Optional[int] = None   # 0..20: the log-probability of every prompt token given what stands before it,
                                             # with that many alternatives per position; combinable with everything above
 
@@ -106,7 +112,7 @@ class OfflineInferenceEngine:
                                                                       r.temperature, r.top_p, r.top_k, r.seed,
                                                                       prompt_logprobs=r.prompt_logprobs,
                                                                       logit_bias=r.logit_bias, min_tokens=r.min_tokens,
-                                                                      min_p=r.min_p),
+                                                                      min_p=r.min_p, logprobs_mode=r.logprobs_mode),
                                    token_params=r.token_params)
                 rcb = self.creator.process(req, vocab_size=self.vocab_size)
                 rcb.metric.arrival_time = time.perf_counter()

@@ -7,8 +7,10 @@ from typing import Dict, List, Optional, Tuple
 
 from hydrainfer_amd.engine.isa import Instruction, InstructionList
 from hydrainfer_amd.memory.token_cache import VirtualTokenCache
+from hydrainfer_amd.utils import keyword_argument
 
 
+@keyword_argument("logprobs_mode")
 @dataclass
 class SamplingParameters:
     max_tokens: int = 50
@@ -17,20 +19,22 @@ class SamplingParameters:
     top_logprobs: int = 0       # 0..20 most likely alternatives in each of them; needs logprobs
     # steps 1-2 of the reference's process_logits (hydrainfer/sampling/logits_processor.py:65-72) over the request's
     # GENERATED tokens (hydrainfer_amd/sampling); (0, 0, 1) is the identity: such a request is sampled as before.  A
-    # penalised request decodes eagerly and cannot ask for logprobs.
+    # penalised request decodes eagerly and can ask for logprobs only with logprobs_mode = "processed_logprobs".
     frequency_penalty: float = 0.0      # subtracted once per earlier occurrence of a token
     presence_penalty: float = 0.0       # subtracted once from every token that occurred
     repetition_penalty: float = 1.0     # > 0: a token that occurred has its logit divided (if negative: multiplied) by it
     # steps 3-5 of process_logits and a seeded draw (hx_sample_rows, include/hydra_hip.h).  temperature 0 is GREEDY
     # (OpenAI's meaning of 0), and an absent temperature means 0 here, where OpenAI's default is 1: every request that does
-    # not ask for sampling keeps the argmax paths.  A sampled request decodes eagerly and cannot ask for logprobs.
+    # not ask for sampling keeps the argmax paths.  A sampled request decodes eagerly and can ask for logprobs only with
+    # logprobs_mode = "processed_logprobs".
     temperature: float = 0.0            # >= 0; > 0: the logits are divided by it and a token is drawn
     top_p: float = 1.0                  # (0, 1]: the smallest set of most likely tokens holding this much probability
     top_k: int = 0                      # >= 0: only the k most likely tokens (ties at the cut are all kept); 0: off
     seed: Optional[int] = None          # 0 .. 2^63 - 1; a sampled request without one is given one at admission
     # token constraints (hx_sample_rows_constrained, include/hydra_hip.h): edits of the logits ahead of the choice, greedy
-    # or sampled.  A constrained request decodes eagerly and cannot ask for logprobs (hx_logprob_rows scores the raw
-    # logits and names the raw argmax); prompt_logprobs stays combinable.  The three are keyword-only — positional
+    # or sampled.  A constrained request decodes eagerly and can ask for logprobs only with logprobs_mode =
+    # "processed_logprobs" (hx_logprob_rows scores the raw logits and names the raw argmax); prompt_logprobs stays
+    # combinable.  The three are keyword-only — positional
     # construction is what it was — and declared AHEAD of prompt_logprobs, which stays the last field.
     # logit_bias: token id -> a bias in -100 .. 100 added to its logit BEFORE the penalties; min_tokens: every
     # eos_token_ids entry is banned until this many tokens are generated; min_p in [0, 1]: only tokens at least this
@@ -38,6 +42,13 @@ class SamplingParameters:
     logit_bias: Optional[Dict[int, float]] = field(default=None, kw_only=True)
     min_tokens: int = field(default=0, kw_only=True)
     min_p: float = field(default=0.0, kw_only=True)
+    # which distribution `logprobs` scores (vLLM's option of the same name; keyword-only, ahead of prompt_logprobs).  None
+    # or "raw_logprobs": the model's softmax over the raw logits (hx_logprob_rows) — such a request cannot be sampled,
+    # penalised or constrained.  "processed_logprobs": the distribution the token was actually chosen from — after
+    # logit_bias, penalties, temperature, top-k, min_p and top-p, renormalised over the kept set (hx_sample_rows_logprobs,
+    # the same launch that chooses the token); needs logprobs, combines with all of the above.  prompt_logprobs stays raw.
+    # (init=False and the class's keyword_argument decorator: taken by keyword only, the generated signature as it was)
+    logprobs_mode: Optional[str] = field(default=None, init=False)
     # the log-probability of every PROMPT token given what stands before it (vLLM's `prompt_logprobs`;
     # hx_token_logprob_rows over the prefill's logits): None = off, 0..20 = score, with that many alternatives per position.
     # Independent of `logprobs` and of the sampling mode: scoring reads the prompt's rows, sampling the last one.  Such a
@@ -46,12 +57,26 @@ class SamplingParameters:
 
 
 MAX_TOP_LOGPROBS = 20
+RAW_LOGPROBS, PROCESSED_LOGPROBS = "raw_logprobs", "processed_logprobs"      # the values of logprobs_mode (None: raw)
+
+
+def check_logprobs_mode(mode, logprobs: bool) -> Optional[str]:
+    """The value checked, or ValueError: None or one of the two names; the processed mode needs logprobs."""
+    if mode is not None and mode not in (RAW_LOGPROBS, PROCESSED_LOGPROBS):
+        raise ValueError(f"logprobs_mode {mode!r} must be {RAW_LOGPROBS!r} or {PROCESSED_LOGPROBS!r}")
+    if mode == PROCESSED_LOGPROBS and not logprobs:
+        raise ValueError(f"logprobs_mode = {PROCESSED_LOGPROBS!r} needs logprobs = True")
+    return mode
 
 
 @dataclass
 class TokenLogprob:
     """One generated token's score: its log-probability under the model's softmax (fp32, hx_logprob_rows) and the
-    request's top_logprobs most likely (token id, log-probability) pairs, most likely first (ties: lower id first)."""
+    request's top_logprobs most likely (token id, log-probability) pairs, most likely first (ties: lower id first).
+    With logprobs_mode = "processed_logprobs" the distribution is the one the step's choice rule picked the token from
+    (fp32, hx_sample_rows_logprobs): the logits after logit_bias, penalties and temperature, cut by top-k, min_p and
+    top-p and renormalised over what is left — for a greedy request the softmax of its biased, penalised logits.
+    `logprob` is then always finite; an alternative that the truncation dropped is still listed, with -inf."""
     token_id: int
     logprob: float
     top: List[Tuple[int, float]] = field(default_factory=list)

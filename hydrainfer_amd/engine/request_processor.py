@@ -9,8 +9,8 @@ import xxhash
 
 from hydrainfer_amd.engine.isa import (EPMigrate, ImageEmbed, ImageEmbedFill, InstructionListBuilder,
                                        PDMigrate, PullCache, TextFill)
-from hydrainfer_amd.engine.rcb import (MAX_TOP_LOGPROBS, RequestControlBlock, RequestMetaData, SamplingParameters,
-                                       ScenarioClassifier, TokenParameters)
+from hydrainfer_amd.engine.rcb import (MAX_TOP_LOGPROBS, PROCESSED_LOGPROBS, RequestControlBlock, RequestMetaData,
+                                       SamplingParameters, ScenarioClassifier, TokenParameters, check_logprobs_mode)
 from hydrainfer_amd.memory.shared_cache import compute_hash
 from hydrainfer_amd.sampling import (PenaltyHistory, TokenConstraints, check_constraints, check_penalties, check_sampling,
                                      is_constrained, is_penalized, is_sampled)
@@ -124,6 +124,7 @@ class InstructionCreator:
             raise ValueError(f"request {request.request_id}: prompt_logprobs {ask!r} must be None or an integer "
                              f"0..{MAX_TOP_LOGPROBS}")
         try:
+            mode = check_logprobs_mode(getattr(sp, "logprobs_mode", None), sp.logprobs)
             penalties = check_penalties(sp.frequency_penalty, sp.presence_penalty, sp.repetition_penalty)
             sampling = check_sampling(sp.temperature, sp.top_p, sp.top_k, sp.seed)
             logit_bias, min_tokens, min_p = check_constraints(sp.logit_bias, sp.min_tokens, sp.min_p)
@@ -131,30 +132,34 @@ class InstructionCreator:
             raise ValueError(f"request {request.request_id}: {e}") from None
         rcb.sampling_params = SamplingParameters(sp.max_tokens, list(sp.eos_token_ids), sp.logprobs, top, *penalties,
                                                  *sampling, prompt_logprobs=ask, logit_bias=logit_bias,
-                                                 min_tokens=min_tokens, min_p=min_p)
+                                                 min_tokens=min_tokens, min_p=min_p, logprobs_mode=mode)
+        # raw scores (hx_logprob_rows) describe the raw argmax: refused beside anything that changes the choice.  The
+        # processed mode scores the choice itself (hx_sample_rows_logprobs) and combines with all of it.
+        raw_scores = sp.logprobs and mode != PROCESSED_LOGPROBS
+        hint = f' (logprobs_mode = "{PROCESSED_LOGPROBS}" scores the token under the distribution it was chosen from)'
         if vocab_size is not None and logit_bias and max(logit_bias) >= vocab_size:
             raise ValueError(f"request {request.request_id}: logit_bias names token {max(logit_bias)}, the vocabulary has "
                              f"{vocab_size}")
         if min_tokens > sp.max_tokens:
             raise ValueError(f"request {request.request_id}: min_tokens {min_tokens} exceeds max_tokens {sp.max_tokens}")
-        if sp.logprobs and (logit_bias or min_tokens > 0 or min_p > 0):
+        if raw_scores and (logit_bias or min_tokens > 0 or min_p > 0):
             raise ValueError(f"request {request.request_id}: logit_bias / min_tokens / min_p cannot be combined with "
                              "logprobs yet: hx_logprob_rows scores the raw logits and names the raw argmax, not the "
                              "constrained choice (prompt_logprobs, which scores the prompt from raw logits by "
-                             "definition, can be)")
+                             "definition, can be)" + hint)
         if is_sampled(rcb.sampling_params):
-            if sp.logprobs:
+            if raw_scores:
                 raise ValueError(f"request {request.request_id}: temperature > 0 cannot be combined with logprobs yet: "
                                  "OpenAI reports the log-probability of the sampled token, hx_logprob_rows that of the "
-                                 "greedy one")
+                                 "greedy one" + hint)
             if rcb.sampling_params.seed is None:
                 # 63 random bits, kept with the request: a finished request can be replayed from its parameters
                 rcb.sampling_params.seed = secrets.randbits(63)
         if is_penalized(rcb.sampling_params):
-            if sp.logprobs:
+            if raw_scores:
                 raise ValueError(f"request {request.request_id}: frequency / presence / repetition penalties cannot be "
                                  "combined with logprobs yet: the score of a penalised choice needs the log-softmax "
-                                 "kernel to see the penalties, a follow-up change")
+                                 "kernel to see the penalties, a follow-up change" + hint)
             rcb.penalty_history = PenaltyHistory()
         if not self.ignore_eos:
             rcb.sampling_params.eos_token_ids.append(self.eos_token_id)

@@ -13,9 +13,13 @@ import math
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional
 
+from hydrainfer_amd.utils import keyword_argument
+
 IMAGE_TOKEN = "<image>"            # hydrainfer/model/llava.py:195
 CHUNK_OBJECT = "chat.completion.chunk"
 MAX_TOP_LOGPROBS = 20              # OpenAI's limit
+PROCESSED_LOGPROBS = "processed_logprobs"
+LOGPROBS_MODES = ("raw_logprobs", PROCESSED_LOGPROBS)      # `logprobs_mode` (vLLM's names; engine/rcb.py)
 MAX_STOP_TOKEN_IDS = 16
 
 
@@ -23,6 +27,7 @@ class ProtocolError(ValueError):
     """A request the reference would reject (its asserts / pydantic validation -> HTTP 4xx / 500 there; 400 here)."""
 
 
+@keyword_argument("logprobs_mode")
 @dataclass
 class ChatRequest:
     model: str
@@ -48,6 +53,10 @@ class ChatRequest:
     min_tokens: int = field(default=0, kw_only=True)
     min_p: float = field(default=0.0, kw_only=True)
     stop_token_ids: Optional[List[int]] = field(default=None, kw_only=True)
+    # extension (vLLM's name): which distribution `logprobs` scores — absent / "raw_logprobs": the model's raw softmax (not
+    # combinable with temperature > 0, penalties or constraints); "processed_logprobs": the one the token was chosen from
+    # (init=False and the class's keyword_argument decorator: taken by keyword only, the generated signature as it was)
+    logprobs_mode: Optional[str] = field(default=None, init=False)
     prompt_logprobs: Optional[int] = None   # extension (vLLM's name; OpenAI's chat API has no `echo`): 0..20 — the stream's
                                             # first chunk carries the score of every prompt token, with that many alternatives
 
@@ -107,6 +116,13 @@ def parse_chat_completion_request(body: dict) -> ChatRequest:
         raise ProtocolError(f"top_logprobs: integer 0..{MAX_TOP_LOGPROBS} required")
     if top_logprobs > 0 and not logprobs:
         raise ProtocolError("top_logprobs requires logprobs: true")
+    logprobs_mode = body.get("logprobs_mode")
+    if logprobs_mode is not None and logprobs_mode not in LOGPROBS_MODES:
+        raise ProtocolError(f"logprobs_mode: one of {' / '.join(LOGPROBS_MODES)} required")
+    if logprobs_mode == PROCESSED_LOGPROBS and not logprobs:
+        raise ProtocolError(f"logprobs_mode: {PROCESSED_LOGPROBS} requires logprobs: true")
+    raw_scores = logprobs and logprobs_mode != PROCESSED_LOGPROBS        # (the processed mode scores the choice itself)
+    hint = f' (logprobs_mode: "{PROCESSED_LOGPROBS}" scores the token under the distribution it was chosen from)'
     penalties = {}
     for name in ("frequency_penalty", "presence_penalty"):
         v = body.get(name)
@@ -121,8 +137,8 @@ def parse_chat_completion_request(body: dict) -> ChatRequest:
     if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v <= 0:
         raise ProtocolError("repetition_penalty: number > 0 required")
     penalties["repetition_penalty"] = float(v)
-    if logprobs and (penalties["frequency_penalty"] or penalties["presence_penalty"] or v != 1):
-        raise ProtocolError("logprobs cannot be combined with frequency / presence / repetition penalties yet")
+    if raw_scores and (penalties["frequency_penalty"] or penalties["presence_penalty"] or v != 1):
+        raise ProtocolError("logprobs cannot be combined with frequency / presence / repetition penalties yet" + hint)
     sampling = {}
     v = body.get("temperature")
     if v is None:
@@ -146,22 +162,22 @@ def parse_chat_completion_request(body: dict) -> ChatRequest:
     if v is not None and (isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= (1 << 63) - 1):
         raise ProtocolError("seed: integer in 0..2^63-1 required")
     sampling["seed"] = v
-    if logprobs and sampling["temperature"] > 0:
-        raise ProtocolError("logprobs cannot be combined with temperature > 0 yet")
+    if raw_scores and sampling["temperature"] > 0:
+        raise ProtocolError("logprobs cannot be combined with temperature > 0 yet" + hint)
     prompt_logprobs = body.get("prompt_logprobs")
     if prompt_logprobs is not None and (isinstance(prompt_logprobs, bool) or not isinstance(prompt_logprobs, int)
                                         or not 0 <= prompt_logprobs <= MAX_TOP_LOGPROBS):
         raise ProtocolError(f"prompt_logprobs: integer 0..{MAX_TOP_LOGPROBS} required")
     constraints = _parse_constraints(body)
-    if logprobs and (constraints["logit_bias"] or constraints["min_tokens"] > 0 or constraints["min_p"] > 0):
-        raise ProtocolError("logprobs cannot be combined with logit_bias / min_tokens / min_p yet")
+    if raw_scores and (constraints["logit_bias"] or constraints["min_tokens"] > 0 or constraints["min_p"] > 0):
+        raise ProtocolError("logprobs cannot be combined with logit_bias / min_tokens / min_p yet" + hint)
     try:
         png = base64.b64decode(images[0], validate=True) if images else None
     except Exception:
         raise ProtocolError("image_url: invalid base64")
     return ChatRequest(model=model, role=role, text=text, image_png=png, max_tokens=max_tokens,
                        stream=bool(body.get("stream", False)), logprobs=logprobs, top_logprobs=top_logprobs, **penalties, **sampling,
-                       prompt_logprobs=prompt_logprobs, **constraints)
+                       prompt_logprobs=prompt_logprobs, logprobs_mode=logprobs_mode, **constraints)
 
 
 def _parse_constraints(body: dict) -> dict:

@@ -287,7 +287,7 @@ class ApiServer:
                                                                prompt_logprobs=req.prompt_logprobs,
                                                                eos_token_ids=list(req.stop_token_ids or ()),
                                                                logit_bias=req.logit_bias, min_tokens=req.min_tokens,
-                                                               min_p=req.min_p))
+                                                               min_p=req.min_p, logprobs_mode=req.logprobs_mode))
 
     # ------------------------------------------------------------------ HTTP
     @staticmethod

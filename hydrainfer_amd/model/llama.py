@@ -616,4 +616,17 @@ class LlamaForCausalLM:
         return sample_rows_constrained(logits, sample_params, bias_ids, bias_values, cu_bias, hist_ids, hist_counts, cu_hist,
                                        penalties, out)
 
+    def forward_scored(self, input_ids_or_embeds, position_ids, model_params, sample_params, bias_ids, bias_values,
+                       cu_bias, hist_ids=None, hist_counts=None, cu_hist=None, penalties=None, *, top_k: int, want=None,
+                       out=None):
+        """forward_constrained() for a step with a request that asked for the scores of the PROCESSED distribution
+        (logprobs_mode = "processed_logprobs"): the same logits, then ONE launch (sampling.sample_rows_logprobs) that
+        gives forward_constrained()'s ids and, for the rows with want >= 0, the log-probability of each id under the
+        distribution it was chosen from and the top_k alternatives — (ids, logprobs, top_ids, top_logprobs), views of
+        one buffer (`out`) in logprob_rows' layout.  Eager only: not part of the launch plan or the captured graphs."""
+        from hydrainfer_amd.sampling import sample_rows_logprobs
+        logits = self.forward_logits(input_ids_or_embeds, position_ids, model_params)
+        return sample_rows_logprobs(logits, sample_params, bias_ids, bias_values, cu_bias, hist_ids, hist_counts, cu_hist,
+                                    penalties, top_k=top_k, want=want, out=out)
+
     __call__ = forward

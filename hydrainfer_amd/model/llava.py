@@ -74,4 +74,17 @@ class LlavaLanguageModel:
                                        sample_params, bias_ids, bias_values, cu_bias, hist_ids, hist_counts, cu_hist,
                                        penalties, out)
 
+    def forward_scored(self, input_ids: Tensor, image_features: Optional[Tensor], position_ids: Tensor,
+                       model_params: LanguageModelParameters, sample_params: Tensor, bias_ids: Tensor, bias_values: Tensor,
+                       cu_bias: Tensor, hist_ids: Optional[Tensor] = None, hist_counts: Optional[Tensor] = None,
+                       cu_hist: Optional[Tensor] = None, penalties: Optional[Tensor] = None, *, top_k: int,
+                       want: Optional[Tensor] = None, out: Optional[Tensor] = None):
+        """forward_constrained() plus the scores of the processed distribution: (ids, logprobs, top_ids, top_logprobs),
+        one launch behind the logits (hx_sample_rows_logprobs); the ids are forward_constrained()'s, a row with
+        want < 0 is not scored."""
+        from hydrainfer_amd.sampling import sample_rows_logprobs
+        return sample_rows_logprobs(self.forward_logits(input_ids, image_features, position_ids, model_params),
+                                    sample_params, bias_ids, bias_values, cu_bias, hist_ids, hist_counts, cu_hist,
+                                    penalties, top_k=top_k, want=want, out=out)
+
     __call__ = forward

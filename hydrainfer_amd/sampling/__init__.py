@@ -21,7 +21,12 @@ CSR, `pack_sample_step` does the same with the rows' sampling records in front â
 Token constraints (`logit_bias`, `min_tokens`, `min_p`): `sample_rows_constrained` (hx_sample_rows_constrained) is
 `sample_rows` with a per-row (token, bias) table added ahead of the penalties and a min_p cut; `TokenConstraints` is a
 request's table on the host (min_tokens: its end-of-sequence ids banned while too few tokens stand), and
-`pack_constrained_step` appends the step's bias CSR to `pack_sample_step`'s buffer."""
+`pack_constrained_step` appends the step's bias CSR to `pack_sample_step`'s buffer.
+
+Scores of the processed distribution (`logprobs_mode = "processed_logprobs"`): `sample_rows_logprobs`
+(hx_sample_rows_logprobs) is `sample_rows_constrained` that also writes, for the rows that want it, the log-probability
+of the chosen token under the distribution it was chosen from and the K most likely alternatives of that distribution,
+in `logprob_rows`' packed layout."""
 import math
 from array import array
 from typing import Optional, Sequence, Tuple
@@ -163,8 +168,10 @@ def pack_penalty_step(entries) -> PenaltyStep:
     return PenaltyStep(buf, rows, total)
 
 
-def _check_sample_arguments(what: str, logits, sample_params, hist_ids, hist_counts, cu_hist, penalties, out, cut_out, u_out):
-    """The argument checks sample_rows and sample_rows_constrained share -> (rows, total, out)."""
+def _check_sample_arguments(what: str, logits, sample_params, hist_ids, hist_counts, cu_hist, penalties, out, cut_out, u_out,
+                            ids_in_packed: bool = False):
+    """The argument checks sample_rows, sample_rows_constrained and sample_rows_logprobs share -> (rows, total, out).
+    ids_in_packed: the ids go into the caller's packed buffer (sample_rows_logprobs): no `out` is checked or made."""
     if logits.dim() != 2 or logits.stride(1) != 1 or logits.dtype not in (torch.float16, torch.bfloat16) \
             or logits.shape[0] < 1 or not 1 <= logits.shape[1] <= SAMPLE_MAX_N or logits.stride(0) < logits.shape[1]:
         raise _lib.HydraHipError(f"{what}: logits must be fp16 / bf16 [rows, n] (rows >= 1, 1 <= n <= {SAMPLE_MAX_N}) "
@@ -186,7 +193,9 @@ def _check_sample_arguments(what: str, logits, sample_params, hist_ids, hist_cou
                 raise _lib.HydraHipError(f"{what}: {name} must be a contiguous int32 tensor of shape {list(shape)}")
         if penalties.dtype != torch.float32 or tuple(penalties.shape) != (rows, 3) or not penalties.is_contiguous():
             raise _lib.HydraHipError(f"{what}: penalties must be a contiguous fp32 tensor of shape [{rows}, 3]")
-    if out is None:
+    if ids_in_packed:
+        pass
+    elif out is None:
         out = torch.empty(rows, dtype=torch.int64, device=logits.device)
     elif out.dtype != torch.int64 or out.shape != (rows,) or not out.is_contiguous() or out.device != logits.device:
         raise _lib.HydraHipError(f"{what}: out must be a contiguous int64 [rows] tensor on the logits' device")
@@ -291,6 +300,18 @@ MAX_LOGIT_BIAS = 300            # entries of one request's logit_bias (OpenAI's 
 LOGIT_BIAS_RANGE = 100.0        # |bias| at most this (OpenAI's range)
 
 
+def _check_bias_arguments(what: str, logits, rows, bias_ids, bias_values, cu_bias) -> int:
+    """The checks of the bias CSR that sample_rows_constrained and sample_rows_logprobs share -> bias_total."""
+    bias_total = bias_ids.numel()
+    for name, t, dtype, shape in (("bias_ids", bias_ids, torch.int32, (bias_total,)),
+                                  ("bias_values", bias_values, torch.float32, (bias_total,)),
+                                  ("cu_bias", cu_bias, torch.int32, (rows + 1,))):
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != logits.device:
+            raise _lib.HydraHipError(f"{what}: {name} must be a contiguous {str(dtype)[6:]} tensor of shape "
+                                     f"{list(shape)} on the logits' device")
+    return bias_total
+
+
 def sample_rows_constrained(logits: Tensor, sample_params: Tensor, bias_ids: Tensor, bias_values: Tensor, cu_bias: Tensor,
                             hist_ids: Optional[Tensor] = None, hist_counts: Optional[Tensor] = None,
                             cu_hist: Optional[Tensor] = None, penalties: Optional[Tensor] = None,
@@ -305,13 +326,7 @@ def sample_rows_constrained(logits: Tensor, sample_params: Tensor, bias_ids: Ten
                      cut_out, u_out)
     rows, total, out = _check_sample_arguments("sample_rows_constrained", logits, sample_params, hist_ids, hist_counts, cu_hist,
                                                penalties, out, cut_out, u_out)
-    bias_total = bias_ids.numel()
-    for name, t, dtype, shape in (("bias_ids", bias_ids, torch.int32, (bias_total,)),
-                                  ("bias_values", bias_values, torch.float32, (bias_total,)),
-                                  ("cu_bias", cu_bias, torch.int32, (rows + 1,))):
-        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != logits.device:
-            raise _lib.HydraHipError(f"sample_rows_constrained: {name} must be a contiguous {str(dtype)[6:]} tensor of shape "
-                                     f"{list(shape)} on the logits' device")
+    bias_total = _check_bias_arguments("sample_rows_constrained", logits, rows, bias_ids, bias_values, cu_bias)
     ptr = (lambda t: t.data_ptr()) if total else (lambda t: None)
     bptr = (lambda t: t.data_ptr()) if bias_total else (lambda t: None)
     _lib.check(_lib.lib().hx_sample_rows_constrained(
@@ -320,6 +335,48 @@ def sample_rows_constrained(logits: Tensor, sample_params: Tensor, bias_ids: Ten
         ptr(penalties), bptr(bias_ids), bptr(bias_values), bptr(cu_bias), bias_total, sample_params.data_ptr(),
         _lib.dtype_code(logits), _lib.current_stream()), "sample_rows_constrained")
     return out
+
+
+def sample_rows_logprobs(logits: Tensor, sample_params: Tensor, bias_ids: Tensor, bias_values: Tensor, cu_bias: Tensor,
+                         hist_ids: Optional[Tensor] = None, hist_counts: Optional[Tensor] = None,
+                         cu_hist: Optional[Tensor] = None, penalties: Optional[Tensor] = None, *, top_k: int,
+                         want: Optional[Tensor] = None, out: Optional[Tensor] = None, cut_out: Optional[Tensor] = None,
+                         u_out: Optional[Tensor] = None):
+    """`sample_rows_constrained` that also scores its choice, still one launch (include/hydra_hip.h:
+    hx_sample_rows_logprobs).  Returns (ids int64 [rows] â€” sample_rows_constrained's, bit for bit â€”, logprobs fp32 [rows],
+    top_ids int32 [rows, K], top_logprobs fp32 [rows, K]): the log-probability of each id under the distribution the
+    row's choice rule picks from (after bias, penalties, temperature, top-k, min_p and top-p, renormalised over the kept
+    set; a greedy row: the softmax of its biased, penalised logits), and the top_k (0..20) most likely tokens of that
+    distribution, -inf for one the truncation dropped.  want: None (every row is scored) or int32 [rows]; a row with
+    want < 0 is not scored (NaN, -1, NaN) and costs what it costs in sample_rows_constrained.  The four results are views
+    of one uint8 buffer with logprob_rows' layout (`out`, or a new one: logprob_rows_bytes / logprob_rows_views), which
+    goes to the host in one copy (logprob_rows_packed)."""
+    from hydrainfer_amd._C.kernel.norm import LOGPROB_MAX_TOP_K, logprob_rows_bytes, logprob_rows_views
+    _lib.require_gpu(logits, sample_params, bias_ids, bias_values, cu_bias, hist_ids, hist_counts, cu_hist, penalties, want,
+                     out, cut_out, u_out)
+    what = "sample_rows_logprobs"
+    if not isinstance(top_k, int) or isinstance(top_k, bool) or not 0 <= top_k <= LOGPROB_MAX_TOP_K:
+        raise _lib.HydraHipError(f"{what}: top_k {top_k!r} outside 0..{LOGPROB_MAX_TOP_K}")
+    rows, total, _ = _check_sample_arguments(what, logits, sample_params, hist_ids, hist_counts, cu_hist, penalties, None,
+                                             cut_out, u_out, ids_in_packed=True)
+    bias_total = _check_bias_arguments(what, logits, rows, bias_ids, bias_values, cu_bias)
+    if want is not None and (want.dtype != torch.int32 or tuple(want.shape) != (rows,) or not want.is_contiguous()
+                             or want.device != logits.device):
+        raise _lib.HydraHipError(f"{what}: want must be a contiguous int32 tensor of shape [{rows}] on the logits' device")
+    if out is None:
+        out = torch.empty(logprob_rows_bytes(rows, top_k), dtype=torch.uint8, device=logits.device)
+    elif out.device != logits.device or out.data_ptr() % 8:
+        raise _lib.HydraHipError(f"{what}: out must be an 8-byte aligned buffer on the logits' device")
+    ids, lp, top_ids, top_lp = logprob_rows_views(out, rows, top_k)
+    ptr = (lambda t: t.data_ptr()) if total else (lambda t: None)
+    bptr = (lambda t: t.data_ptr()) if bias_total else (lambda t: None)
+    _lib.check(_lib.lib().hx_sample_rows_logprobs(
+        ids.data_ptr(), cut_out.data_ptr() if cut_out is not None else None, u_out.data_ptr() if u_out is not None else None,
+        logits.data_ptr(), rows, logits.shape[1], logits.stride(0), ptr(hist_ids), ptr(hist_counts), ptr(cu_hist), total,
+        ptr(penalties), bptr(bias_ids), bptr(bias_values), bptr(cu_bias), bias_total, sample_params.data_ptr(),
+        lp.data_ptr(), top_ids.data_ptr() if top_k else None, top_lp.data_ptr() if top_k else None, top_k,
+        want.data_ptr() if want is not None else None, _lib.dtype_code(logits), _lib.current_stream()), what)
+    return ids, lp, top_ids, top_lp
 
 
 def check_constraints(logit_bias, min_tokens, min_p):

@@ -345,6 +345,31 @@ int hx_sample_rows_constrained(int64_t* ids, float* cut_out, float* u_out, const
                                int64_t total, const float* penalties, const int32_t* bias_ids, const float* bias_values,
                                const int32_t* cu_bias, int64_t bias_total, const void* sample_params, int dtype,
                                hx_stream stream);
+/* hx_sample_rows_logprobs: hx_sample_rows_constrained that also SCORES the token it chose, under the distribution it
+ * chose it from, still one launch and one read of the logits (extension; added WITHOUT raising HX_ABI_VERSION: nothing
+ * that existed changed).  ids, cut_out and u_out are hx_sample_rows_constrained's bit for bit, whatever want and top_k.
+ * want: int32 [rows], may be NULL (every row is scored).  logprobs fp32 [rows]; top_ids int32 / top_logprobs fp32, dense
+ * [rows, top_k], top_k in 0..20 (both may be NULL with top_k == 0).  Per row r:
+ *   want[r] < 0 — not scored: logprobs[r] NaN, top_ids -1, top_logprobs NaN; the row does what it does in
+ *   hx_sample_rows_constrained and nothing more (a greedy row leaves before the selection).
+ *   Scored: T' = T if T > 0, else 1; z_i = s_i / T' (s: the biased, penalised value); m = max z; e_i = expf(z_i - m).
+ *   The kept set S is {z_i >= v*} for a sampled row and every index for a greedy one (which ignores top_k, top_p and
+ *   min_p, as its choice does).  Z_S: the fp32 sum of e over S — for a sampled row the very value the draw was made
+ *   against, for a greedy row the same reduction over the whole row.
+ *       lp_i = (z_i - m) - logf(Z_S)   for i in S,   -inf outside S
+ *   logprobs[r] = lp of ids[r], always finite (a greedy row: -logf(Z_S)).  top_ids[r, :top_k]: the first top_k indices
+ *   in the order (larger z, then lower index) — hx_argmax_rows' order — each with its lp: -inf when it lies outside S,
+ *   but named all the same; entries past n: id -1, -inf.
+ *   Scored and degenerate (a NaN in the row, or a largest z that is not finite): the id as in hx_sample_rows, logprobs[r]
+ *   NaN, top_ids -1, top_logprobs NaN.
+ * Errors: hx_sample_rows_constrained's rules; top_k outside 0..20: HX_ERR_SHAPE; logprobs NULL, or top_ids / top_logprobs
+ * NULL with top_k > 0: HX_ERR_NULL — nothing is launched. */
+int hx_sample_rows_logprobs(int64_t* ids, float* cut_out, float* u_out, const void* logits, int64_t rows, int64_t n,
+                            int64_t ld, const int32_t* hist_ids, const int32_t* hist_counts, const int32_t* cu_hist,
+                            int64_t total, const float* penalties, const int32_t* bias_ids, const float* bias_values,
+                            const int32_t* cu_bias, int64_t bias_total, const void* sample_params, float* logprobs,
+                            int32_t* top_ids, float* top_logprobs, int top_k, const int32_t* want, int dtype,
+                            hx_stream stream);
 /* The same product for M <= 32 with the activations held in REGISTERS (csrc/gemm_xreg.hip): a
  * workgroup spans the whole K of its split, so K <= 4096 needs ONE slab (no K split) and K = 11008
  * three instead of eleven — the fp32 slab traffic of a decode layer drops from 25 MB to 6.5 MB.
