@@ -79,6 +79,18 @@ inline Launcher<P...> launcher(void (*kernel)(P...), dim3 grid, dim3 block, size
   return Launcher<P...>{kernel, grid, block, lds, stream};
 }
 
+// A launch with `lds` bytes of dynamic LDS -> HX_OK or HX_ERR_HIP.  Above 48 KiB a launch needs the kernel's limit
+// raised first: on the kernel that is launched, before every such launch (a recorded one too).
+template <typename... P, typename... A>
+inline int launch_lds(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, const A&... args) {
+  if (lds > 48 * 1024) {
+    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return hip_rc(e);
+  }
+  launcher(kernel, grid, block, lds, stream)(args...);
+  return check_launch();
+}
+
 // CUs of the current device, asked once.  Without a device 256, the MI355X's own count: the planning entries
 // (workspace sizes, split counts, "supported") answer on a machine that has none.
 inline int n_cus() {
@@ -174,6 +186,16 @@ __device__ __forceinline__ bool arg_better(float a, int ia, float b, int ib) {
   if (an != bn) return an;
   if (!an && a != b) return a > b;
   return ia < ib;
+}
+// the first of a wave's 64 (v, i) in that order, in every lane.  Used where it leaves the kernel's code as it was
+// (logprobs.hip); the argmax, penalty and sampling kernels keep the loop written out (profiles/token_choice_refactor.md).
+__device__ __forceinline__ void wave_first(float& v, int& i) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const float ov = __shfl_xor(v, off, 64);
+    const int oi = __shfl_xor(i, off, 64);
+    if (arg_better(ov, oi, v, i)) { v = ov; i = oi; }
+  }
 }
 
 // A logit under (frequency, presence, repetition) with count c, in the reference's order, every operation rounded to

@@ -73,12 +73,7 @@ __device__ __forceinline__ void lp_candidate_of(const u16* src, int n, bool vec,
   } else {
     for (int i = owner + LP_THREADS * lane; i < n; i += 64 * LP_THREADS) take(i);
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float ov = __shfl_xor(bv, off, 64);
-    const int oi = __shfl_xor(bi, off, 64);
-    if (arg_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-  }
+  wave_first(bv, bi);
   cv = bv;
   ci = bi;
 }
@@ -86,12 +81,7 @@ __device__ __forceinline__ void lp_candidate_of(const u16* src, int n, bool vec,
 // the first of all threads' (v, i), in every thread.  part: 16 floats + 16 ints of LDS, not in use by a reduction that
 // other waves may still be reading (the callers alternate two).
 __device__ __forceinline__ void lp_block_first(float& v, int& i, float* part_v, int* part_i) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float ov = __shfl_xor(v, off, 64);
-    const int oi = __shfl_xor(i, off, 64);
-    if (arg_better(ov, oi, v, i)) { v = ov; i = oi; }
-  }
+  wave_first(v, i);
   if ((threadIdx.x & 63) == 0) { part_v[threadIdx.x >> 6] = v; part_i[threadIdx.x >> 6] = i; }
   __syncthreads();
   v = part_v[0];
@@ -121,27 +111,7 @@ __global__ __launch_bounds__(LP_THREADS) void logprob_rows_kernel(int64_t* __res
   const u16* src = p;
   bool vec = gvec;
   if (LDS) {
-    if (gvec) {
-      const int nvec = n >> 3;
-      // four independent 16-byte loads per thread in flight, like argmax_rows_kernel: one memory round trip for a
-      // 32064-wide row
-      for (int i0 = threadIdx.x; i0 < nvec; i0 += 4 * LP_THREADS) {
-        u16x8 v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const u16x8*>(p + (int64_t)min(i0 + LP_THREADS * u, nvec - 1) * 8);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int i = i0 + LP_THREADS * u;
-          if (i < nvec) *reinterpret_cast<u16x8*>(staged + i * 8) = v[u];
-        }
-      }
-      for (int i = nvec * 8 + threadIdx.x; i < n; i += LP_THREADS) staged[i] = p[i];
-    } else {
-      for (int i = threadIdx.x; i < n; i += LP_THREADS) staged[i] = p[i];
-    }
-    __syncthreads();
-    src = staged;
-    vec = true;
+#include "logprobs_stage.inc"
   }
 
   // round 0: the greedy id
@@ -168,30 +138,7 @@ __global__ __launch_bounds__(LP_THREADS) void logprob_rows_kernel(int64_t* __res
     ids[row] = bi;
     logprobs[row] = (best - best) - log_sum;
   }
-  float wv = best;
-  int wi = bi;
-  for (int r = 0; r < top_k; ++r) {
-    if (r > 0) {
-      // the previous winner's owner needs its next candidate: its wave finds it together (alone, the owner would walk
-      // its 32 elements one after the other while 1023 threads wait: 7 us a round, measured)
-      const int nvec8 = (n >> 3) * 8;
-      const int owner = vec ? (wi < nvec8 ? (wi >> 3) & (LP_THREADS - 1) : wi - nvec8) : wi & (LP_THREADS - 1);
-      if (wi != LP_NONE && (owner >> 6) == (int)(threadIdx.x >> 6)) {
-        float nv;
-        int ni;
-        lp_candidate_of<T>(src, n, vec, owner, wv, wi, nv, ni);
-        if ((int)threadIdx.x == owner) { cv = nv; ci = ni; }
-      }
-      wv = cv;
-      wi = ci;
-      lp_block_first(wv, wi, part_v[r & 1], part_i[r & 1]);
-    }
-    if (threadIdx.x == 0) {
-      const bool none = wi == LP_NONE;                                    // K > n: the row is used up
-      top_ids[row * top_k + r] = none ? -1 : wi;
-      top_logprobs[row * top_k + r] = none ? -INFINITY : (wv - best) - log_sum;
-    }
-  }
+#include "logprobs_rounds.inc"
 }
 
 // ---- hx_token_logprob_rows: the score of a GIVEN id per row (prompt log-probabilities) ------------------------------
@@ -254,26 +201,7 @@ __global__ __launch_bounds__(LP_THREADS) void token_logprob_rows_kernel(float* _
   const u16* src = p;
   bool vec = gvec;
   if (LDS) {
-    // (logprob_rows_kernel's staging loop, word for word: as a shared function it changes that kernel's code)
-    if (gvec) {
-      const int nvec = n >> 3;
-      for (int i0 = threadIdx.x; i0 < nvec; i0 += 4 * LP_THREADS) {
-        u16x8 v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const u16x8*>(p + (int64_t)min(i0 + LP_THREADS * u, nvec - 1) * 8);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int i = i0 + LP_THREADS * u;
-          if (i < nvec) *reinterpret_cast<u16x8*>(staged + i * 8) = v[u];
-        }
-      }
-      for (int i = nvec * 8 + threadIdx.x; i < n; i += LP_THREADS) staged[i] = p[i];
-    } else {
-      for (int i = threadIdx.x; i < n; i += LP_THREADS) staged[i] = p[i];
-    }
-    __syncthreads();
-    src = staged;
-    vec = true;
+#include "logprobs_stage.inc"
   }
 
   float m, s = 0.f;
@@ -367,53 +295,24 @@ __global__ __launch_bounds__(LP_THREADS) void token_logprob_rows_kernel(float* _
   }
   if (top_k == 0) return;
 
-  // the rounds (logprob_rows_kernel's loop, word for word: as a shared function it changes that kernel's code)
   const float best = m;
-  float wv = best;
-  int wi = bi;
-  for (int r = 0; r < top_k; ++r) {
-    if (r > 0) {
-      const int nvec8 = (n >> 3) * 8;
-      const int owner = vec ? (wi < nvec8 ? (wi >> 3) & (LP_THREADS - 1) : wi - nvec8) : wi & (LP_THREADS - 1);
-      if (wi != LP_NONE && (owner >> 6) == (int)(threadIdx.x >> 6)) {
-        float nv;
-        int ni;
-        lp_candidate_of<T>(src, n, vec, owner, wv, wi, nv, ni);
-        if ((int)threadIdx.x == owner) { cv = nv; ci = ni; }
-      }
-      wv = cv;
-      wi = ci;
-      lp_block_first(wv, wi, part_v[r & 1], part_i[r & 1]);
-    }
-    if (threadIdx.x == 0) {
-      const bool none = wi == LP_NONE;                                    // K > n: the row is used up
-      top_ids[row * top_k + r] = none ? -1 : wi;
-      top_logprobs[row * top_k + r] = none ? -INFINITY : (wv - best) - log_sum;
-    }
-  }
+#include "logprobs_rounds.inc"
 }
 
 }  // namespace hx
 
 using namespace hx;
 
+// bytes of LDS for a staged row of n elements
+static size_t lp_row_bytes(int64_t n) { return (size_t)((n + 7) / 8 * 8) * sizeof(u16); }
+
 template <typename T>
 static int launch_logprob_rows(int64_t* ids, float* logprobs, int32_t* top_ids, float* top_logprobs, const void* logits,
                                int64_t rows, int64_t n, int64_t ld, int top_k, hipStream_t s) {
-  if (n <= LP_LDS_ELEMS) {
-    const size_t lds = (size_t)((n + 7) / 8 * 8) * sizeof(u16);
-    if (lds > 48 * 1024) {
-      hipError_t e = hipFuncSetAttribute((const void*)logprob_rows_kernel<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)lds);
-      if (e != hipSuccess) return hip_rc(e);
-    }
-    hx::launcher(logprob_rows_kernel<T, true>, (unsigned)rows, LP_THREADS, lds, s)(ids, logprobs, top_ids, top_logprobs,
-                                                                                 (const u16*)logits, (int32_t)n, ld, top_k);
-  } else {
-    hx::launcher(logprob_rows_kernel<T, false>, (unsigned)rows, LP_THREADS, 0, s)(ids, logprobs, top_ids, top_logprobs,
-                                                                                (const u16*)logits, (int32_t)n, ld, top_k);
-  }
-  return check_launch();
+  const bool staged = n <= LP_LDS_ELEMS;
+  return launch_lds(staged ? logprob_rows_kernel<T, true> : logprob_rows_kernel<T, false>, (unsigned)rows, LP_THREADS,
+                    staged ? lp_row_bytes(n) : 0, s, ids, logprobs, top_ids, top_logprobs, (const u16*)logits, (int32_t)n, ld,
+                    top_k);
 }
 
 extern "C" int hx_logprob_rows(int64_t* ids, float* logprobs, int32_t* top_ids, float* top_logprobs, const void* logits,
@@ -422,9 +321,8 @@ extern "C" int hx_logprob_rows(int64_t* ids, float* logprobs, int32_t* top_ids, 
   if (top_k < 0 || top_k > LP_MAX_K) return HX_ERR_SHAPE;
   if (dtype != HX_F16 && dtype != HX_BF16) return HX_ERR_DTYPE;
   if (!ids || !logprobs || !logits || (top_k > 0 && (!top_ids || !top_logprobs))) return HX_ERR_NULL;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == HX_F16) return launch_logprob_rows<F16>(ids, logprobs, top_ids, top_logprobs, logits, rows, n, ld, top_k, s);
-  return launch_logprob_rows<BF16>(ids, logprobs, top_ids, top_logprobs, logits, rows, n, ld, top_k, s);
+  return (dtype == HX_F16 ? launch_logprob_rows<F16> : launch_logprob_rows<BF16>)(ids, logprobs, top_ids, top_logprobs, logits,
+                                                                                   rows, n, ld, top_k, (hipStream_t)stream);
 }
 
 // form: 0 — the form kept per top_k class (profiles/token_logprob_rows.md); 1 — the pass straight from global memory;
@@ -433,20 +331,10 @@ template <typename T>
 static int launch_token_logprob_rows(float* logprobs, int32_t* ranks, int32_t* top_ids, float* top_logprobs, const void* logits,
                                      const int32_t* targets, int64_t rows, int64_t n, int64_t ld, int top_k, int form,
                                      hipStream_t s) {
-  if (n <= LP_LDS_ELEMS && (form == 2 || (form == 0 && top_k > 0))) {
-    const size_t lds = (size_t)((n + 7) / 8 * 8) * sizeof(u16);
-    if (lds > 48 * 1024) {
-      hipError_t e = hipFuncSetAttribute((const void*)token_logprob_rows_kernel<T, true>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return hip_rc(e);
-    }
-    hx::launcher(token_logprob_rows_kernel<T, true>, (unsigned)rows, LP_THREADS, lds, s)(
-        logprobs, ranks, top_ids, top_logprobs, (const u16*)logits, targets, (int32_t)n, ld, top_k);
-  } else {
-    hx::launcher(token_logprob_rows_kernel<T, false>, (unsigned)rows, LP_THREADS, 0, s)(
-        logprobs, ranks, top_ids, top_logprobs, (const u16*)logits, targets, (int32_t)n, ld, top_k);
-  }
-  return check_launch();
+  const bool staged = n <= LP_LDS_ELEMS && (form == 2 || (form == 0 && top_k > 0));
+  return launch_lds(staged ? token_logprob_rows_kernel<T, true> : token_logprob_rows_kernel<T, false>, (unsigned)rows,
+                    LP_THREADS, staged ? lp_row_bytes(n) : 0, s, logprobs, ranks, top_ids, top_logprobs, (const u16*)logits,
+                    targets, (int32_t)n, ld, top_k);
 }
 
 extern "C" int hx_token_logprob_rows_ex(float* logprobs, int32_t* ranks, int32_t* top_ids, float* top_logprobs,
@@ -456,10 +344,8 @@ extern "C" int hx_token_logprob_rows_ex(float* logprobs, int32_t* ranks, int32_t
   if (top_k < 0 || top_k > LP_MAX_K || form < 0 || form > 2) return HX_ERR_SHAPE;
   if (dtype != HX_F16 && dtype != HX_BF16) return HX_ERR_DTYPE;
   if (!logprobs || !ranks || !logits || !targets || (top_k > 0 && (!top_ids || !top_logprobs))) return HX_ERR_NULL;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == HX_F16)
-    return launch_token_logprob_rows<F16>(logprobs, ranks, top_ids, top_logprobs, logits, targets, rows, n, ld, top_k, form, s);
-  return launch_token_logprob_rows<BF16>(logprobs, ranks, top_ids, top_logprobs, logits, targets, rows, n, ld, top_k, form, s);
+  return (dtype == HX_F16 ? launch_token_logprob_rows<F16> : launch_token_logprob_rows<BF16>)(
+      logprobs, ranks, top_ids, top_logprobs, logits, targets, rows, n, ld, top_k, form, (hipStream_t)stream);
 }
 
 extern "C" int hx_token_logprob_rows(float* logprobs, int32_t* ranks, int32_t* top_ids, float* top_logprobs,

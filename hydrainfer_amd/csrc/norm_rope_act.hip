@@ -395,7 +395,7 @@ __global__ __launch_bounds__(256) void decode_step_head_kernel(const StepHeadPar
 // (hydrainfer/model/llama.py:99-104, torch.argmax).  torch's rule: the largest value, NaN counts as
 // larger than everything, ties go to the smallest index (hx::arg_better).
 template <typename T>
-__global__ __launch_bounds__(1024) void argmax_rows_kernel(int64_t* __restrict__ out,
+__global__ __launch_bounds__(1024) void argmax_rows_kernel(int64_t* __restrict__ ids,
                                                            const typename T::storage* __restrict__ logits,
                                                            int32_t n, int64_t ld) {
   __shared__ float s_v[16];
@@ -435,19 +435,7 @@ __global__ __launch_bounds__(1024) void argmax_rows_kernel(int64_t* __restrict__
       if (arg_better(f, i, best, bi)) { best = f; bi = i; }
     }
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float ov = __shfl_xor(best, off, 64);
-    const int oi = __shfl_xor(bi, off, 64);
-    if (arg_better(ov, oi, best, bi)) { best = ov; bi = oi; }
-  }
-  if ((threadIdx.x & 63) == 0) { s_v[threadIdx.x >> 6] = best; s_i[threadIdx.x >> 6] = bi; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int k = 1; k < 16; ++k)
-      if (arg_better(s_v[k], s_i[k], best, bi)) { best = s_v[k]; bi = s_i[k]; }
-    out[row] = bi;
-  }
+#include "argmax_finish.inc"
 }
 
 // ---------------------------------------------------------------------------

@@ -96,19 +96,7 @@ __global__ __launch_bounds__(PEN_THREADS) void penalized_argmax_rows_kernel(
       if (!taken && arg_better(x, i, best, bi)) { best = x; bi = i; }
     }
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float ov = __shfl_xor(best, off, 64);
-    const int oi = __shfl_xor(bi, off, 64);
-    if (arg_better(ov, oi, best, bi)) { best = ov; bi = oi; }
-  }
-  if ((threadIdx.x & 63) == 0) { s_v[threadIdx.x >> 6] = best; s_i[threadIdx.x >> 6] = bi; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int k = 1; k < PEN_THREADS / 64; ++k)
-      if (arg_better(s_v[k], s_i[k], best, bi)) { best = s_v[k]; bi = s_i[k]; }
-    ids[row] = bi;
-  }
+#include "argmax_finish.inc"
 }
 
 }  // namespace hx

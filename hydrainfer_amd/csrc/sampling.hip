@@ -134,85 +134,68 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_rows_logprobs_kernel(
 
 using namespace hx;
 
-// One workgroup per row; a row wider than 12288 elements needs more dynamic LDS than a launch gets without the attribute.
-template <typename T>
-static int launch_sample_rows(bool constrained, int64_t* ids, float* cut_out, float* u_out, const void* logits, int64_t rows,
-                              int64_t n, int64_t ld, const int32_t* hist_ids, const int32_t* hist_counts,
-                              const int32_t* cu_hist, int64_t total, const float* penalties, const int32_t* bias_ids,
-                              const float* bias_values, const int32_t* cu_bias, int64_t bias_total, const void* sample_params,
-                              hipStream_t s) {
-  const size_t lds = (size_t)((n + 7) / 8 * 8) * sizeof(float);
-  if (lds > 48 * 1024) {
-    const void* kernel = constrained ? (const void*)sample_rows_constrained_kernel<T> : (const void*)sample_rows_kernel<T>;
-    hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return hip_rc(e);
-  }
-  if (constrained)
-    hx::launcher(sample_rows_constrained_kernel<T>, (unsigned)rows, SMP_THREADS, lds, s)(
-        ids, cut_out, u_out, (const u16*)logits, (int32_t)n, ld, hist_ids, hist_counts, cu_hist, (int32_t)total, penalties,
-        (const uint32_t*)sample_params, bias_ids, bias_values, cu_bias, (int32_t)bias_total);
-  else
-    hx::launcher(sample_rows_kernel<T>, (unsigned)rows, SMP_THREADS, lds, s)(
-        ids, cut_out, u_out, (const u16*)logits, (int32_t)n, ld, hist_ids, hist_counts, cu_hist, (int32_t)total, penalties,
-        (const uint32_t*)sample_params);
-  return check_launch();
-}
+// What the three entries are called with.  hx_sample_rows comes with no bias table (bias_total 0); only
+// hx_sample_rows_logprobs fills the score fields.
+struct SampleArgs {
+  int64_t* ids; float* cut_out; float* u_out;
+  const void* logits; int64_t rows, n, ld;
+  const int32_t* hist_ids; const int32_t* hist_counts; const int32_t* cu_hist; int64_t total; const float* penalties;
+  const int32_t* bias_ids; const float* bias_values; const int32_t* cu_bias; int64_t bias_total;
+  const void* sample_params;
+  float* logprobs; int32_t* top_ids; float* top_logprobs; int top_k; const int32_t* want;
+  int dtype; hipStream_t stream;
+};
+enum SampleKernel { SMP_PLAIN, SMP_CONSTRAINED, SMP_SCORED };
 
-template <typename T>
-static int launch_sample_rows_logprobs(int64_t* ids, float* cut_out, float* u_out, const void* logits, int64_t rows, int64_t n,
-                                       int64_t ld, const int32_t* hist_ids, const int32_t* hist_counts, const int32_t* cu_hist,
-                                       int64_t total, const float* penalties, const int32_t* bias_ids,
-                                       const float* bias_values, const int32_t* cu_bias, int64_t bias_total,
-                                       const void* sample_params, float* logprobs, int32_t* top_ids, float* top_logprobs,
-                                       int top_k, const int32_t* want, hipStream_t s) {
-  const size_t lds = (size_t)((n + 7) / 8 * 8) * sizeof(float);
-  if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)sample_rows_logprobs_kernel<T>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return hip_rc(e);
-  }
-  hx::launcher(sample_rows_logprobs_kernel<T>, (unsigned)rows, SMP_THREADS, lds, s)(
-      ids, cut_out, u_out, (const u16*)logits, (int32_t)n, ld, hist_ids, hist_counts, cu_hist, (int32_t)total, penalties,
-      (const uint32_t*)sample_params, bias_ids, bias_values, cu_bias, (int32_t)bias_total, logprobs, top_ids, top_logprobs,
-      (int32_t)top_k, want);
-  return check_launch();
-}
-
-// hx_sample_rows_constrained's argument checks, which all three entries share
-static int sample_rows_check(const int64_t* ids, const void* logits, int64_t rows, int64_t n, int64_t ld,
-                             const int32_t* hist_ids, const int32_t* hist_counts, const int32_t* cu_hist, int64_t total,
-                             const float* penalties, const int32_t* bias_ids, const float* bias_values,
-                             const int32_t* cu_bias, int64_t bias_total, const void* sample_params, int dtype) {
-  if (rows < 1 || n < 1 || ld < n || n > SAMPLE_MAX_N || rows > 0x7fffffff || total < 0 || total > 0x7fffffff ||
-      bias_total < 0 || bias_total > 0x7fffffff)
+// The argument checks: top_k's range in front of everything for the scored entry, then shape, dtype, null pointers.
+static int sample_rows_check(SampleKernel which, const SampleArgs& a) {
+  if (which == SMP_SCORED && (a.top_k < 0 || a.top_k > 20)) return HX_ERR_SHAPE;
+  if (a.rows < 1 || a.n < 1 || a.ld < a.n || a.n > SAMPLE_MAX_N || a.rows > 0x7fffffff || a.total < 0 ||
+      a.total > 0x7fffffff || a.bias_total < 0 || a.bias_total > 0x7fffffff)
     return HX_ERR_SHAPE;
-  if (dtype != HX_F16 && dtype != HX_BF16) return HX_ERR_DTYPE;
-  if (!ids || !logits || !sample_params || (total > 0 && (!hist_ids || !hist_counts || !cu_hist || !penalties)) ||
-      (bias_total > 0 && (!bias_ids || !bias_values || !cu_bias)))
+  if (a.dtype != HX_F16 && a.dtype != HX_BF16) return HX_ERR_DTYPE;
+  if (!a.ids || !a.logits || !a.sample_params ||
+      (a.total > 0 && (!a.hist_ids || !a.hist_counts || !a.cu_hist || !a.penalties)) ||
+      (a.bias_total > 0 && (!a.bias_ids || !a.bias_values || !a.cu_bias)))
     return HX_ERR_NULL;
+  if (which == SMP_SCORED && (!a.logprobs || (a.top_k > 0 && (!a.top_ids || !a.top_logprobs)))) return HX_ERR_NULL;
   return HX_OK;
 }
 
-// Both entries: the argument checks (hx_sample_rows comes with no bias table: bias_total 0), then the launch by dtype.
-static int sample_rows_entry(bool constrained, int64_t* ids, float* cut_out, float* u_out, const void* logits, int64_t rows,
-                             int64_t n, int64_t ld, const int32_t* hist_ids, const int32_t* hist_counts,
-                             const int32_t* cu_hist, int64_t total, const float* penalties, const int32_t* bias_ids,
-                             const float* bias_values, const int32_t* cu_bias, int64_t bias_total, const void* sample_params,
-                             int dtype, hx_stream stream) {
-  const int rc = sample_rows_check(ids, logits, rows, n, ld, hist_ids, hist_counts, cu_hist, total, penalties, bias_ids,
-                                   bias_values, cu_bias, bias_total, sample_params, dtype);
+// One workgroup per row, the row as fp32 in dynamic LDS (wider than 12288 elements: more than a launch gets unasked).
+template <typename T>
+static int launch_sample_rows(SampleKernel which, const SampleArgs& a) {
+  const size_t lds = (size_t)((a.n + 7) / 8 * 8) * sizeof(float);
+  const unsigned rows = (unsigned)a.rows;
+  const u16* logits = (const u16*)a.logits;
+  const uint32_t* params = (const uint32_t*)a.sample_params;
+  const int32_t n = (int32_t)a.n, total = (int32_t)a.total, bias_total = (int32_t)a.bias_total;
+  if (which == SMP_PLAIN)
+    return launch_lds(sample_rows_kernel<T>, rows, SMP_THREADS, lds, a.stream, a.ids, a.cut_out, a.u_out, logits, n, a.ld,
+                      a.hist_ids, a.hist_counts, a.cu_hist, total, a.penalties, params);
+  if (which == SMP_CONSTRAINED)
+    return launch_lds(sample_rows_constrained_kernel<T>, rows, SMP_THREADS, lds, a.stream, a.ids, a.cut_out, a.u_out, logits,
+                      n, a.ld, a.hist_ids, a.hist_counts, a.cu_hist, total, a.penalties, params, a.bias_ids, a.bias_values,
+                      a.cu_bias, bias_total);
+  return launch_lds(sample_rows_logprobs_kernel<T>, rows, SMP_THREADS, lds, a.stream, a.ids, a.cut_out, a.u_out, logits, n,
+                    a.ld, a.hist_ids, a.hist_counts, a.cu_hist, total, a.penalties, params, a.bias_ids, a.bias_values,
+                    a.cu_bias, bias_total, a.logprobs, a.top_ids, a.top_logprobs, (int32_t)a.top_k, a.want);
+}
+
+// All three entries: the argument checks, then the launch by dtype.
+static int sample_rows(SampleKernel which, const SampleArgs& a) {
+  const int rc = sample_rows_check(which, a);
   if (rc != HX_OK) return rc;
-  return (dtype == HX_F16 ? launch_sample_rows<F16> : launch_sample_rows<BF16>)(
-      constrained, ids, cut_out, u_out, logits, rows, n, ld, hist_ids, hist_counts, cu_hist, total, penalties, bias_ids,
-      bias_values, cu_bias, bias_total, sample_params, (hipStream_t)stream);
+  return a.dtype == HX_F16 ? launch_sample_rows<F16>(which, a) : launch_sample_rows<BF16>(which, a);
 }
 
 extern "C" int hx_sample_rows(int64_t* ids, float* cut_out, float* u_out, const void* logits, int64_t rows, int64_t n,
                               int64_t ld, const int32_t* hist_ids, const int32_t* hist_counts, const int32_t* cu_hist,
                               int64_t total, const float* penalties, const void* sample_params, int dtype,
                               hx_stream stream) {
-  return sample_rows_entry(false, ids, cut_out, u_out, logits, rows, n, ld, hist_ids, hist_counts, cu_hist, total, penalties,
-                           nullptr, nullptr, nullptr, 0, sample_params, dtype, stream);
+  return sample_rows(SMP_PLAIN, {ids, cut_out, u_out, logits, rows, n, ld, hist_ids, hist_counts, cu_hist, total, penalties,
+                                 nullptr, nullptr, nullptr, 0, sample_params, nullptr, nullptr, nullptr, 0, nullptr, dtype,
+                                 (hipStream_t)stream});
 }
 
 extern "C" int hx_sample_rows_constrained(int64_t* ids, float* cut_out, float* u_out, const void* logits, int64_t rows,
@@ -220,8 +203,9 @@ extern "C" int hx_sample_rows_constrained(int64_t* ids, float* cut_out, float* u
                                           const int32_t* cu_hist, int64_t total, const float* penalties,
                                           const int32_t* bias_ids, const float* bias_values, const int32_t* cu_bias,
                                           int64_t bias_total, const void* sample_params, int dtype, hx_stream stream) {
-  return sample_rows_entry(true, ids, cut_out, u_out, logits, rows, n, ld, hist_ids, hist_counts, cu_hist, total, penalties,
-                           bias_ids, bias_values, cu_bias, bias_total, sample_params, dtype, stream);
+  return sample_rows(SMP_CONSTRAINED, {ids, cut_out, u_out, logits, rows, n, ld, hist_ids, hist_counts, cu_hist, total,
+                                       penalties, bias_ids, bias_values, cu_bias, bias_total, sample_params, nullptr, nullptr,
+                                       nullptr, 0, nullptr, dtype, (hipStream_t)stream});
 }
 
 extern "C" int hx_sample_rows_logprobs(int64_t* ids, float* cut_out, float* u_out, const void* logits, int64_t rows, int64_t n,
@@ -230,12 +214,7 @@ extern "C" int hx_sample_rows_logprobs(int64_t* ids, float* cut_out, float* u_ou
                                        const int32_t* bias_ids, const float* bias_values, const int32_t* cu_bias,
                                        int64_t bias_total, const void* sample_params, float* logprobs, int32_t* top_ids,
                                        float* top_logprobs, int top_k, const int32_t* want, int dtype, hx_stream stream) {
-  if (top_k < 0 || top_k > 20) return HX_ERR_SHAPE;
-  const int rc = sample_rows_check(ids, logits, rows, n, ld, hist_ids, hist_counts, cu_hist, total, penalties, bias_ids,
-                                   bias_values, cu_bias, bias_total, sample_params, dtype);
-  if (rc != HX_OK) return rc;
-  if (!logprobs || (top_k > 0 && (!top_ids || !top_logprobs))) return HX_ERR_NULL;
-  return (dtype == HX_F16 ? launch_sample_rows_logprobs<F16> : launch_sample_rows_logprobs<BF16>)(
-      ids, cut_out, u_out, logits, rows, n, ld, hist_ids, hist_counts, cu_hist, total, penalties, bias_ids, bias_values,
-      cu_bias, bias_total, sample_params, logprobs, top_ids, top_logprobs, top_k, want, (hipStream_t)stream);
+  return sample_rows(SMP_SCORED, {ids, cut_out, u_out, logits, rows, n, ld, hist_ids, hist_counts, cu_hist, total, penalties,
+                                  bias_ids, bias_values, cu_bias, bias_total, sample_params, logprobs, top_ids, top_logprobs,
+                                  top_k, want, dtype, (hipStream_t)stream});
 }

@@ -352,25 +352,46 @@ class BatchFillExecutor:
                     p.append_token_id(token, last)
         batch.step()
 
+    @staticmethod
+    def _step_rows(inputs, logits):
+        """The row geometry of an eager step -> (sel, decode, n_rows).  logits: None, or the ready logits of the step's
+        sampling rows, one row per entry of inputs.selected_token_ids (a step that also scores prompts:
+        _execute_scoring) — the forward is not run again, the same kernels follow.  decode: the logits are those of a
+        decode batch's own forward, which keeps every input row, the sampling rows at `sel`.  n_rows: the logits' rows."""
+        sel, decode = inputs.selected_token_ids, inputs.all_sequences_decode and logits is None
+        return sel, decode, inputs.input_ids.shape[0] if decode else len(sel)
+
+    @staticmethod
+    def _raw_scores(logits, top_k: int):
+        """The side launch for requests that asked for raw log-probabilities (hx_logprob_rows) -> its packed buffer."""
+        return logprob_rows_packed(logprob_rows(logits, top_k)[0], top_k)
+
+    @staticmethod
+    def _to_host(packed, n_rows: int, top_k: int):
+        """A packed buffer -> (ids, logprobs, top_ids, top_logprobs) as host lists: ONE device-to-host copy, a sync."""
+        return [t.tolist() for t in logprob_rows_views(packed.cpu(), n_rows, top_k)]
+
+    @staticmethod
+    def _pick(geometry, sampled, scores=None):
+        """(sampled, scores) per logits row -> per sampling row."""
+        sel, decode, n_rows = geometry
+        if decode and n_rows != len(sel):
+            sampled = [sampled[j] for j in sel]
+            scores = scores and tuple([col[j] for j in sel] for col in scores)
+        return sampled, scores
+
     def _sample_with_logprobs(self, inputs, params, top_k: int, logits=None):
         """The eager step of a batch in which some request asked for log-probabilities: the same logits, ids by the same
-        rule, and the scores beside them — one launch (hx_logprob_rows), one packed buffer, ONE device-to-host copy.
-        logits (here and in _sample): None, or the ready logits of the step's sampling rows, one row per
-        entry of inputs.selected_token_ids (a step that also scores prompts: _execute_scoring) — the forward is not run
-        again, the same kernels follow."""
+        rule, and the scores beside them — one launch (hx_logprob_rows), one packed buffer, ONE device-to-host copy:
+        the step's only device sync."""
+        geometry = self._step_rows(inputs, logits)
         if logits is None:
             ids = self.language_model.forward_logprobs(inputs.input_ids, inputs.image_features, inputs.position_ids,
                                                        params, top_k)[0]
         else:
             ids = logprob_rows(logits, top_k)[0]
-        rows = ids.shape[0]
-        host = logprob_rows_packed(ids, top_k).cpu()                                   # the step's only device sync
-        ids, lp, top_ids, top_lp = logprob_rows_views(host, rows, top_k)
-        sampled, scores = ids.tolist(), (lp.tolist(), top_ids.tolist(), top_lp.tolist())
-        if inputs.all_sequences_decode and rows != len(inputs.selected_token_ids):
-            sel = inputs.selected_token_ids
-            sampled, scores = [sampled[j] for j in sel], tuple([col[j] for j in sel] for col in scores)
-        return sampled, scores
+        sampled, *scores = self._to_host(logprob_rows_packed(ids, top_k), geometry[2], top_k)
+        return self._pick(geometry, sampled, scores)
 
     def _sample(self, mode: str, batch: BatchRequest, inputs, params, top_k: Optional[int], logits=None):
         """The eager step of a batch that does not end in the plain argmax -> (sampled, scores).  Mode "logprobs" is
@@ -385,8 +406,7 @@ class BatchFillExecutor:
         if mode == "logprobs":
             return self._sample_with_logprobs(inputs, params, top_k, logits)
         take, packer, forward, kernel = SAMPLING_MODES[mode]
-        sel, decode = inputs.selected_token_ids, inputs.all_sequences_decode and logits is None
-        n_rows = inputs.input_ids.shape[0] if decode else len(sel)        # the rows of the logits
+        geometry = sel, decode, n_rows = self._step_rows(inputs, logits)
         entries, _ = self._step_entries(batch, sel, decode, n_rows, take)
         tables = globals()[packer](entries).to_device(self.device)
         lm, scores = self.language_model, None
@@ -396,16 +416,12 @@ class BatchFillExecutor:
             if logits is None:
                 logits = lm.forward_logits(inputs.input_ids, inputs.image_features, inputs.position_ids, params)
             if top_k is not None:
-                packed = logprob_rows_packed(logprob_rows(logits, top_k)[0], top_k)
+                packed = self._raw_scores(logits, top_k)
             sampled = globals()[kernel](logits, *tables)
         sampled = sampled.tolist()                      # the step's only device sync beside the scores' copy
         if top_k is not None:
-            _, lp, top_ids, top_lp = logprob_rows_views(packed.cpu(), n_rows, top_k)
-            scores = (lp.tolist(), top_ids.tolist(), top_lp.tolist())
-        if decode and n_rows != len(sel):
-            sampled = [sampled[j] for j in sel]
-            scores = scores and tuple([col[j] for j in sel] for col in scores)
-        return sampled, scores
+            scores = self._to_host(packed, n_rows, top_k)[1:]
+        return self._pick(geometry, sampled, scores)
 
     @staticmethod
     def _step_entries(batch: BatchRequest, sel, decode: bool, n_rows: int, take: int):
@@ -435,8 +451,7 @@ class BatchFillExecutor:
         scores from hx_logprob_rows over the raw logits, exactly as in _sample: a mixed batch is two launches and two
         packed buffers."""
         rows = sampling_rows(batch)
-        sel, decode = inputs.selected_token_ids, inputs.all_sequences_decode and logits is None
-        n_rows = inputs.input_ids.shape[0] if decode else len(sel)        # the rows of the logits
+        geometry = sel, decode, n_rows = self._step_rows(inputs, logits)
         entries, at = self._step_entries(batch, sel, decode, n_rows, 4)
         step = pack_constrained_step(entries)
         size = step.buffer.size
@@ -466,17 +481,33 @@ class BatchFillExecutor:
             if logits is None:
                 logits = lm.forward_logits(inputs.input_ids, inputs.image_features, inputs.position_ids, params)
             if raw:
-                raw_packed = logprob_rows_packed(logprob_rows(logits, max(raw))[0], max(raw))
+                raw_packed = self._raw_scores(logits, max(raw))
             ids = sample_rows_logprobs(logits, *tables, top_k=top_k, want=want)[0]
-        ids, lp, top_ids, top_lp = logprob_rows_views(logprob_rows_packed(ids, top_k).cpu(), n_rows, top_k)
-        sampled, scores = ids.tolist(), [lp.tolist(), top_ids.tolist(), top_lp.tolist()]
+        sampled, *scores = self._to_host(logprob_rows_packed(ids, top_k), n_rows, top_k)
         if raw:
-            raw_scores = [t.tolist() for t in logprob_rows_views(raw_packed.cpu(), n_rows, max(raw))[1:]]
+            raw_scores = self._to_host(raw_packed, n_rows, max(raw))[1:]
             for row, (rcb, _) in zip(at, rows):
                 if rcb.sampling_params.logprobs and not asks_processed(rcb):
                     for col, raw_col in zip(scores, raw_scores):
                         col[row] = raw_col[row]
-        return [sampled[j] for j in at], tuple([col[j] for j in at] for col in scores)
+        return self._pick(geometry, sampled, scores)
+
+    def _choose(self, batch: BatchRequest, inputs, params, logits=None):
+        """What an eager step that samples runs -> (sampled, scores): the ONE place that decides it, for execute and for
+        _execute_scoring (logits: as in _step_rows).  scored_rows first, then step_mode, then the plain argmax — the
+        language model's own when it runs the forward, the step's only device sync."""
+        rows = sampling_rows(batch)
+        if scored_rows(rows):
+            return self._sample_scored(batch, inputs, params, logits)
+        mode, top_k = step_mode(rows)
+        if mode != "plain":
+            return self._sample(mode, batch, inputs, params, top_k, logits)
+        if logits is not None:
+            return argmax_rows(logits).tolist(), None
+        sampled = self.language_model.forward(inputs.input_ids, inputs.image_features, inputs.position_ids, params)
+        if inputs.all_sequences_decode and sampled.numel() != len(inputs.selected_token_ids):
+            sampled = sampled[inputs.selected_token_ids_tensor]
+        return sampled.tolist(), None
 
     def _execute_scoring(self, batch: BatchRequest, inputs) -> None:
         """The eager step of a batch in which some request scores its prompt (sampling_params.prompt_logprobs): ONE forward
@@ -493,14 +524,7 @@ class BatchFillExecutor:
         packed = token_logprob_rows_packed(token_logprob_rows(logits, plan.targets_tensor, k)[0], k)
         sampled = scores = None
         if inputs.selected_token_ids:
-            rows = logits.index_select(0, plan.sample_pos_tensor)
-            mode, top_k = step_mode(sampling_rows(batch))
-            if scored_rows(sampling_rows(batch)):
-                sampled, scores = self._sample_scored(batch, inputs, params, rows)
-            elif mode == "plain":
-                sampled = argmax_rows(rows).tolist()
-            else:
-                sampled, scores = self._sample(mode, batch, inputs, params, top_k, rows)
+            sampled, scores = self._choose(batch, inputs, params, logits.index_select(0, plan.sample_pos_tensor))
         lp, ranks, top_ids, top_lp = (t.tolist() for t in token_logprob_rows_views(packed.cpu(), len(plan.rows), k))
         for u, dst in enumerate(plan.dst):
             if dst is not None:
@@ -557,18 +581,7 @@ class BatchFillExecutor:
                 inputs.position_ids, params)
             batch.step()
             return
-        if scored_rows(sampling_rows(batch)):
-            self._deliver(batch, *self._sample_scored(batch, inputs, params))
-            return
-        mode, top_k = step_mode(sampling_rows(batch))
-        if mode != "plain":
-            self._deliver(batch, *self._sample(mode, batch, inputs, params, top_k))
-            return
-        sampled = self.language_model.forward(inputs.input_ids, inputs.image_features, inputs.position_ids,
-                                              params)
-        if inputs.all_sequences_decode and sampled.numel() != len(inputs.selected_token_ids):
-            sampled = sampled[inputs.selected_token_ids_tensor]
-        self._deliver(batch, sampled.tolist())          # the step's only device sync
+        self._deliver(batch, *self._choose(batch, inputs, params))
 
 
 class BatchImageEmbedExecutor:

@@ -133,3 +133,70 @@ def test_xreg_split_plan_is_stable():
     assert l.hx_gate_up_silu_xreg_supported(32, 11008, 4096) == 1 and l.hx_gate_up_silu_xreg_supported(32, 13824, 5120) == 1
     assert l.hx_norm_xreg_supported(32, 12288, 4096, 0) == 1 and l.hx_norm_xreg_supported(32, 4096, 11008, 0) == 0
     assert l.hx_fragment_major_elems(5, 4096) == 16 * 4096 and l.hx_fragment_major_elems(32, 64) == 32 * 64
+
+
+# The token-choice entries refuse bad arguments before any launch, so their status codes can be read without a GPU.
+# Per entry: a good argument list (the pointer 4096 is never dereferenced: no call below is good), the positions of
+# rows, n, ld, top_k and dtype in it, further (position, value) pairs that are a shape error, and the pointers that
+# must not be null.  HX_ERR_DTYPE -1, HX_ERR_SHAPE -2, HX_ERR_NULL -4.
+_P = 4096
+_SMP_MAX_N = 35840
+_BIG = 0x7ffffff1            # n of a logprob row past 0x7ffffff0
+_TOKEN_CHOICE_ENTRIES = {
+    #                 ids cut   u     logits rows n ld hist_ids counts cu total pen records dtype stream
+    "hx_sample_rows": ([_P, None, None, _P, 1, 8, 8, _P, _P, _P, 1, _P, _P, 1, None],
+                       dict(rows=4, n=5, ld=6, top_k=None, dtype=13),
+                       [(5, _SMP_MAX_N + 1), (10, -1), (10, 1 << 31)], [0, 3, 12, 7, 8, 9, 11]),
+    #                             ... pen bias_ids values cu bias_total records dtype stream
+    "hx_sample_rows_constrained": ([_P, None, None, _P, 1, 8, 8, _P, _P, _P, 1, _P, _P, _P, _P, 1, _P, 1, None],
+                                   dict(rows=4, n=5, ld=6, top_k=None, dtype=17),
+                                   [(5, _SMP_MAX_N + 1), (10, -1), (10, 1 << 31), (15, -1), (15, 1 << 31)],
+                                   [0, 3, 16, 7, 8, 9, 11, 12, 13, 14]),
+    #                          ... records logprobs top_ids top_logprobs top_k want dtype stream
+    "hx_sample_rows_logprobs": ([_P, None, None, _P, 1, 8, 8, _P, _P, _P, 1, _P, _P, _P, _P, 1, _P, _P, _P, _P, 2, None, 1, None],
+                                dict(rows=4, n=5, ld=6, top_k=20, dtype=22),
+                                [(5, _SMP_MAX_N + 1), (10, -1), (10, 1 << 31), (15, -1), (15, 1 << 31)],
+                                [0, 3, 16, 7, 8, 9, 11, 12, 13, 14, 17, 18, 19]),
+    #                  ids logprobs top_ids top_logprobs logits rows n ld top_k dtype stream
+    "hx_logprob_rows": ([_P, _P, _P, _P, _P, 2, 16, 16, 1, 1, None],
+                        dict(rows=5, n=6, ld=7, top_k=8, dtype=9), [(6, _BIG), (5, 1 << 31)], [0, 1, 2, 3, 4]),
+    #                           logprobs ranks top_ids top_logprobs logits targets rows n ld top_k dtype form stream
+    "hx_token_logprob_rows_ex": ([_P, _P, _P, _P, _P, _P, 2, 16, 16, 1, 1, 0, None],
+                                 dict(rows=6, n=7, ld=8, top_k=9, dtype=10),
+                                 [(7, _BIG), (6, 1 << 31), (11, -1), (11, 3)], [0, 1, 2, 3, 4, 5]),
+}
+
+
+def _token_choice_cases(name):
+    """[(what, arguments, status)] for one entry.  The statuses are what the library gave before the three sampling
+    entries shared one argument record and every entry one launch helper; they are written out here, not derived."""
+    ok, at, shape, pointers = _TOKEN_CHOICE_ENTRIES[name]
+
+    def call(*changes):
+        args = list(ok)
+        for pos, v in changes:
+            args[pos] = v
+            if pos == at["n"] and v > args[at["ld"]]:
+                args[at["ld"]] = v                  # a wide row, not a row stride below the width
+        return args
+    f32, rows0, null0 = (at["dtype"], 0), (at["rows"], 0), (pointers[0], None)
+    cases = [("rows 0", call(rows0), -2), ("n 0", call((at["n"], 0)), -2), ("ld < n", call((at["ld"], ok[at["n"]] - 1)), -2)]
+    cases += [(f"shape {pos} {v}", call((pos, v)), -2) for pos, v in shape]
+    if at["top_k"] is not None:
+        cases += [("top_k 21", call((at["top_k"], 21)), -2), ("top_k -1", call((at["top_k"], -1)), -2),
+                  ("top_k before dtype and null", call((at["top_k"], 21), f32, null0), -2)]
+    cases += [("fp32", call(f32), -1), ("shape before dtype and null", call(rows0, f32, null0), -2),
+              ("dtype before null", call(f32, null0), -1)]
+    cases += [(f"null {pos}", call((pos, None)), -4) for pos in pointers]
+    return cases
+
+
+def test_token_choice_entries_refuse_bad_arguments_with_the_same_status():
+    from hydrainfer_amd.sampling import SAMPLE_MAX_N
+    assert SAMPLE_MAX_N == _SMP_MAX_N
+    lib = _lib.lib()
+    for name in _TOKEN_CHOICE_ENTRIES:
+        cases = _token_choice_cases(name)
+        assert len(cases) >= 14
+        for what, args, status in cases:
+            assert getattr(lib, name)(*args) == status, (name, what)

@@ -88,7 +88,7 @@ def mixed_records(rows, n, seed0):
     return [kinds[r % 4] + ((1 << 33) + seed0 * 131 + r, r) for r in range(rows)]
 
 
-@pytest.mark.parametrize("n", [1, 7, 8, 1023, 1025, 32064, SAMPLE_MAX_N])
+@pytest.mark.parametrize("n", [1, 7, 8, 1023, 1025, 12288, 12296, 32064, SAMPLE_MAX_N])
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
 def test_equals_sample_rows_on_pre_biased_logits(dtype, n):
     """8 rows with 0, 1, 300 and 1500 entries (the last: the strided entry loop beyond 1024 threads), once with greedy /

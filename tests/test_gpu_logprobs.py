@@ -54,11 +54,12 @@ def _check(logits, top_k, ref, what):
     return max(e1, e2)
 
 
-@pytest.mark.parametrize("n", [1, 7, 8, 63, 1000, 32064, 40000, 100000])
+@pytest.mark.parametrize("n", [1, 7, 8, 63, 1000, 24576, 24584, 32064, 40000, 100000])
 @pytest.mark.parametrize("dt", sorted(DTYPES))
 def test_shape_grid(n, dt):
-    """n: below / at / past a 16-byte piece, one trip of the load loop (32064), two (40000), a row that does not fit in
-    LDS (100000); rows 1, 3, 33; K 0, 1, 5, 20 (K > n for the small ones); three layouts."""
+    """n: below / at / past a 16-byte piece, a staged row of exactly 48 KiB and the first past it, which needs the
+    kernel's dynamic LDS limit raised (24576, 24584), one trip of the load loop (32064), two (40000), a row that does
+    not fit in LDS (100000); rows 1, 3, 33; K 0, 1, 5, 20 (K > n for the small ones); three layouts."""
     worst = 0.0
     for rows in (1, 3, 33):
         x, views = _views(rows, n, DTYPES[dt], seed=1000 * rows + n)

@@ -93,7 +93,7 @@ def want_variants(rows):
     return [None, [-1] * rows, [(-1 if r % 2 else r) for r in range(rows)]]
 
 
-@pytest.mark.parametrize("n,rows", [(1, 1), (7, 2), (1000, 3), (1024, 4), (1025, 5), (4099, 5), (32064, 5), (SAMPLE_MAX_N, 3)])
+@pytest.mark.parametrize("n,rows", [(1, 1), (7, 2), (1000, 3), (1024, 4), (1025, 5), (4099, 5), (12288, 5), (12296, 5), (32064, 5), (SAMPLE_MAX_N, 3)])
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
 def test_parity_and_scores(dtype, n, rows):
     g = torch.Generator().manual_seed(4000 + n)

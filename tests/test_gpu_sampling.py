@@ -73,7 +73,7 @@ def test_u_is_philox(dtype):
     verify(logits, plain(recs), ids, cut, u)
 
 
-@pytest.mark.parametrize("n", [1, 7, 8, 1023, 1025, 32064, SAMPLE_MAX_N])
+@pytest.mark.parametrize("n", [1, 7, 8, 1023, 1025, 12288, 12296, 32064, SAMPLE_MAX_N])
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
 def test_parameter_grid(dtype, n):
     """72 rows of randn * 3 in one launch, each with its own (T, top_k, top_p, seed, offset)"""

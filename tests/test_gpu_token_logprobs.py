@@ -63,11 +63,12 @@ def _targets(rows, n, g):
     return t
 
 
-@pytest.mark.parametrize("n", [1, 7, 8, 9, 1023, 1025, 32064, 65536, 65537])
+@pytest.mark.parametrize("n", [1, 7, 8, 9, 1023, 1025, 24576, 24584, 32064, 65536, 65537])
 @pytest.mark.parametrize("dt", sorted(DTYPES))
 def test_shape_grid(n, dt):
-    """n: below / at / past a 16-byte piece, below / past one piece per thread, the vocabulary, the widest row that is
-    staged in LDS and the first that is not; rows 1, 3, 70; K 0, 1, 5, 20 (K > n for the small ones); three layouts;
+    """n: below / at / past a 16-byte piece, below / past one piece per thread, a staged row of exactly 48 KiB and the
+    first past it, which needs the kernel's dynamic LDS limit raised (24576, 24584), the vocabulary, the widest row that
+    is staged in LDS and the first that is not; rows 1, 3, 70; K 0, 1, 5, 20 (K > n for the small ones); three layouts;
     three forms."""
     worst = 0.0
     for rows in (1, 3, 70):
