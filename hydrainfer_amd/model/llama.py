@@ -12,7 +12,8 @@ MI355X-first differences (all rounding-neutral with respect to the reference's u
     silu*mul each run as one HIP launch.
 GEMMs are plain library GEMMs (torch.matmul -> hipBLASLt); everything else is libhydra_hip."""
 import os
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
+from types import SimpleNamespace
 from typing import Dict, List, Optional
 
 import torch
@@ -26,6 +27,7 @@ from hydrainfer_amd.layer.causal_attention import AttentionParameters
 from hydrainfer_amd._C.kernel.flash_attn import decode_attention_fused, mha_varlen_fwd
 from hydrainfer_amd._C.kernel import gemm as hip_gemm
 from hydrainfer_amd import _lib, launch_plan
+from hydrainfer_amd.model.decode_plan import Dims, Layouts, StepPlan, mlp_xreg_ok, plan_layouts, resolve, wide_ok
 
 
 @dataclass
@@ -77,6 +79,7 @@ class LlamaForCausalLM:
         self.cos_sin = build_cos_sin(shape, dtype, self.device)
         self.q_size = shape.num_attention_heads * shape.head_dim
         self.kv_size = shape.num_key_value_heads * shape.head_dim
+        self.dims = Dims(shape.hidden_size, shape.intermediate_size, self.q_size, self.q_size + 2 * self.kv_size, shape.num_hidden_layers)
         # decode batches (<= 64 rows) stream the weights through the HIP kernel; larger
         # batches (prefill) use the library GEMM
         self.use_hip_gemm = True
@@ -111,6 +114,7 @@ class LlamaForCausalLM:
         self.packed_x: Dict[str, Tensor] = {}
         self.dw: Dict[str, "hip_gemm.DecodeWeight"] = {}       # descriptors of the packed copies (xreg layout)
         self.dw_lds: Dict[str, "hip_gemm.DecodeWeight"] = {}   # ... (LDS-slice layout)
+        self.decode_layouts: Optional[Layouts] = None          # what pack_decode_weights built (None: nothing yet)
         # decode-side weight layouts are built ONCE, by prepare_decode (engine build / runner construction), for
         # the largest decode batch the owner will ever run — never in the middle of serving
         self.decode_rows_prepared = 0
@@ -129,17 +133,13 @@ class LlamaForCausalLM:
         if max_rows > self.decode_rows_prepared and not self.decode_only:
             self.pack_decode_weights(all_lds_slice=max_rows > 32 and not self._wide_ok(max_rows))
             self.decode_rows_prepared = max_rows
-        if not keep_row_major and not self.decode_only and self._all_packed():
+        if not keep_row_major and not self.decode_only and len(set(self.packed) | set(self.packed_x)) == 4 * self.shape.num_hidden_layers:
             for l in range(self.shape.num_hidden_layers):
                 for n in ("wqkv", "wo", "wgu", "wdown"):
                     w = self.state[f"l{l}.{n}"]
                     # shape / stride / dtype carrier without storage: anything that tries to read it fails loudly
                     self.state[f"l{l}.{n}"] = torch.empty_strided(w.shape, w.stride(), dtype=w.dtype, device="meta")
             self.decode_only = True
-
-    def _all_packed(self) -> bool:
-        return all((f"l{l}.{n}" in self.packed or f"l{l}.{n}" in self.packed_x)
-                   for l in range(self.shape.num_hidden_layers) for n in ("wqkv", "wo", "wgu", "wdown"))
 
     def weight_bytes_resident(self) -> int:
         """Bytes of HBM the weights occupy in all their layouts (row-major + packed copies)."""
@@ -150,7 +150,7 @@ class LlamaForCausalLM:
     def release(self) -> None:
         """Drops every weight tensor (bench.py frees the 7B model before its 13B leg)."""
         self.state, self.packed, self.packed_x, self.dw, self.dw_lds = {}, {}, {}, {}, {}
-        self.xreg_sync = None
+        self.xreg_sync = self.decode_layouts = None
 
     def handover_failed(self) -> bool:
         """True if an in-kernel hand-over of the last decode step gave up waiting (word 1 of a norm-fused
@@ -170,73 +170,37 @@ class LlamaForCausalLM:
         return None
 
     def pack_decode_weights(self, all_lds_slice: bool = False) -> None:
-        """Builds the packed copies of the decoder-layer weights (prepare_decode calls this; never during a capture)
-        through the library's one decode-weight entry (hx_decode_weight_plan / _pack, gemm.DecodeWeight): planned for
-        <= 32 rows it picks the activations-in-registers layout where the shape allows it (gate|up with its halves
-        interleaved for the fused silu*mul epilogue), planned for 64 rows the LDS-slice layout.  o and layer 0's qkv
-        always take the LDS-slice layout (o: at 33 MB the x broadcast of the other kernel would dominate; layer 0's
-        qkv: its x comes row-major from the embedding launch); the LDS-slice copies of the other projections are
-        built only when batches of 33..64 rows are announced: all_lds_slice."""
-        if not (self.use_packed and self.use_hip_gemm and self.dtype in (torch.float16, torch.bfloat16)):
-            return
-        if self.use_xreg and self._xreg_mlp_ok(32):
-            for l in range(self.shape.num_hidden_layers):
-                if f"l{l}.wgu" not in self.packed_x:
-                    for n, gu in (("wgu", True), ("wdown", False)):
-                        dw = hip_gemm.DecodeWeight(self.state[f"l{l}.{n}"], max_rows=32, gate_up=gu)
-                        assert dw.layout == "xreg"
-                        self.dw[f"l{l}.{n}"], self.packed_x[f"l{l}.{n}"] = dw, dw.packed
-                    wq = self.state[f"l{l}.wqkv"]
-                    if self.xreg_qkv and l > 0 and wq.stride(1) == 1 and hip_gemm.xreg_supported(32, wq.shape[0], wq.shape[1], self.dtype):
-                        dw = hip_gemm.DecodeWeight(wq, max_rows=32)
-                        self.dw[f"l{l}.wqkv"], self.packed_x[f"l{l}.wqkv"] = dw, dw.packed
-        for l in range(self.shape.num_hidden_layers):
-            for n in ("wqkv", "wo", "wgu", "wdown"):
-                key = f"l{l}.{n}"
-                if all_lds_slice or key not in self.packed_x:
-                    self._pack_lds_slice(key)
-
-    def _pack_lds_slice(self, key: str) -> Optional[Tensor]:
-        w = self.state[key]
-        if key not in self.packed and w.shape[0] % 16 == 0 and w.shape[1] % 256 == 0 and w.stride(1) == 1:
-            dw = hip_gemm.DecodeWeight(w, max_rows=64, lds_slice=True)     # row-major x in (o, layer 0's qkv) / 13B-like shapes
+        """Builds the packed copies that decode_plan.plan_layouts names (prepare_decode calls this; never during a capture)
+        through the library's one decode-weight entry (gemm.DecodeWeight) and records them in decode_layouts, which the step
+        plan reads.  all_lds_slice: batches of 33..64 rows are announced that the wide kernel cannot take."""
+        L = self.shape.num_hidden_layers
+        ok = self.use_hip_gemm and all(self.state[f"l{l}.{p}"].stride(1) == 1 for l in range(L) for p in ("wqkv", "wo", "wgu", "wdown"))
+        lay = plan_layouts(self.dims, self.dtype, self if ok else None, all_lds_slice, self.decode_layouts)
+        for key in lay.xreg_keys(L):
+            if key not in self.packed_x:
+                dw = hip_gemm.DecodeWeight(self.state[key], max_rows=32, gate_up=key.endswith("wgu"))
+                assert dw.layout == "xreg"
+                self.dw[key], self.packed_x[key] = dw, dw.packed
+        for key in sorted(lay.lds_slice - set(self.packed)):     # row-major x in (o, layer 0's qkv) / 13B-like shapes
+            dw = hip_gemm.DecodeWeight(self.state[key], max_rows=64, lds_slice=True)
             assert dw.layout == "lds_slice"
             self.dw_lds[key], self.packed[key] = dw, dw.packed
-        return self.packed.get(key)
+        # how gate|up is packed: from here on the descriptor's answer (before: the predicate hx_decode_weight_plan decides by)
+        self.decode_layouts = replace(lay, gu_interleaved=self.dw["l0.wgu"].interleaved) if lay.mlp_xreg else lay
 
     def _new_sync(self, device) -> Tensor:
         return torch.empty((self.shape.num_hidden_layers, 2, hip_gemm.XREG_SYNC_WORDS), dtype=torch.int32, device=device)
 
-    def _xreg_mlp_ok(self, n: int) -> bool:
-        hid, inter = self.shape.hidden_size, self.shape.intermediate_size
-        if n > 32:
-            return self._wide_ok(n)
-        return (self.dtype in (torch.float16, torch.bfloat16) and inter % 32 == 0 and hid % 32 == 0
-                and hip_gemm.xreg_supported(n, 2 * inter, hid, self.dtype) and hip_gemm.xreg_supported(n, hid, inter, self.dtype)
-                and all(self.state[f"l0.{k}"].stride(1) == 1 for k in ("wgu", "wdown")))
+    def _layouts(self) -> Layouts:
+        return self.decode_layouts or plan_layouts(self.dims, self.dtype)
 
-    def _gu_interleaved(self) -> bool:
-        """Whether the packed gate|up weight has its halves interleaved: the descriptor's answer once packed, before
-        that the predicate hx_decode_weight_plan decides by (the 32-row launch has the silu*mul epilogue)."""
-        dw = self.dw.get("l0.wgu")
-        if dw is not None:
-            return dw.interleaved
-        return hip_gemm.gate_up_silu_supported(32, self.shape.intermediate_size, self.shape.hidden_size, self.dtype)
+    def _xreg_mlp_ok(self, n: int) -> bool:
+        return self._wide_ok(n) if n > 32 else mlp_xreg_ok(self.dims, n, self.dtype)
 
     def _wide_ok(self, n: int) -> bool:
-        """Batches of 33 .. 64 rows on the activations-in-registers layout (the wide kernel reads the <= 32-row packing:
-        no second copy): gate|up, down and qkv of this shape must all be supported (LLaVA-1.5-7B, and since round 5
-        LLaVA-1.5-13B: its k-steps per wave, 40 and 27, halve to 20 and 14 + 13; other shapes stay on LDS-slice copies)."""
-        hid, inter = self.shape.hidden_size, self.shape.intermediate_size
-        qkv_n = self.q_size + 2 * self.kv_size
-        # gate|up: hx_gate_up_xreg reads the INTERLEAVED packing; a shape whose 32-row launch has no silu epilogue is
-        # packed with its halves in order (gemm.DecodeWeight.interleaved) and takes the plain wide product
-        gu_ok = (hip_gemm.gate_up_xreg_supported(n, inter, hid, self.dtype) if self._gu_interleaved()
-                 else hip_gemm.xreg_supported(n, 2 * inter, hid, self.dtype))
-        return (32 < n <= 64 and self.use_wide and self.use_xreg and self.xreg_qkv and self.dtype in (torch.float16, torch.bfloat16)
-                and inter % 32 == 0 and hid % 32 == 0 and self._xreg_mlp_ok(32) and gu_ok
-                and hip_gemm.xreg_supported(n, hid, inter, self.dtype) and hip_gemm.xreg_supported(n, qkv_n, hid, self.dtype)
-                and hip_gemm.xreg_supported(32, qkv_n, hid, self.dtype))
+        """Batches of 33 .. 64 rows on the activations-in-registers layout (LLaVA-1.5-7B and -13B; other shapes stay on
+        LDS-slice copies)."""
+        return wide_ok(self.dims, n, self.dtype, self, self._layouts().gu_interleaved)
 
     def _partial(self, x: Tensor, key: str, ws: Tensor) -> int:
         """split-K slabs of x @ state[key]^T into ws; packed weights when available."""
@@ -329,147 +293,118 @@ class LlamaForCausalLM:
         return torch.nn.functional.embedding(input_ids, self.state["embed"])
 
     def _decode_plan(self, n: int, dtype) -> dict:
-        """Which launches a decode step of n rows is made of (decided before the step's first launch, because that
-        launch — hx_decode_step_head — also zeroes the hand-over areas of the norm-fused launches)."""
-        sh = self.shape
-        L, hid, inter = sh.num_hidden_layers, sh.hidden_size, sh.intermediate_size
-        qkv_n = self.q_size + 2 * self.kv_size
-        xreg = self.use_xreg and self._xreg_mlp_ok(n) and f"l{L - 1}.wdown" in self.packed_x
-        wide = bool(xreg and n > 32)       # 33 .. 64 rows: two K splits per product; 6 launches per layer, 5 where wide_silu
-        fused = xreg and not wide and hip_gemm.gate_up_silu_supported(n, inter, hid, dtype)
-        if wide:
-            nf_gu = bool(self.fuse_norm and self._gu_interleaved()
-                         and hip_gemm.gate_up_xreg_supported(n, inter, hid, dtype, with_norm=True))
-        else:
-            nf_gu = bool(xreg and self.fuse_norm and fused and hip_gemm.norm_xreg_supported(n, 2 * inter, hid, dtype, gate_up=True))
-        nf_qkv = bool(xreg and self.fuse_norm and f"l{L - 1}.wqkv" in self.packed_x
-                      and hip_gemm.norm_xreg_supported(n, qkv_n, hid, dtype))
-        wide_silu = bool(wide and nf_gu and self.use_wide_silu and hip_gemm.gate_up_silu_wide_supported(n, inter, hid, dtype))
-        return {"xreg": xreg, "fused": fused, "nf_gu": nf_gu, "nf_qkv": nf_qkv, "wide": wide, "wide_silu": wide_silu}
+        """Which launches a decode step of n rows is made of: the six flags of the resolved plan."""
+        return resolve(self.dims, n, dtype, self, self._layouts()).flags()
 
-    def _decode_hidden_hip_gemm(self, h: Tensor, position_ids: Tensor,
-                                model_params: LanguageModelParameters, x0: Optional[Tensor] = None,
-                                sync: Optional[Tensor] = None) -> Tensor:
-        """All-decode step with the weight-streaming HIP GEMMs and fused slab consumers: 8
-        launches per layer — qkv GEMM, [slab reduce + RoPE + cache append + attention], o GEMM,
-        [slab reduce + residual add + RMSNorm], gate|up GEMM, [slab reduce + silu*mul], down GEMM,
-        [slab reduce + residual add + RMSNorm]; 7 with use_xreg at <= 32 rows ([gate|up GEMM +
-        silu*mul] is one launch).  Same rounding points as the unfused path."""
-        sh, st = self.shape, self.state
-        n = h.shape[0]
-        H, HK, D = sh.num_attention_heads, sh.num_key_value_heads, sh.head_dim
-        q_size, kv_size, inter, hid = self.q_size, self.kv_size, sh.intermediate_size, sh.hidden_size
-        eps, L = sh.rms_norm_eps, sh.num_hidden_layers
-        ws_n = max(hip_gemm.workspace_floats(n, q_size + 2 * kv_size, hid), hip_gemm.workspace_floats(n, hid, q_size),
-                   hip_gemm.workspace_floats(n, 2 * inter, hid), hip_gemm.workspace_floats(n, hid, inter),
-                   hip_gemm.xreg_workspace_floats(n, hid, inter),
-                   # qkv and an un-fused gate|up on the activations-in-registers kernel also land in ws where no
-                   # norm-fused launch gives them a buffer of their own (two slabs each at 33 .. 64 rows)
-                   hip_gemm.xreg_workspace_floats(n, q_size + 2 * kv_size, hid), hip_gemm.xreg_workspace_floats(n, 2 * inter, hid))
-        ws = torch.empty(ws_n, dtype=torch.float32, device=h.device)
-        x = torch.empty_like(h)
+    def _step_plan(self, n: int, dtype) -> StepPlan:
+        """The plan of the step about to run.  Resolved per step and never cached (fuse_norm is cleared at run time after
+        a hand-over gave up), before the step's first launch, which zeroes the hand-over areas the plan asks for."""
         if n > self.decode_rows_prepared and not self.decode_only:
             if torch.cuda.is_current_stream_capturing():
                 raise RuntimeError(f"decode batch of {n} rows captured before prepare_decode(max_rows >= {n})")
-            # a caller that never announced its batch size (unit tests, ad-hoc scripts): everything a <= 64-row
-            # batch can need, once; the engine / runners call prepare_decode at build time
-            self.prepare_decode(max_rows=64)
-        dp = self._decode_plan(n, h.dtype)
-        xreg, fused, nf_gu, nf_qkv, wide = dp["xreg"], dp["fused"], dp["nf_gu"], dp["nf_qkv"], dp["wide"]
-        qkv_n = q_size + 2 * kv_size
-        ws_q = ws          # where the current layer's qkv slabs live
-        if xreg:
-            xf = torch.empty(hip_gemm.fragment_major_elems(n, hid), dtype=h.dtype, device=h.device)
-            actf = torch.empty(hip_gemm.fragment_major_elems(n, inter), dtype=h.dtype, device=h.device) if fused else None
-            # add+norm folded into the launch that consumes its output (hx_norm_*_xreg): 5 launches per layer
-            if nf_gu or nf_qkv:
-                # one zeroed hand-over area per fused launch of this step: zeroed by the step's first launch
-                # (hx_decode_step_head) when the caller came through it, by a launch of its own otherwise
-                if sync is None:
-                    sync = self._new_sync(h.device)
-                    _lib.memset_zero(sync)
-                self.xreg_sync = sync
-            if nf_qkv:   # the fused launch reads the down slabs (ws) while it writes the qkv slab
-                ws_q = torch.empty(max(hip_gemm.xreg_workspace_floats(n, qkv_n, hid), hip_gemm.workspace_floats(n, qkv_n, hid)),
-                                   dtype=torch.float32, device=h.device)
-            wide_silu = bool(wide and nf_gu and dp["wide_silu"])
-            if wide and not wide_silu:     # gate|up slabs of the wide product (the norm-fused form reads the o slabs in ws meanwhile)
-                gu_interleaved = self._gu_interleaved()
-                ws_gu = torch.empty(hip_gemm.gate_up_xreg_workspace_floats(n, inter, hid) if gu_interleaved
-                                    else hip_gemm.xreg_workspace_floats(n, 2 * inter, hid), dtype=torch.float32, device=h.device)
-            actf_w = torch.empty(hip_gemm.fragment_major_elems(n, inter), dtype=h.dtype, device=h.device) if wide_silu else None
-        if x0 is not None:
-            x = x0          # the first layer's norm came with the embedding gather
-        else:
-            rms_norm(x, h, st["l0.norm1"], eps)
+            self.prepare_decode(max_rows=64)     # a caller that never announced its batch size (unit tests, ad-hoc scripts)
+        return resolve(self.dims, n, dtype, self, self._layouts())
+
+    def _decode_hidden_hip_gemm(self, h: Tensor, position_ids: Tensor, model_params: LanguageModelParameters, plan: StepPlan,
+                                x0: Optional[Tensor] = None, sync: Optional[Tensor] = None) -> Tensor:
+        """All-decode step of <= 64 rows on the weight-streaming HIP GEMMs and their fused slab consumers.  A layer is five
+        stages — qkv, attention + o, norm2 + gate|up + silu*mul, down, close (residual add + the next norm) — each run in
+        the variant `plan` names: five to eight launches, listed per plan in tests/decode_arms.py::SEQUENCES.  Nothing is
+        decided here.  Same rounding points as the unfused path."""
+        sh, n, last = self.shape, h.shape[0], self.shape.num_hidden_layers - 1
+        f32 = lambda k: torch.empty(k, dtype=torch.float32, device=h.device)
+        frag = lambda K: torch.empty(hip_gemm.fragment_major_elems(n, K), dtype=h.dtype, device=h.device)
+        ws = f32(plan.ws)
+        b = SimpleNamespace(n=n, h=h, x=x0, ws=ws, ws_q=f32(plan.ws_q) if plan.ws_q else ws, ws_gu=f32(plan.ws_gu) if plan.ws_gu else ws,
+                            xf=frag(sh.hidden_size) if plan.xf else None, sync=sync,
+                            actf=frag(sh.intermediate_size) if plan.actf or plan.actf_w else None)
+        if plan.sync and sync is None:   # the caller did not come through the step head, whose launch zeroes the areas
+            b.sync = self._new_sync(h.device)
+            _lib.memset_zero(b.sync)
+        if plan.sync:
+            self.xreg_sync = b.sync
+        if x0 is None:                   # else the first layer's norm came with the embedding gather
+            b.x = torch.empty_like(h)
+            rms_norm(b.x, h, self.state["l0.norm1"], sh.rms_norm_eps)
         s_qkv = None
-        for l in range(L):
-            ap = model_params.attention_params[l]
-            kc, vc = ap.kv_cache.get_kv_cache()
-            if s_qkv is None:
-                if xreg and f"l{l}.wqkv" in self.packed_x:
-                    if wide:
-                        s_qkv = hip_gemm.linear_decode_partial_xreg(xf, self.packed_x[f"l{l}.wqkv"], qkv_n, ws_q, frag_shape=(n, hid))
-                    else:
-                        s_qkv = hip_gemm.linear_decode_ex(xf, self.dw[f"l{l}.wqkv"], ws_q, frag_shape=(n, hid))
-                else:
-                    s_qkv = self._partial(x, f"l{l}.wqkv", ws_q)
-            o = torch.empty((n, H, D), dtype=h.dtype, device=h.device)
-            # q / k_new / v_new arguments are shape carriers here: the kernel reads the slabs
-            decode_attention_fused(o, o, o[:, :HK], o[:, :HK], kc, vc, position_ids, self.cos_sin,
-                                   ap.new_cache_slots, ap.q_cu_seq_lens, ap.kv_cu_seq_lens, ap.block_tables,
-                                   ap.cu_blocks_lens, ap.kv_max_seq_len, D ** -0.5, 0, ws_q, s_qkv, ap.decode_rank)
-            s_qkv = None
-            s_o = self._partial(o.view(n, q_size), f"l{l}.wo", ws)
-            if xreg:
-                # fragment-major activations from here to the down projection
-                pgu, pdn = self.packed_x[f"l{l}.wgu"], self.packed_x[f"l{l}.wdown"]
-                if wide:
-                    # 33 .. 64 rows: (norm +) gate|up to two slabs, then silu*mul (fragment-major for the down product)
-                    if wide_silu:
-                        # silu * mul inside the same launch (both K halves in one workgroup): 5 launches per layer, no slabs
-                        hip_gemm.norm_gate_up_silu_wide_xreg(h, ws, s_o, st[f"l{l}.norm2"], eps, xf, pgu, inter, actf_w, sync[l, 0])
-                        a_f = actf_w
-                    else:
-                        if nf_gu:
-                            s_gu = hip_gemm.norm_gate_up_xreg(h, ws, s_o, st[f"l{l}.norm2"], eps, xf, pgu, inter, ws_gu, sync[l, 0])
-                        else:
-                            add_rms_norm_slabs(xf, h, ws, s_o, st[f"l{l}.norm2"], eps, fragment_major=True)
-                            if gu_interleaved:
-                                s_gu = hip_gemm.gate_up_xreg(xf, pgu, inter, ws_gu, frag_shape=(n, hid))
-                            else:   # halves in order: the plain wide product already gives [gate | up] columns
-                                s_gu = hip_gemm.linear_decode_partial_xreg(xf, pgu, 2 * inter, ws_gu, frag_shape=(n, hid))
-                        a_f = silu_and_mul_slabs(ws_gu, s_gu, n, inter, h.dtype, fragment_major=True)
-                elif nf_gu:
-                    hip_gemm.norm_gate_up_silu_xreg(h, ws, s_o, st[f"l{l}.norm2"], eps, xf, pgu, inter, actf, sync[l, 0])
-                    a_f = actf
-                else:
-                    add_rms_norm_slabs(xf, h, ws, s_o, st[f"l{l}.norm2"], eps, fragment_major=True)
-                    if fused:
-                        hip_gemm.gate_up_silu_xreg(xf, pgu, inter, actf, frag_shape=(n, hid))
-                        a_f = actf
-                    else:
-                        s_gu = hip_gemm.linear_decode_partial_xreg(xf, pgu, 2 * inter, ws, frag_shape=(n, hid))
-                        a_f = silu_and_mul_slabs(ws, s_gu, n, inter, h.dtype, fragment_major=True)
-                if wide:
-                    s_dn = hip_gemm.linear_decode_partial_xreg(a_f, pdn, hid, ws, frag_shape=(n, inter))
-                else:
-                    s_dn = hip_gemm.linear_decode_ex(a_f, self.dw[f"l{l}.wdown"], ws, frag_shape=(n, inter))
-            else:
-                add_rms_norm_slabs(x, h, ws, s_o, st[f"l{l}.norm2"], eps)
-                s_gu = self._partial(x, f"l{l}.wgu", ws)
-                act = silu_and_mul_slabs(ws, s_gu, n, inter, h.dtype)
-                s_dn = self._partial(act, f"l{l}.wdown", ws)
-            nxt = st[f"l{l + 1}.norm1"] if l + 1 < L else st["norm"]
-            if xreg and f"l{l + 1}.wqkv" in self.packed_x:
-                if nf_qkv:   # h += down; x = norm1(h); next layer's qkv slab — one launch
-                    s_qkv = hip_gemm.norm_linear_decode_xreg(h, ws, s_dn, nxt, eps, xf, self.packed_x[f"l{l + 1}.wqkv"],
-                                                             qkv_n, ws_q, sync[l, 1])
-                else:
-                    add_rms_norm_slabs(xf, h, ws, s_dn, nxt, eps, fragment_major=True)
-            else:
-                add_rms_norm_slabs(x, h, ws, s_dn, nxt, eps)
-        return x
+        for l in range(last + 1):
+            s_qkv = self._stage_qkv(plan.qkv if l else "rowmajor", l, b, s_qkv)
+            s_o = self._stage_attention_o(l, b, s_qkv, position_ids, model_params.attention_params[l])
+            act = self._stage_mlp_in(plan.mlp, l, b, s_o)
+            s_dn = self._stage_down(plan.down, l, b, act)
+            s_qkv = self._stage_close(plan.close if l < last else "rowmajor", l, b, s_dn)
+        return b.x
+
+    def _stage_qkv(self, variant: str, l: int, b, handed: Optional[int]) -> int:
+        """Slabs of x @ wqkv^T in b.ws_q; returns their count."""
+        key, hid = f"l{l}.wqkv", self.shape.hidden_size
+        if variant == "handover":
+            return handed
+        if variant == "ex":
+            return hip_gemm.linear_decode_ex(b.xf, self.dw[key], b.ws_q, frag_shape=(b.n, hid))
+        if variant == "wide":
+            return hip_gemm.linear_decode_partial_xreg(b.xf, self.packed_x[key], self.q_size + 2 * self.kv_size, b.ws_q, frag_shape=(b.n, hid))
+        return self._partial(b.x, key, b.ws_q)
+
+    def _stage_attention_o(self, l: int, b, s_qkv: int, position_ids: Tensor, ap: AttentionParameters) -> int:
+        """[slab reduce + RoPE + cache append + attention], then the slabs of o @ wo^T in b.ws; returns their count."""
+        H, HK, D = self.shape.num_attention_heads, self.shape.num_key_value_heads, self.shape.head_dim
+        kc, vc = ap.kv_cache.get_kv_cache()
+        o = torch.empty((b.n, H, D), dtype=b.h.dtype, device=b.h.device)
+        # q / k_new / v_new arguments are shape carriers here: the kernel reads the slabs
+        decode_attention_fused(o, o, o[:, :HK], o[:, :HK], kc, vc, position_ids, self.cos_sin,
+                               ap.new_cache_slots, ap.q_cu_seq_lens, ap.kv_cu_seq_lens, ap.block_tables,
+                               ap.cu_blocks_lens, ap.kv_max_seq_len, D ** -0.5, 0, b.ws_q, s_qkv, ap.decode_rank)
+        return self._partial(o.view(b.n, self.q_size), f"l{l}.wo", b.ws)
+
+    def _stage_mlp_in(self, variant: str, l: int, b, s_o: int) -> Tensor:
+        """h += o; x = norm2(h); returns silu(x Wg^T) * (x Wu^T) as the down stage reads it: row-major for "slabs", else
+        fragment-major.  The "norm_" variants produce x inside the gate|up launch (hand-over area b.sync[l, 0])."""
+        n, h, ws, xf, nw, eps = b.n, b.h, b.ws, b.xf, self.state[f"l{l}.norm2"], self.shape.rms_norm_eps
+        hid, inter = self.shape.hidden_size, self.shape.intermediate_size
+        if variant == "slabs":
+            add_rms_norm_slabs(b.x, h, ws, s_o, nw, eps)
+            s_gu = self._partial(b.x, f"l{l}.wgu", ws)
+            return silu_and_mul_slabs(ws, s_gu, n, inter, h.dtype)
+        pgu = self.packed_x[f"l{l}.wgu"]
+        if variant == "norm_silu":
+            hip_gemm.norm_gate_up_silu_xreg(h, ws, s_o, nw, eps, xf, pgu, inter, b.actf, b.sync[l, 0])
+            return b.actf
+        if variant == "norm_wide_silu":     # 33 .. 64 rows, both K halves in one workgroup: no slabs
+            hip_gemm.norm_gate_up_silu_wide_xreg(h, ws, s_o, nw, eps, xf, pgu, inter, b.actf, b.sync[l, 0])
+            return b.actf
+        if variant == "norm_wide":
+            s_gu = hip_gemm.norm_gate_up_xreg(h, ws, s_o, nw, eps, xf, pgu, inter, b.ws_gu, b.sync[l, 0])
+            return silu_and_mul_slabs(b.ws_gu, s_gu, n, inter, h.dtype, fragment_major=True)
+        add_rms_norm_slabs(xf, h, ws, s_o, nw, eps, fragment_major=True)
+        if variant == "silu":
+            hip_gemm.gate_up_silu_xreg(xf, pgu, inter, b.actf, frag_shape=(n, hid))
+            return b.actf
+        if variant == "wide":
+            s_gu = hip_gemm.gate_up_xreg(xf, pgu, inter, b.ws_gu, frag_shape=(n, hid))
+        else:   # "plain" (b.ws_gu is ws), "wide_plain": halves in order, the plain product already gives [gate | up] columns
+            s_gu = hip_gemm.linear_decode_partial_xreg(xf, pgu, 2 * inter, b.ws_gu, frag_shape=(n, hid))
+        return silu_and_mul_slabs(b.ws_gu, s_gu, n, inter, h.dtype, fragment_major=True)
+
+    def _stage_down(self, variant: str, l: int, b, act: Tensor) -> int:
+        """Slabs of act @ wdown^T in b.ws; returns their count."""
+        key, inter = f"l{l}.wdown", self.shape.intermediate_size
+        if variant == "ex":
+            return hip_gemm.linear_decode_ex(act, self.dw[key], b.ws, frag_shape=(b.n, inter))
+        if variant == "wide":
+            return hip_gemm.linear_decode_partial_xreg(act, self.packed_x[key], self.shape.hidden_size, b.ws, frag_shape=(b.n, inter))
+        return self._partial(act, key, b.ws)
+
+    def _stage_close(self, variant: str, l: int, b, s_dn: int) -> Optional[int]:
+        """h += down; x = the next layer's first norm of h (after the last layer: the final norm).  "handover": the same
+        launch also writes the next layer's qkv slabs and returns their count."""
+        nxt = self.state[f"l{l + 1}.norm1" if l + 1 < self.shape.num_hidden_layers else "norm"]
+        if variant == "handover":
+            return hip_gemm.norm_linear_decode_xreg(b.h, b.ws, s_dn, nxt, self.shape.rms_norm_eps, b.xf, self.packed_x[f"l{l + 1}.wqkv"],
+                                                    self.q_size + 2 * self.kv_size, b.ws_q, b.sync[l, 1])
+        if variant == "fm":
+            return add_rms_norm_slabs(b.xf, b.h, b.ws, s_dn, nxt, self.shape.rms_norm_eps, fragment_major=True)
+        return add_rms_norm_slabs(b.x, b.h, b.ws, s_dn, nxt, self.shape.rms_norm_eps)
 
     def _decode_fast_path(self, n: int, dtype, model_params: LanguageModelParameters) -> bool:
         sh = self.shape
@@ -488,16 +423,16 @@ class LlamaForCausalLM:
         sh, st = self.shape, self.state
         x0 = sync = None
         head = model_params.step_head
-        if input_ids_or_embeds.dtype in (torch.int32, torch.int64):
+        is_ids = input_ids_or_embeds.dtype in (torch.int32, torch.int64)
+        n, dtype = input_ids_or_embeds.shape[0], st["embed"].dtype if is_ids else input_ids_or_embeds.dtype
+        plan = self._step_plan(n, dtype) if self._decode_fast_path(n, dtype, model_params) else None
+        if is_ids:
             ids = input_ids_or_embeds
-            if (model_params.all_sequences_decode and ids.dim() == 1 and ids.shape[0] <= 64
-                    and embed_rms_norm_supported(ids, st["embed"])):
+            if model_params.all_sequences_decode and ids.dim() == 1 and n <= 64 and embed_rms_norm_supported(ids, st["embed"]):
                 # decode step: embedding gather + the first layer's norm + the zeroing of the hand-over areas of the
                 # step's norm-fused launches + the caller's metadata advance / look-ahead feed: ONE launch
-                if self._decode_fast_path(ids.shape[0], st["embed"].dtype, model_params):
-                    dp = self._decode_plan(ids.shape[0], st["embed"].dtype)
-                    if dp["nf_gu"] or dp["nf_qkv"]:
-                        sync = self._new_sync(ids.device)
+                if plan is not None and plan.sync:
+                    sync = self._new_sync(ids.device)
                 h, x0 = decode_step_head(ids, st["embed"], st["l0.norm1"], sh.rms_norm_eps, zero=sync, head=head)
                 head = None
             else:
@@ -509,9 +444,9 @@ class LlamaForCausalLM:
                                "fp16 / bf16 embedding table): the caller must run its advance / feed itself")
         if not h.is_contiguous():
             h = h.contiguous()
+        if plan is not None:
+            return self._decode_hidden_hip_gemm(h, position_ids, model_params, plan, x0, sync)
         n = h.shape[0]
-        if self._decode_fast_path(n, h.dtype, model_params):
-            return self._decode_hidden_hip_gemm(h, position_ids, model_params, x0, sync)
         H, HK, D = sh.num_attention_heads, sh.num_key_value_heads, sh.head_dim
         q_size, kv_size, inter = self.q_size, self.kv_size, sh.intermediate_size
         eps = sh.rms_norm_eps

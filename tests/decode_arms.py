@@ -458,11 +458,12 @@ class Spied(list):
 
 
 @contextlib.contextmanager
-def spy(keep_tensors: bool = False, max_elems: int = 1 << 22):
-    """Wraps, for the duration of the block, the names _decode_hidden_hip_gemm (and forward_hidden) call through
-    hydrainfer_amd.model.llama: every launch wrapper of hip_gemm, add_rms_norm_slabs, silu_and_mul_slabs,
-    decode_attention_fused, rms_norm, decode_step_head (and the generic loop's add_rms_norm, silu_and_mul), and
-    _lib.memset_zero.  Yields the list of (name, layer) seen so far; no hook in product code."""
+def spy(keep_tensors: bool = False, max_elems: int = 1 << 22, stubs: Optional[dict] = None):
+    """Wraps, for the duration of the block, the names the decode layer (_decode_hidden_hip_gemm, its _stage_* functions
+    and forward_hidden) calls through hydrainfer_amd.model.llama: every launch wrapper of hip_gemm, add_rms_norm_slabs,
+    silu_and_mul_slabs, decode_attention_fused, rms_norm, decode_step_head (and the generic loop's add_rms_norm,
+    silu_and_mul), and _lib.memset_zero.  Yields the list of (name, layer) seen so far; no hook in product code.
+    stubs: {name: function} called in place of the wrapper of that name (a dry run without a device: dry_stubs())."""
     from hydrainfer_amd import _lib
     from hydrainfer_amd.model import llama
     seen = Spied()
@@ -471,6 +472,7 @@ def spy(keep_tensors: bool = False, max_elems: int = 1 << 22):
 
     def wrap(owner, attr):
         orig = getattr(owner, attr)
+        call = orig if stubs is None else stubs[attr]
 
         @functools.wraps(orig)
         def f(*a, **k):
@@ -486,7 +488,7 @@ def spy(keep_tensors: bool = False, max_elems: int = 1 << 22):
                     seen[-1] = (seen[-1][0], state["layer"])
             idx = len(seen)
             seen.append((name, HEAD if attr in HEAD_NAMES else state["layer"]))
-            out = orig(*a, **k)
+            out = call(*a, **k)
             if keep_tensors:
                 grab = lambda t: t.detach().clone() if isinstance(t, Tensor) and t.numel() <= max_elems else None
                 seen.tensors.append({"args": [grab(t) for t in a], "kwargs": {n: grab(t) for n, t in k.items()},
@@ -508,11 +510,30 @@ def spy(keep_tensors: bool = False, max_elems: int = 1 << 22):
             setattr(owner, attr, orig)
 
 
+def dry_stubs() -> dict:
+    """A stub for every name the spy wraps that touches nothing and returns a value of the wrapper's kind: a slab count
+    for the GEMMs that return one, an empty tensor of the result's shape for silu_and_mul_slabs (the only result the
+    layer passes on as a tensor; fragment-major: flat, rows padded to 16), None for the rest."""
+    def silu(partial, n_splits, rows, inter, dtype, fragment_major=False):
+        return torch.empty((rows + 15) // 16 * 16 * inter if fragment_major else (rows, inter), dtype=dtype)
+    counted = set(PLAIN_GEMMS) - {"linear_decode"} | {"norm_linear_decode_xreg", "gate_up_xreg", "norm_gate_up_xreg"}
+    stubs = {n: (lambda *a, **k: 2) if n in counted else (lambda *a, **k: None)
+             for n in GEMM_WRAPPERS + LLAMA_WRAPPERS + ("memset_zero",)}
+    stubs["silu_and_mul_slabs"] = silu
+    return stubs
+
+
+def decode_layer_functions() -> list:
+    """The functions that make up the decode layer: the body, one function per stage, and _partial."""
+    from hydrainfer_amd.model.llama import LlamaForCausalLM as M
+    return [M._decode_hidden_hip_gemm, M._stage_qkv, M._stage_attention_o, M._stage_mlp_in, M._stage_down, M._stage_close,
+            M._partial]
+
+
 def call_sites() -> set:
     """Every launch wrapper named in the source of the decode layer: hip_gemm.<name>( that is not a host planning query,
     plus the four non-GEMM wrappers."""
-    from hydrainfer_amd.model.llama import LlamaForCausalLM as M
-    src = inspect.getsource(M._decode_hidden_hip_gemm) + inspect.getsource(M._partial)
+    src = "".join(inspect.getsource(f) for f in decode_layer_functions())
     names = {n for n in re.findall(r"hip_gemm\.(\w+)\(", src)
              if not n.endswith(("_supported", "_floats", "_elems"))}
     for n in ("add_rms_norm_slabs", "silu_and_mul_slabs", "decode_attention_fused", "rms_norm"):
@@ -535,10 +556,11 @@ def build_model(shape_key: str, dname: str, sw: Switches, device):
     return model
 
 
-def device_step(model, c: Case, device, pool_d: Tensor, feed: str = "int64", keep_tensors: bool = False):
+def device_step(model, c: Case, device, pool_d: Tensor, feed: str = "int64", keep_tensors: bool = False,
+                stubs: Optional[dict] = None):
     """Runs the case's step on the HIP model over pool_d (the case's pool on the device: written in place).  feed: the
-    way into the step — "int64" / "int32" token ids, or "embeds" (model.embed(ids) passed as embeddings).  Returns
-    (logits, the spied list)."""
+    way into the step — "int64" / "int32" token ids, or "embeds" (model.embed(ids) passed as embeddings).  stubs: the
+    spy's (a dry run: device "cpu", no launch).  Returns (logits, the spied list)."""
     from hydrainfer_amd._C.kernel.flash_attn import decode_rank
     from hydrainfer_amd.layer.causal_attention import AttentionParameters
     from hydrainfer_amd.memory.kv_cache import KVCache
@@ -546,7 +568,7 @@ def device_step(model, c: Case, device, pool_d: Tensor, feed: str = "int64", kee
     m = c.meta()
     d = lambda t: t.to(device)
     q_cu, kv_cu, slots, bt, cu_b = d(m.q_cu_seq_lens), d(m.kv_cu_seq_lens), d(m.new_cache_slots), d(m.block_tables), d(m.cu_blocks_lens)
-    rank = decode_rank(kv_cu)
+    rank = decode_rank(kv_cu) if stubs is None else None
     ap = [AttentionParameters(kv_cache=KVCache(pool_d[l, 0], pool_d[l, 1]), q_cu_seq_lens=q_cu, kv_cu_seq_lens=kv_cu,
                               new_cache_slots=slots, block_tables=bt, cu_blocks_lens=cu_b, num_sequences=c.n,
                               all_sequences_decode=True, q_max_seq_len=1, kv_max_seq_len=max(c.ctx), decode_rank=rank)
@@ -554,6 +576,6 @@ def device_step(model, c: Case, device, pool_d: Tensor, feed: str = "int64", kee
     params = LanguageModelParameters(attention_params=ap, all_sequences_decode=True)
     ids = d(c.ids)
     x = {"int64": lambda: ids, "int32": lambda: ids.to(torch.int32), "embeds": lambda: model.embed(ids)}[feed]()
-    with spy(keep_tensors) as seen:
+    with spy(keep_tensors, stubs=stubs) as seen:
         logits = model.forward_logits(x, d(c.positions), params)
     return logits, seen

@@ -157,3 +157,89 @@ def test_spy_wraps_every_call_site_and_restores():
         assert llama.hip_gemm.linear_decode_ex is not before[0] and llama.rms_norm is not before[1]
         assert _lib.memset_zero is not before[2] and list(seen) == []
     assert (llama.hip_gemm.linear_decode_ex, llama.rms_norm, _lib.memset_zero) == before
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the resolved step plan (hydrainfer_amd/model/decode_plan.py) and a dry run of the layer body, both without a device
+# ---------------------------------------------------------------------------------------------------------------------
+_dry_states = {}
+
+
+def _dry_model(arm, dname):
+    """The arm's three-layer model on uninitialised CPU tensors (no launch reads them) after what prepare_decode(64)
+    would do without packing anything: the layout record of decode_plan.plan_layouts — the statement pack_decode_weights
+    packs by — and a placeholder in the layout dicts for every key the record names."""
+    from hydrainfer_amd.model.decode_plan import plan_layouts
+    from hydrainfer_amd.model.llama import LlamaForCausalLM
+    dt, sh = A.DTYPES[dname], A.llama_shape(arm.shape)
+    if (arm.shape, dname) not in _dry_states:
+        hid, inter = sh.hidden_size, sh.intermediate_size
+        sizes = {"wqkv": (3 * hid, hid), "wo": (hid, hid), "wgu": (2 * inter, hid), "wdown": (hid, inter), "norm1": (hid,), "norm2": (hid,)}
+        st = {f"l{l}.{k}": torch.empty(s, dtype=dt) for l in range(A.LAYERS) for k, s in sizes.items()}
+        st.update(embed=torch.zeros((A.VOCAB, hid), dtype=dt), lm_head=torch.zeros((A.VOCAB, hid), dtype=dt), norm=torch.empty(hid, dtype=dt))
+        _dry_states[(arm.shape, dname)] = st
+    model = LlamaForCausalLM(sh, dt, "cpu", dict(_dry_states[(arm.shape, dname)]))
+    arm.sw.apply(model)
+    lay = plan_layouts(model.dims, dt, arm.sw, all_lds_slice=not model._wide_ok(64))        # as prepare_decode(64) asks
+    for k in lay.xreg_keys(A.LAYERS):
+        model.packed_x[k] = model.dw[k] = object()
+    for k in lay.lds_slice:
+        model.packed[k] = model.dw_lds[k] = object()
+    model.decode_layouts, model.decode_rows_prepared = lay, 64
+    return model
+
+
+DRY = [(a, d) for a in A.ARMS for d in A.DTYPES]
+
+
+@pytest.mark.parametrize("arm,dname", DRY, ids=[f"{a.name}-{d}" for a, d in DRY])
+def test_resolver_plans_what_the_table_says(arm, dname):
+    """decode_plan.resolve on the arm's switches and the layout record of its shape: the six flags are the table's and
+    the independent restatement's (host_plan), the record is host_qkv_packed's, at every row count the arm runs."""
+    from hydrainfer_amd.model.decode_plan import resolve
+    model = _dry_model(arm, dname)
+    lay = model.decode_layouts
+    assert lay.qkv_xreg == A.host_qkv_packed(arm.shape, arm.sw)
+    assert set(lay.lds_slice) >= {f"l{l}.wo" for l in range(A.LAYERS)} | {"l0.wqkv"} or not arm.sw.use_packed
+    # a second (LDS-slice) copy of a projection exactly where 64 rows cannot run on the activations-in-registers one
+    xk = set(lay.xreg_keys(A.LAYERS))
+    assert bool(set(lay.lds_slice) & xk) == (bool(xk) and not model._wide_ok(64))
+    for n in arm.rows():
+        if n <= 64:
+            plan = resolve(model.dims, n, A.DTYPES[dname], arm.sw, lay)
+            assert plan.flags() == A.PLAN_OF[arm.family(n)] == A.host_plan(arm.shape, arm.sw, n), (arm.name, n, plan)
+            assert plan.flags() == model._decode_plan(n, A.DTYPES[dname])
+            assert (plan.ws_q is not None) == plan.flags()["nf_qkv"] and plan.xf == plan.flags()["xreg"]
+            assert (plan.ws_gu is not None) == (plan.flags()["wide"] and not plan.flags()["wide_silu"])
+
+
+@pytest.mark.parametrize("arm,dname", DRY, ids=[f"{a.name}-{d}" for a, d in DRY])
+def test_dry_run_of_the_layer_body(arm, dname):
+    """The real forward_logits on the "embeds" feed with every launch wrapper stubbed (tests/decode_arms.py::dry_stubs):
+    the layer body assembles the arm's launch sequence, layer by layer, and zeroes a hand-over area of its own exactly
+    where the plan has a hand-over."""
+    model = _dry_model(arm, dname)
+    heads = A.SHAPES[arm.shape][2]
+    for n in arm.rows():
+        if n > 64:
+            continue
+        c = A.Case(arm.shape, dname, n, torch.zeros(n, dtype=torch.int64), [1] * n, [[i] for i in range(n)],
+                   torch.empty((A.LAYERS, 2, n, A.BS, heads, A.HEAD_DIM), dtype=A.DTYPES[dname]))
+        logits, seen = A.device_step(model, c, "cpu", c.pool, "embeds", stubs=A.dry_stubs())
+        fam, plan = arm.family(n), model._step_plan(n, A.DTYPES[dname])
+        assert logits.shape == (n, A.VOCAB)
+        for l in range(A.LAYERS):
+            assert seen.layer(l) == A.SEQUENCES[fam][l], f"layer {l} of {arm.name} at {n} rows"
+        assert plan.sync == (A.PLAN_OF[fam]["nf_gu"] or A.PLAN_OF[fam]["nf_qkv"])
+        assert seen.layer(A.HEAD) == (["memset_zero", "rms_norm"] if plan.sync else ["rms_norm"])
+        assert (model.xreg_sync is not None) == plan.sync
+        model.xreg_sync = None
+
+
+def test_the_layer_body_decides_nothing():
+    """The body and its stage functions read the plan: no switch, no packed_x membership, no support query."""
+    import inspect
+    for f in A.decode_layer_functions():
+        src = inspect.getsource(f)
+        for banned in ("in self.packed_x", "_gu_interleaved", "_supported(", "self.use_", "self.fuse_norm", "self.xreg_qkv"):
+            assert banned not in src, (f.__name__, banned)
