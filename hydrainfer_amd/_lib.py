@@ -117,6 +117,8 @@ _SIGNATURES = {
                                    + [c_int64, c_void_p, c_int, c_void_p]),
     "hx_sample_rows_logprobs": (c_int, [c_void_p] * 4 + [c_int64] * 3 + [c_void_p] * 3 + [c_int64, c_void_p] + [c_void_p] * 3
                                 + [c_int64] + [c_void_p] * 4 + [c_int, c_void_p, c_int, c_void_p]),
+    "hx_sample_rows_masked": (c_int, [c_void_p] * 4 + [c_int64] * 3 + [c_void_p] * 3 + [c_int64, c_void_p] + [c_void_p] * 3
+                              + [c_int64] + [c_void_p] * 4 + [c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p]),
     "hx_norm_xreg_supported": (c_int, [c_int64] * 3 + [c_int]),
     "hx_norm_linear_decode_xreg": (c_int, [c_void_p] * 3 + [c_int32, c_void_p, c_float, c_void_p, c_void_p] + [c_int64] * 3 + [c_void_p, c_int64, c_int, c_void_p]),
     "hx_norm_gate_up_silu_xreg": (c_int, [c_void_p] * 3 + [c_int32, c_void_p, c_float, c_void_p, c_void_p] + [c_int64] * 3 + [c_void_p, c_int, c_void_p]),

@@ -29,6 +29,10 @@
 // the block m, the cut and Z_S, so the log-probability of the chosen token under the distribution it was chosen from is
 // (z - m) - logf(Z_S), and the K most likely alternatives are K block-argmax rounds over the registers — no second read
 // of the row, no second launch.  A greedy row that is scored does not leave early: T' = 1 and S is the whole row.
+//
+// hx_sample_rows_masked (allowed_token_ids, guided_choice) is the scored body with a step 1a: a row that names one of
+// the launch's token bitmasks (32 tokens per word, 1 = allowed) gets -inf at every token whose bit is clear, in the staged
+// row and ahead of everything else, from one read of the mask's 4 KB — no LDS beyond the row's own.
 #include <math.h>
 
 #include "hx_common.h"
@@ -84,6 +88,10 @@ __device__ __forceinline__ float smp_block_sum(float s, float* part) {
   constexpr bool SCORED = false;                                                                       \
   float* const logprobs = nullptr; int32_t* const top_ids = nullptr; float* const top_logprobs = nullptr; \
   const int32_t score_k = 0; const int32_t* const want = nullptr;
+// and for its masks, in the kernels that take none (MASKED false: no statement that reads them is compiled)
+#define SMP_NO_MASK                                                                                    \
+  constexpr bool MASKED = false;                                                                       \
+  const uint32_t* const allow_words = nullptr; const int32_t n_masks = 0; const int32_t* const mask_row = nullptr;
 
 template <typename T>
 __global__ __launch_bounds__(SMP_THREADS) void sample_rows_kernel(
@@ -93,6 +101,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_rows_kernel(
     const uint32_t* __restrict__ sample_params) {
   constexpr bool CONSTRAINED = false;
   SMP_NO_SCORES
+  SMP_NO_MASK
   const int32_t* const bias_ids = nullptr; const float* const bias_values = nullptr; const int32_t* const cu_bias = nullptr;
   const int32_t bias_total = 0;
 #include "sampling_body.inc"
@@ -110,6 +119,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_rows_constrained_kernel(
     const float* __restrict__ bias_values, const int32_t* __restrict__ cu_bias, int32_t bias_total) {
   constexpr bool CONSTRAINED = true;
   SMP_NO_SCORES
+  SMP_NO_MASK
 #include "sampling_body.inc"
 }
 
@@ -127,6 +137,27 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_rows_logprobs_kernel(
     const int32_t* __restrict__ want) {
   constexpr bool CONSTRAINED = true;
   constexpr bool SCORED = true;
+  SMP_NO_MASK
+#include "sampling_body.inc"
+}
+
+// hx_sample_rows_masked: the scored body with step 1a — a row that names a mask has every element whose bit is clear set
+// to -inf in the staged row, ahead of the bias table; everything after that is the body as it stands, which handles -inf
+// bans already.  Scoring is optional per launch here (logprobs null: no row is scored).  MASKED is false in the three
+// kernels above, which keep their device code byte for byte.
+template <typename T>
+__global__ __launch_bounds__(SMP_THREADS) void sample_rows_masked_kernel(
+    int64_t* __restrict__ ids, float* __restrict__ cut_out, float* __restrict__ u_out, const u16* __restrict__ logits,
+    int32_t n, int64_t ld, const int32_t* __restrict__ hist_ids, const int32_t* __restrict__ hist_counts,
+    const int32_t* __restrict__ cu_hist, int32_t total, const float* __restrict__ penalties,
+    const uint32_t* __restrict__ sample_params, const int32_t* __restrict__ bias_ids,
+    const float* __restrict__ bias_values, const int32_t* __restrict__ cu_bias, int32_t bias_total,
+    float* __restrict__ logprobs, int32_t* __restrict__ top_ids, float* __restrict__ top_logprobs, int32_t score_k,
+    const int32_t* __restrict__ want, const uint32_t* __restrict__ allow_words, int32_t n_masks,
+    const int32_t* __restrict__ mask_row) {
+  constexpr bool CONSTRAINED = true;
+  constexpr bool SCORED = true;
+  constexpr bool MASKED = true;
 #include "sampling_body.inc"
 }
 
@@ -134,8 +165,8 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_rows_logprobs_kernel(
 
 using namespace hx;
 
-// What the three entries are called with.  hx_sample_rows comes with no bias table (bias_total 0); only
-// hx_sample_rows_logprobs fills the score fields.
+// What the four entries are called with.  hx_sample_rows comes with no bias table (bias_total 0); only
+// hx_sample_rows_logprobs and hx_sample_rows_masked fill the score fields, only the latter the mask fields.
 struct SampleArgs {
   int64_t* ids; float* cut_out; float* u_out;
   const void* logits; int64_t rows, n, ld;
@@ -144,12 +175,16 @@ struct SampleArgs {
   const void* sample_params;
   float* logprobs; int32_t* top_ids; float* top_logprobs; int top_k; const int32_t* want;
   int dtype; hipStream_t stream;
+  const uint32_t* allow_words = nullptr; int64_t n_masks = 0; const int32_t* mask_row = nullptr;
 };
-enum SampleKernel { SMP_PLAIN, SMP_CONSTRAINED, SMP_SCORED };
+enum SampleKernel { SMP_PLAIN, SMP_CONSTRAINED, SMP_SCORED, SMP_MASKED };
 
-// The argument checks: top_k's range in front of everything for the scored entry, then shape, dtype, null pointers.
+// The argument checks: top_k's range in front of everything for the scored entry, then shape, dtype, null pointers.  The
+// masked entry is scored when it comes with logprobs: the scored entry's rules hold then, none of them otherwise.
 static int sample_rows_check(SampleKernel which, const SampleArgs& a) {
-  if (which == SMP_SCORED && (a.top_k < 0 || a.top_k > 20)) return HX_ERR_SHAPE;
+  const bool scored = which == SMP_SCORED || (which == SMP_MASKED && a.logprobs);
+  if (scored && (a.top_k < 0 || a.top_k > 20)) return HX_ERR_SHAPE;
+  if (which == SMP_MASKED && (a.n_masks < 0 || a.n_masks > 0x7fffffff)) return HX_ERR_SHAPE;
   if (a.rows < 1 || a.n < 1 || a.ld < a.n || a.n > SAMPLE_MAX_N || a.rows > 0x7fffffff || a.total < 0 ||
       a.total > 0x7fffffff || a.bias_total < 0 || a.bias_total > 0x7fffffff)
     return HX_ERR_SHAPE;
@@ -158,7 +193,8 @@ static int sample_rows_check(SampleKernel which, const SampleArgs& a) {
       (a.total > 0 && (!a.hist_ids || !a.hist_counts || !a.cu_hist || !a.penalties)) ||
       (a.bias_total > 0 && (!a.bias_ids || !a.bias_values || !a.cu_bias)))
     return HX_ERR_NULL;
-  if (which == SMP_SCORED && (!a.logprobs || (a.top_k > 0 && (!a.top_ids || !a.top_logprobs)))) return HX_ERR_NULL;
+  if (scored && (!a.logprobs || (a.top_k > 0 && (!a.top_ids || !a.top_logprobs)))) return HX_ERR_NULL;
+  if (which == SMP_MASKED && (!a.mask_row || (a.n_masks > 0 && !a.allow_words))) return HX_ERR_NULL;
   return HX_OK;
 }
 
@@ -177,12 +213,18 @@ static int launch_sample_rows(SampleKernel which, const SampleArgs& a) {
     return launch_lds(sample_rows_constrained_kernel<T>, rows, SMP_THREADS, lds, a.stream, a.ids, a.cut_out, a.u_out, logits,
                       n, a.ld, a.hist_ids, a.hist_counts, a.cu_hist, total, a.penalties, params, a.bias_ids, a.bias_values,
                       a.cu_bias, bias_total);
-  return launch_lds(sample_rows_logprobs_kernel<T>, rows, SMP_THREADS, lds, a.stream, a.ids, a.cut_out, a.u_out, logits, n,
+  if (which == SMP_SCORED)
+    return launch_lds(sample_rows_logprobs_kernel<T>, rows, SMP_THREADS, lds, a.stream, a.ids, a.cut_out, a.u_out, logits, n,
+                      a.ld, a.hist_ids, a.hist_counts, a.cu_hist, total, a.penalties, params, a.bias_ids, a.bias_values,
+                      a.cu_bias, bias_total, a.logprobs, a.top_ids, a.top_logprobs, (int32_t)a.top_k, a.want);
+  const int32_t score_k = a.logprobs ? (int32_t)a.top_k : 0;      // (unscored: top_ids, top_logprobs and want are not read)
+  return launch_lds(sample_rows_masked_kernel<T>, rows, SMP_THREADS, lds, a.stream, a.ids, a.cut_out, a.u_out, logits, n,
                     a.ld, a.hist_ids, a.hist_counts, a.cu_hist, total, a.penalties, params, a.bias_ids, a.bias_values,
-                    a.cu_bias, bias_total, a.logprobs, a.top_ids, a.top_logprobs, (int32_t)a.top_k, a.want);
+                    a.cu_bias, bias_total, a.logprobs, a.top_ids, a.top_logprobs, score_k, a.logprobs ? a.want : nullptr,
+                    a.allow_words, (int32_t)a.n_masks, a.mask_row);
 }
 
-// All three entries: the argument checks, then the launch by dtype.
+// All four entries: the argument checks, then the launch by dtype.
 static int sample_rows(SampleKernel which, const SampleArgs& a) {
   const int rc = sample_rows_check(which, a);
   if (rc != HX_OK) return rc;
@@ -217,4 +259,16 @@ extern "C" int hx_sample_rows_logprobs(int64_t* ids, float* cut_out, float* u_ou
   return sample_rows(SMP_SCORED, {ids, cut_out, u_out, logits, rows, n, ld, hist_ids, hist_counts, cu_hist, total, penalties,
                                   bias_ids, bias_values, cu_bias, bias_total, sample_params, logprobs, top_ids, top_logprobs,
                                   top_k, want, dtype, (hipStream_t)stream});
+}
+
+extern "C" int hx_sample_rows_masked(int64_t* ids, float* cut_out, float* u_out, const void* logits, int64_t rows, int64_t n,
+                                     int64_t ld, const int32_t* hist_ids, const int32_t* hist_counts, const int32_t* cu_hist,
+                                     int64_t total, const float* penalties, const int32_t* bias_ids, const float* bias_values,
+                                     const int32_t* cu_bias, int64_t bias_total, const void* sample_params, float* logprobs,
+                                     int32_t* top_ids, float* top_logprobs, int top_k, const int32_t* want,
+                                     const uint32_t* allow_words, int64_t n_masks, const int32_t* mask_row, int dtype,
+                                     hx_stream stream) {
+  return sample_rows(SMP_MASKED, {ids, cut_out, u_out, logits, rows, n, ld, hist_ids, hist_counts, cu_hist, total, penalties,
+                                  bias_ids, bias_values, cu_bias, bias_total, sample_params, logprobs, top_ids, top_logprobs,
+                                  top_k, want, dtype, (hipStream_t)stream, allow_words, n_masks, mask_row});
 }

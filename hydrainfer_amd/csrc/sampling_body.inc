@@ -1,8 +1,9 @@
 // sampling_body.inc — the body of sampling.hip's kernel, included into sample_rows_kernel (CONSTRAINED = false),
-// sample_rows_constrained_kernel (CONSTRAINED = true) and sample_rows_logprobs_kernel (CONSTRAINED and SCORED).  Expects the
+// sample_rows_constrained_kernel (CONSTRAINED = true), sample_rows_logprobs_kernel (CONSTRAINED and SCORED) and
+// sample_rows_masked_kernel (CONSTRAINED, SCORED and MASKED).  Expects the
 // kernels' arguments (bias_ids, bias_values, cu_bias, bias_total included: null and 0 in sample_rows_kernel, where no
-// statement that names them is compiled; logprobs, top_ids, top_logprobs, score_k, want likewise where SCORED is false),
-// T, CONSTRAINED and SCORED in scope.
+// statement that names them is compiled; logprobs, top_ids, top_logprobs, score_k, want likewise where SCORED is false;
+// allow_words, n_masks, mask_row likewise where MASKED is false), T, CONSTRAINED, SCORED and MASKED in scope.
   extern __shared__ __attribute__((aligned(16))) float zs[];      // the row as fp32, n elements (rounded up to 8)
   __shared__ float part_f[2][SMP_WAVES];
   __shared__ int part_i[2][SMP_WAVES];
@@ -20,7 +21,8 @@
   const float u = (float)(smp_philox0(rec[6], rec[7], rec[4], rec[5]) >> 8) * 0x1p-24f;
   const bool sampled = temperature > 0.f;                          // (a NaN or a negative temperature: greedy)
   // SCORED: the row's scores are wanted (the same in every thread); a greedy row is then scored as T = 1 over all of it
-  const bool scored = SCORED && (want == nullptr || want[row] >= 0);
+  // (MASKED: scoring is optional per launch as well — with logprobs null no row is scored and want is not read)
+  const bool scored = SCORED && (!MASKED || logprobs != nullptr) && (want == nullptr || want[row] >= 0);
   const float tdiv = SCORED && !sampled ? 1.f : temperature;
 
   // 1. the row into LDS as fp32: 16-byte loads, four in flight, like argmax_rows_kernel
@@ -48,6 +50,32 @@
     for (int i = tid; i < n; i += SMP_THREADS) zs[i] = T::to_float(p[i]);
   }
   __syncthreads();
+
+  // 1a. MASKED: every element of a masked row whose bit is clear becomes -inf, ahead of everything that looks at the
+  // row.  Byte i of the row's mask (little-endian words: bits 8 i .. 8 i + 7) covers the eight elements a thread holds
+  // as two f32x4 of LDS; the mask's (n + 7) / 8 bytes are read from global memory once, nothing of it for a row whose
+  // index names no mask.  Bits at or above n fall on the row's padding (rounded up to 8), which nothing reads.
+  if (MASKED) {
+    const int32_t mr = mask_row[row];
+    if (mr >= 0 && mr < n_masks) {                                 // the same in every thread of the workgroup
+      const uint8_t* mb = reinterpret_cast<const uint8_t*>(allow_words + (int64_t)mr * ((n + 31) >> 5));
+      const int nbytes = (n + 7) >> 3;
+      for (int i = tid; i < nbytes; i += SMP_THREADS) {
+        const uint32_t bits = mb[i];
+        if (bits != 0xffu) {
+          f32x4 a = *reinterpret_cast<f32x4*>(zs + i * 8), b = *reinterpret_cast<f32x4*>(zs + i * 8 + 4);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            a[e] = (bits >> e) & 1u ? a[e] : -INFINITY;
+            b[e] = (bits >> (4 + e)) & 1u ? b[e] : -INFINITY;
+          }
+          *reinterpret_cast<f32x4*>(zs + i * 8) = a;
+          *reinterpret_cast<f32x4*>(zs + i * 8 + 4) = b;
+        }
+      }
+      __syncthreads();
+    }
+  }
 
   // 1b. the row's slice of the bias table, held inside [0, bias_total] like the history: x + b, one fp32 addition per
   // entry, one entry per thread; the barrier because a token may be in both tables and the penalties start from x + b
@@ -111,7 +139,7 @@
   const float m = best / tdiv;
   if (SCORED) {                                                    // no scores: the fill values, and on as without them
     const bool degenerate = best != best || !(fabsf(m) < INFINITY);
-    if (!scored || degenerate) {
+    if ((!scored || degenerate) && (!MASKED || logprobs != nullptr)) {   // (MASKED without scores: nothing to fill)
       if (tid == 0) logprobs[row] = __builtin_nanf("");
       if (tid < score_k) {
         top_ids[row * score_k + tid] = -1;

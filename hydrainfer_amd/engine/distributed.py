@@ -88,6 +88,17 @@ def refuse_constraints(request) -> None:
                          "offline engine")
 
 
+def refuse_token_mask(request) -> None:
+    """Nor token masks (allowed_token_ids, guided_choice): the wire format carries neither the masks nor the trie node a
+    request stands on, which would have to follow it from rank to rank.  A request that sets neither passes."""
+    sp = getattr(request, "sampling_params", None)
+    if sp is not None and (getattr(sp, "allowed_token_ids", None) is not None
+                           or getattr(sp, "guided_choice", None) is not None):
+        raise ValueError(f"request {request.request_id}: allowed_token_ids / guided_choice are not available in "
+                         "multi-process serving (one engine process per GPU); use the single-process server or the "
+                         "offline engine")
+
+
 def rcb_to_wire(rcb: RequestControlBlock) -> dict:
     """Everything the next stage needs: the instructions from the current one on (a flat list —
     the linked chain would pickle recursively), the block tables + IPC handles of the caches, the
@@ -342,6 +353,7 @@ class RankEngine:
         refuse_sampling(request)
         refuse_prompt_logprobs(request)
         refuse_constraints(request)
+        refuse_token_mask(request)
         self.token_handlers[request.request_id] = processor
         has_image = request.pixel_values is not None
         dst = entry_rank(self._n_submitted[has_image], self.roles, has_image, self.dead)

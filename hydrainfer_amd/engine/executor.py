@@ -22,8 +22,9 @@ from hydrainfer_amd.engine.parameters_builder import LanguageModelParametersBuil
 from hydrainfer_amd.engine.rcb import PROCESSED_LOGPROBS, BatchRequest, PromptTokenLogprob, TokenLogprob
 from hydrainfer_amd.model.llama import LanguageModelParameters
 # (the packers and kernels are reached by name: SAMPLING_MODES)
-from hydrainfer_amd.sampling import (GREEDY_RECORD, NO_PENALTIES, pack_constrained_step, pack_penalty_step, pack_sample_step,
-                                     penalized_argmax_rows, sample_rows, sample_rows_constrained, sample_rows_logprobs)
+from hydrainfer_amd.sampling import (GREEDY_RECORD, NO_PENALTIES, pack_constrained_step, pack_masked_step, pack_penalty_step,
+                                     pack_sample_step, penalized_argmax_rows, sample_rows, sample_rows_constrained,
+                                     sample_rows_logprobs, sample_rows_masked)
 
 
 # What the table-driven modes of the eager sampling step (BatchFillExecutor._sample) differ in: how many elements of a
@@ -73,6 +74,14 @@ def scored_rows(rows) -> bool:
     hx_sample_rows_logprobs launch for the whole batch (BatchFillExecutor._sample_scored), whatever step_mode says —
     this decision is consulted first."""
     return any(asks_processed(rcb) and not inst.is_chunked for rcb, inst in rows)
+
+
+def masked_rows(rows) -> bool:
+    """rows: the sampling (rcb, inst) pairs of an eager step.  True when some request carries a token mask
+    (allowed_token_ids, guided_choice) and delivers a token this step (a chunk head's sample is discarded): the step then
+    runs ONE hx_sample_rows_masked launch for the whole batch (BatchFillExecutor._sample_masked) — consulted ahead of
+    scored_rows.  Read with a default: a stand-in for a request need not carry the attribute."""
+    return any(getattr(rcb, "token_mask", None) is not None and not inst.is_chunked for rcb, inst in rows)
 
 
 class PendingToken:
@@ -141,9 +150,10 @@ class BatchFillExecutor:
         for rcb, inst in batch:
             if (len(inst.token_ids) != 1 or not inst.sample or rcb.sampling_params.logprobs
                     or rcb.penalty_history is not None or rcb.sampling_params.temperature > 0
-                    or inst.score_targets is not None or rcb.token_constraints is not None):
+                    or inst.score_targets is not None or rcb.token_constraints is not None
+                    or getattr(rcb, "token_mask", None) is not None):
                 return None                    # (a request that wants log-probabilities, one under sampling penalties,
-                                               # a sampled or a constrained one decodes eagerly: execute(); so does a one-token piece
+                                               # a sampled, a constrained or a masked one decodes eagerly: execute(); so does a one-token piece
                                                # of a prompt that is being scored — decode Fills carry no score list)
             token = inst.token_ids[0]
             if isinstance(token, PendingToken):
@@ -338,6 +348,9 @@ class BatchFillExecutor:
                 rcb.output_token_ids.append(token)
                 if rcb.penalty_history is not None:
                     rcb.penalty_history.append(token)           # generated tokens only: a chunk head's sample never gets here
+                if getattr(rcb, "token_mask", None) is not None:
+                    rcb.token_mask.advance(token)               # guided_choice: on to the child; a complete choice ends the
+                                                                # request (rcb.is_finished), as an end-of-sequence id does
                 if scores is not None and rcb.sampling_params.logprobs:
                     k = rcb.sampling_params.top_logprobs        # this request's own count out of the batch's largest
                     entry = TokenLogprob(token, scores[0][i], list(zip(scores[1][i][:k], scores[2][i][:k])))
@@ -492,11 +505,56 @@ class BatchFillExecutor:
                         col[row] = raw_col[row]
         return self._pick(geometry, sampled, scores)
 
+    def _sample_masked(self, batch: BatchRequest, inputs, params, logits=None):
+        """The eager step of a batch in which some request carries a token mask (masked_rows) -> (sampled, scores).  The
+        same logits, then ONE hx_sample_rows_masked launch for the whole batch, modelled on _sample_scored: the
+        four-element entries of the constrained mode, want = -1 on every row but those of the processed-logprobs requests
+        that deliver a token, mask_row = -1 on every row without a mask (a chunk head's discarded sample included); rows on
+        the same trie node share one mask of the step.  The tables, `want`, `mask_row` and the step's distinct masks reach
+        the device as one pinned buffer in one copy.  With no processed request in the batch the launch is unscored and
+        only the ids come back.  RAW-mode logprobs requests beside them keep hx_logprob_rows over the raw logits."""
+        rows = sampling_rows(batch)
+        geometry = sel, decode, n_rows = self._step_rows(inputs, logits)
+        entries, at = self._step_entries(batch, sel, decode, n_rows, 4)
+        entries = [e + (-1, None) for e in entries]
+        top_k, raw = None, []                   # the processed requests' K (None: nobody asks); the raw-mode requests' top_logprobs
+        for row, (rcb, inst) in zip(at, rows):
+            if inst.is_chunked:
+                continue
+            sp, mask = rcb.sampling_params, getattr(rcb, "token_mask", None)
+            want = -1
+            if sp.logprobs and asks_processed(rcb):
+                want, top_k = 0, max(top_k or 0, sp.top_logprobs)
+            elif sp.logprobs:
+                raw.append(sp.top_logprobs)
+            entries[row] = entries[row][:4] + (want, mask.current() if mask is not None else None)
+        *tables, want = pack_masked_step(entries).to_device(self.device)
+        if logits is None:
+            logits = self.language_model.forward_logits(inputs.input_ids, inputs.image_features, inputs.position_ids, params)
+        if raw:
+            raw_packed = self._raw_scores(logits, max(raw))
+        if top_k is None:
+            sampled, scores = sample_rows_masked(logits, *tables).tolist(), None
+            if raw:
+                scores = [[float("nan")] * n_rows, [[]] * n_rows, [[]] * n_rows]
+        else:
+            ids = sample_rows_masked(logits, *tables, top_k=top_k, want=want)[0]
+            sampled, *scores = self._to_host(logprob_rows_packed(ids, top_k), n_rows, top_k)
+        if raw:
+            raw_scores = self._to_host(raw_packed, n_rows, max(raw))[1:]
+            for row, (rcb, _) in zip(at, rows):
+                if rcb.sampling_params.logprobs and not asks_processed(rcb):
+                    for col, raw_col in zip(scores, raw_scores):
+                        col[row] = raw_col[row]
+        return self._pick(geometry, sampled, scores)
+
     def _choose(self, batch: BatchRequest, inputs, params, logits=None):
         """What an eager step that samples runs -> (sampled, scores): the ONE place that decides it, for execute and for
-        _execute_scoring (logits: as in _step_rows).  scored_rows first, then step_mode, then the plain argmax — the
-        language model's own when it runs the forward, the step's only device sync."""
+        _execute_scoring (logits: as in _step_rows).  masked_rows first, then scored_rows, then step_mode, then the plain
+        argmax — the language model's own when it runs the forward, the step's only device sync."""
         rows = sampling_rows(batch)
+        if masked_rows(rows):
+            return self._sample_masked(batch, inputs, params, logits)
         if scored_rows(rows):
             return self._sample_scored(batch, inputs, params, logits)
         mode, top_k = step_mode(rows)

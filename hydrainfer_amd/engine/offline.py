@@ -31,6 +31,8 @@ class OfflineInferenceOutput:
     prompt_logprobs: List[Optional[PromptTokenLogprob]] = field(default_factory=list)
 
 
+@keyword_argument("guided_choice")
+@keyword_argument("allowed_token_ids")
 @keyword_argument("logprobs_mode")
 @dataclass
 class OfflineRequest:
@@ -59,6 +61,11 @@ class OfflineRequest:
     # constraints); "processed_logprobs": the distribution the token was chosen from, combinable with all of them
     # (init=False and the class's keyword_argument decorator: taken by keyword only, the generated signature as it was)
     logprobs_mode: Optional[str] = field(default=None, init=False)
+    # token masks, by keyword only like logprobs_mode.  allowed_token_ids: the only token ids the request may emit;
+    # guided_choice: token id SEQUENCES (there is no tokenizer offline) of which the request emits exactly one and ends
+    # there.  At most one of the two; such a request decodes eagerly
+    allowed_token_ids: Optional[List[int]] = field(default=None, init=False)
+    guided_choice: Optional[List[List[int]]] = field(default=None, init=False)
     prompt_logprobs: Optional[int] = None   # 0..20: the log-probability of every prompt token given what stands before it,
                                             # with that many alternatives per position; combinable with everything above
 
@@ -84,7 +91,7 @@ class OfflineInferenceEngine:
                                           n_image_tokens_per_image=self.n_image_tokens, block_size=16, ignore_eos=True,
                                           max_position_embeddings=shape.max_position_embeddings)
         self.processor = ClipImageProcessor(size=vision_model.shape.image_size)
-        self.vocab_size = getattr(shape, "vocab_size", None)      # logit_bias ids are checked against it
+        self.vocab_size = getattr(shape, "vocab_size", None)      # logit_bias ids and token masks are checked against it
         if warm_up:
             warm_library_gemms(language_model, token_budgets, max_running_requests)
             size = vision_model.shape.image_size
@@ -112,7 +119,9 @@ class OfflineInferenceEngine:
                                                                       r.temperature, r.top_p, r.top_k, r.seed,
                                                                       prompt_logprobs=r.prompt_logprobs,
                                                                       logit_bias=r.logit_bias, min_tokens=r.min_tokens,
-                                                                      min_p=r.min_p, logprobs_mode=r.logprobs_mode),
+                                                                      min_p=r.min_p, logprobs_mode=r.logprobs_mode,
+                                                                      allowed_token_ids=r.allowed_token_ids,
+                                                                      guided_choice=r.guided_choice),
                                    token_params=r.token_params)
                 rcb = self.creator.process(req, vocab_size=self.vocab_size)
                 rcb.metric.arrival_time = time.perf_counter()

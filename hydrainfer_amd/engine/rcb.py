@@ -10,6 +10,8 @@ from hydrainfer_amd.memory.token_cache import VirtualTokenCache
 from hydrainfer_amd.utils import keyword_argument
 
 
+@keyword_argument("guided_choice")
+@keyword_argument("allowed_token_ids")
 @keyword_argument("logprobs_mode")
 @dataclass
 class SamplingParameters:
@@ -49,6 +51,14 @@ class SamplingParameters:
     # the same launch that chooses the token); needs logprobs, combines with all of the above.  prompt_logprobs stays raw.
     # (init=False and the class's keyword_argument decorator: taken by keyword only, the generated signature as it was)
     logprobs_mode: Optional[str] = field(default=None, init=False)
+    # token masks (hx_sample_rows_masked, include/hydra_hip.h; vLLM's names): the request may only emit tokens of a set.
+    # allowed_token_ids: one set, every step.  guided_choice: the request emits exactly one of several token SEQUENCES
+    # (1..64 of 1..64 ids, none a prefix of another) and ends there; cut short by max_tokens it emits a truncated choice.
+    # At most one of the two.  Such a request decodes eagerly and can ask for logprobs only with logprobs_mode =
+    # "processed_logprobs" (the scores are then those over the allowed set); prompt_logprobs stays combinable.
+    # (init=False and keyword_argument, like logprobs_mode: by keyword only, the generated signature as it was)
+    allowed_token_ids: Optional[List[int]] = field(default=None, init=False)
+    guided_choice: Optional[List[List[int]]] = field(default=None, init=False)
     # the log-probability of every PROMPT token given what stands before it (vLLM's `prompt_logprobs`;
     # hx_token_logprob_rows over the prefill's logits): None = off, 0..20 = score, with that many alternatives per position.
     # Independent of `logprobs` and of the sampling mode: scoring reads the prompt's rows, sampling the last one.  Such a
@@ -190,6 +200,7 @@ class RequestControlBlock:
         self.prompt_logprobs: List[Optional[PromptTokenLogprob]] = []
         self.penalty_history = None      # sampling.PenaltyHistory of a penalised request (its delivered tokens), else None
         self.token_constraints = None    # sampling.TokenConstraints of a constrained request (logit_bias, min_tokens, min_p), else None
+        self.token_mask = None           # sampling.TokenMask of a request with allowed_token_ids / guided_choice, else None
         self.scenario_type: Optional[ScenarioType] = None
         self.metric = RequestMetric()
         self.eos_hit = False      # set when a token read back late (decode look-ahead) was end-of-sequence
@@ -207,6 +218,8 @@ class RequestControlBlock:
 
     def is_finished(self) -> bool:
         if self.instructions.curr is None or self.eos_hit:
+            return True
+        if self.token_mask is not None and self.token_mask.finished:           # guided_choice: the choice is complete
             return True
         if len(self.output_token_ids) >= self.sampling_params.max_tokens:      # (>=: a cancelled stream lowers max_tokens, api_server.py)
             return True

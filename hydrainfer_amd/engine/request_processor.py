@@ -12,8 +12,8 @@ from hydrainfer_amd.engine.isa import (EPMigrate, ImageEmbed, ImageEmbedFill, In
 from hydrainfer_amd.engine.rcb import (MAX_TOP_LOGPROBS, PROCESSED_LOGPROBS, RequestControlBlock, RequestMetaData,
                                        SamplingParameters, ScenarioClassifier, TokenParameters, check_logprobs_mode)
 from hydrainfer_amd.memory.shared_cache import compute_hash
-from hydrainfer_amd.sampling import (PenaltyHistory, TokenConstraints, check_constraints, check_penalties, check_sampling,
-                                     is_constrained, is_penalized, is_sampled)
+from hydrainfer_amd.sampling import (PenaltyHistory, TokenConstraints, TokenMask, check_constraints, check_penalties,
+                                     check_sampling, check_token_mask, is_constrained, is_penalized, is_sampled)
 
 
 @dataclass
@@ -108,7 +108,8 @@ class InstructionCreator:
 
     def process(self, request: TokenRequest, vocab_size: Optional[int] = None) -> RequestControlBlock:
         """vocab_size: None (unchecked), or the number of tokens the model scores: a logit_bias id at or above it is
-        refused (the kernel would ignore it: the client would never learn that the bias did nothing)."""
+        refused (the kernel would ignore it: the client would never learn that the bias did nothing).  A request with
+        allowed_token_ids or guided_choice needs it: its masks are as wide as the rows they mask."""
         rcb = RequestControlBlock()
         rcb.request_id = request.request_id
         sp = request.sampling_params or SamplingParameters()
@@ -128,11 +129,14 @@ class InstructionCreator:
             penalties = check_penalties(sp.frequency_penalty, sp.presence_penalty, sp.repetition_penalty)
             sampling = check_sampling(sp.temperature, sp.top_p, sp.top_k, sp.seed)
             logit_bias, min_tokens, min_p = check_constraints(sp.logit_bias, sp.min_tokens, sp.min_p)
+            allowed, choices = check_token_mask(getattr(sp, "allowed_token_ids", None), getattr(sp, "guided_choice", None),
+                                                vocab_size)
         except ValueError as e:
             raise ValueError(f"request {request.request_id}: {e}") from None
         rcb.sampling_params = SamplingParameters(sp.max_tokens, list(sp.eos_token_ids), sp.logprobs, top, *penalties,
                                                  *sampling, prompt_logprobs=ask, logit_bias=logit_bias,
-                                                 min_tokens=min_tokens, min_p=min_p, logprobs_mode=mode)
+                                                 min_tokens=min_tokens, min_p=min_p, logprobs_mode=mode,
+                                                 allowed_token_ids=allowed, guided_choice=choices)
         # raw scores (hx_logprob_rows) describe the raw argmax: refused beside anything that changes the choice.  The
         # processed mode scores the choice itself (hx_sample_rows_logprobs) and combines with all of it.
         raw_scores = sp.logprobs and mode != PROCESSED_LOGPROBS
@@ -147,6 +151,15 @@ class InstructionCreator:
                              "logprobs yet: hx_logprob_rows scores the raw logits and names the raw argmax, not the "
                              "constrained choice (prompt_logprobs, which scores the prompt from raw logits by "
                              "definition, can be)" + hint)
+        masked = allowed is not None or choices is not None
+        if raw_scores and masked:
+            raise ValueError(f"request {request.request_id}: allowed_token_ids / guided_choice cannot be combined with "
+                             "logprobs yet: hx_logprob_rows scores the raw logits and names the raw argmax, not the "
+                             "masked choice (prompt_logprobs, which scores the prompt from raw logits by definition, "
+                             "can be)" + hint)
+        if choices is not None and min_tokens > 0:
+            raise ValueError(f"request {request.request_id}: min_tokens cannot be combined with guided_choice: the "
+                             "request ends where its choice ends")
         if is_sampled(rcb.sampling_params):
             if raw_scores:
                 raise ValueError(f"request {request.request_id}: temperature > 0 cannot be combined with logprobs yet: "
@@ -165,6 +178,13 @@ class InstructionCreator:
             rcb.sampling_params.eos_token_ids.append(self.eos_token_id)
         if is_constrained(rcb.sampling_params):       # (after the server's own end-of-sequence id: min_tokens holds it back too)
             rcb.token_constraints = TokenConstraints(logit_bias, rcb.sampling_params.eos_token_ids, min_tokens)
+        if masked:
+            # (after the server's own end-of-sequence id as well) min_tokens bans every end-of-sequence id for a while: a set
+            # of nothing else would leave the row all -inf — the kernel's degenerate row, whose id 0 may lie outside the set
+            if allowed is not None and min_tokens > 0 and set(allowed) <= set(rcb.sampling_params.eos_token_ids):
+                raise ValueError(f"request {request.request_id}: min_tokens = {min_tokens} with allowed_token_ids that are "
+                                 "all end-of-sequence ids leaves no token to emit")
+            rcb.token_mask = TokenMask(vocab_size, allowed, choices)
 
         has_image = request.pixel_values is not None
         n_keep = self._pruned_count(request)

@@ -21,12 +21,15 @@ MAX_TOP_LOGPROBS = 20              # OpenAI's limit
 PROCESSED_LOGPROBS = "processed_logprobs"
 LOGPROBS_MODES = ("raw_logprobs", PROCESSED_LOGPROBS)      # `logprobs_mode` (vLLM's names; engine/rcb.py)
 MAX_STOP_TOKEN_IDS = 16
+MAX_GUIDED_CHOICES = 64            # `guided_choice` (hydrainfer_amd/sampling)
 
 
 class ProtocolError(ValueError):
     """A request the reference would reject (its asserts / pydantic validation -> HTTP 4xx / 500 there; 400 here)."""
 
 
+@keyword_argument("guided_choice")
+@keyword_argument("allowed_token_ids")
 @keyword_argument("logprobs_mode")
 @dataclass
 class ChatRequest:
@@ -57,6 +60,11 @@ class ChatRequest:
     # combinable with temperature > 0, penalties or constraints); "processed_logprobs": the one the token was chosen from
     # (init=False and the class's keyword_argument decorator: taken by keyword only, the generated signature as it was)
     logprobs_mode: Optional[str] = field(default=None, init=False)
+    # extensions (vLLM's names), by keyword only like logprobs_mode; at most one of the two.  allowed_token_ids: the only
+    # token ids the answer may consist of; guided_choice: strings of which the answer is exactly one (the server encodes
+    # them with its tokenizer).  Not combinable with raw-mode logprobs; guided_choice not with min_tokens
+    allowed_token_ids: Optional[List[int]] = field(default=None, init=False)
+    guided_choice: Optional[List[str]] = field(default=None, init=False)
     prompt_logprobs: Optional[int] = None   # extension (vLLM's name; OpenAI's chat API has no `echo`): 0..20 — the stream's
                                             # first chunk carries the score of every prompt token, with that many alternatives
 
@@ -171,13 +179,44 @@ def parse_chat_completion_request(body: dict) -> ChatRequest:
     constraints = _parse_constraints(body)
     if raw_scores and (constraints["logit_bias"] or constraints["min_tokens"] > 0 or constraints["min_p"] > 0):
         raise ProtocolError("logprobs cannot be combined with logit_bias / min_tokens / min_p yet" + hint)
+    masks = _parse_token_mask(body)
+    if raw_scores and (masks["allowed_token_ids"] is not None or masks["guided_choice"] is not None):
+        raise ProtocolError("logprobs cannot be combined with allowed_token_ids / guided_choice yet" + hint)
+    if masks["guided_choice"] is not None and constraints["min_tokens"] > 0:
+        raise ProtocolError("min_tokens cannot be combined with guided_choice: the answer ends where the choice ends")
     try:
         png = base64.b64decode(images[0], validate=True) if images else None
     except Exception:
         raise ProtocolError("image_url: invalid base64")
     return ChatRequest(model=model, role=role, text=text, image_png=png, max_tokens=max_tokens,
                        stream=bool(body.get("stream", False)), logprobs=logprobs, top_logprobs=top_logprobs, **penalties, **sampling,
-                       prompt_logprobs=prompt_logprobs, logprobs_mode=logprobs_mode, **constraints)
+                       prompt_logprobs=prompt_logprobs, logprobs_mode=logprobs_mode, **constraints, **masks)
+
+
+def _parse_token_mask(body: dict) -> dict:
+    """allowed_token_ids and guided_choice of a request body, as ChatRequest's fields (None where absent)."""
+    allowed, choices = body.get("allowed_token_ids"), body.get("guided_choice")
+    if allowed is not None and choices is not None:
+        raise ProtocolError("allowed_token_ids and guided_choice cannot be combined")
+    if allowed is not None:
+        if not isinstance(allowed, list) or not allowed:
+            raise ProtocolError("allowed_token_ids: non-empty list of token ids required")
+        for t in allowed:
+            if isinstance(t, bool) or not isinstance(t, int) or not 0 <= t <= 0x7fffffff:
+                raise ProtocolError("allowed_token_ids: integers >= 0 required")
+        if len(set(allowed)) != len(allowed):
+            raise ProtocolError("allowed_token_ids: a token id stands twice")
+        allowed = list(allowed)
+    if choices is not None:
+        if not isinstance(choices, list) or not 1 <= len(choices) <= MAX_GUIDED_CHOICES:
+            raise ProtocolError(f"guided_choice: list of 1..{MAX_GUIDED_CHOICES} strings required")
+        for c in choices:
+            if not isinstance(c, str) or not c:
+                raise ProtocolError("guided_choice: non-empty strings required")
+        if len(set(choices)) != len(choices):
+            raise ProtocolError("guided_choice: a choice stands twice")
+        choices = list(choices)
+    return {"allowed_token_ids": allowed, "guided_choice": choices}
 
 
 def _parse_constraints(body: dict) -> dict:

@@ -217,12 +217,13 @@ class RankEngineFrontend(EngineFrontend):
 
     def _start(self, request: TokenRequest, processor: StreamOutputTokenProcessor) -> None:
         from hydrainfer_amd.engine.distributed import (refuse_constraints, refuse_logprobs, refuse_penalties,
-                                                       refuse_prompt_logprobs, refuse_sampling)
+                                                       refuse_prompt_logprobs, refuse_sampling, refuse_token_mask)
         refuse_logprobs(request)                      # ValueError: the rank protocol carries no log-probabilities
         refuse_penalties(request)                     # nor sampling penalties
         refuse_sampling(request)                      # nor sampled decoding
         refuse_prompt_logprobs(request)               # nor prompt log-probabilities
         refuse_constraints(request)                   # nor logit_bias / min_tokens / min_p
+        refuse_token_mask(request)                    # nor allowed_token_ids / guided_choice
         self.engine.submit(request, processor, self.creator, self._index)
         self._index += 1
 
@@ -261,6 +262,19 @@ class ApiServer:
         if req.logit_bias and vocab_size is not None and max(req.logit_bias) >= vocab_size:
             # (the creator refuses it as well, but by then the stream is open: here the answer is still a 400)
             raise proto.ProtocolError(f"logit_bias: token id {max(req.logit_bias)} outside the vocabulary ({vocab_size})")
+        guided_choice = None
+        if req.allowed_token_ids is not None and vocab_size is not None and max(req.allowed_token_ids) >= vocab_size:
+            raise proto.ProtocolError(f"allowed_token_ids: token id {max(req.allowed_token_ids)} outside the vocabulary "
+                                      f"({vocab_size})")
+        if req.guided_choice is not None:
+            # the choices as token ids: the engine's trie walks what the model emits.  (No special tokens: a choice is a
+            # continuation of the prompt, not a text of its own.)
+            guided_choice = [self._encode_choice(c) for c in req.guided_choice]
+            from hydrainfer_amd.sampling import check_token_mask
+            try:
+                check_token_mask(None, guided_choice, vocab_size)
+            except ValueError as e:
+                raise proto.ProtocolError(str(e))
         pixels, image_hash, size = None, 0, tuple(self.image_size)
         if req.image_png is not None:
             from PIL import Image
@@ -287,7 +301,16 @@ class ApiServer:
                                                                prompt_logprobs=req.prompt_logprobs,
                                                                eos_token_ids=list(req.stop_token_ids or ()),
                                                                logit_bias=req.logit_bias, min_tokens=req.min_tokens,
-                                                               min_p=req.min_p, logprobs_mode=req.logprobs_mode))
+                                                               min_p=req.min_p, logprobs_mode=req.logprobs_mode,
+                                                               allowed_token_ids=req.allowed_token_ids,
+                                                               guided_choice=guided_choice))
+
+    def _encode_choice(self, text: str) -> list:
+        """One guided_choice string as token ids, by the tokenizer's `encode`; an empty encoding is refused."""
+        ids = [int(t) for t in self.tokenizer.encode(text)]
+        if not ids:
+            raise proto.ProtocolError(f"guided_choice: {text!r} encodes to no token")
+        return ids
 
     # ------------------------------------------------------------------ HTTP
     @staticmethod

@@ -26,7 +26,13 @@ request's table on the host (min_tokens: its end-of-sequence ids banned while to
 Scores of the processed distribution (`logprobs_mode = "processed_logprobs"`): `sample_rows_logprobs`
 (hx_sample_rows_logprobs) is `sample_rows_constrained` that also writes, for the rows that want it, the log-probability
 of the chosen token under the distribution it was chosen from and the K most likely alternatives of that distribution,
-in `logprob_rows`' packed layout."""
+in `logprob_rows`' packed layout.
+
+Token masks (`allowed_token_ids`, `guided_choice`): `sample_rows_masked` (hx_sample_rows_masked) is the scored launch with
+a per-row bitmask of the tokens a row may choose — 32 tokens per int32 word, 1 = allowed, the format grammar engines
+exchange — applied as -inf ahead of everything else; `TokenMask` holds a request's masks (one node, or a trie over its
+choices' token sequences) and where it stands, and `pack_masked_step` appends `want`, the rows' mask indices and the step's
+distinct masks to `pack_constrained_step`'s buffer."""
 import math
 from array import array
 from typing import Optional, Sequence, Tuple
@@ -483,3 +489,223 @@ def pack_constrained_step(entries) -> ConstrainedStep:
             buf[at + bias_total:at + bias_total + n] = np.asarray(b[1], dtype=np.float32).view(np.int32)
             at += n
     return ConstrainedStep(buf, rows, step.total, bias_total)
+
+
+# ---- token masks: allowed_token_ids, guided_choice (hx_sample_rows_masked, include/hydra_hip.h) ----
+MAX_GUIDED_CHOICES = 64         # choices of one request's guided_choice
+MAX_CHOICE_TOKENS = 64          # token ids of one choice
+
+
+def mask_words(n: int) -> int:
+    """The int32 words of one mask over n tokens: 32 tokens per word."""
+    return (n + 31) // 32
+
+
+def pack_mask_words(token_ids, n: int) -> np.ndarray:
+    """token_ids: distinct integers in 0 .. n - 1 -> uint32 [(n + 31) // 32], the format grammar engines exchange: bit
+    t & 31 of word t >> 5 is set when token t may be chosen; no bit at or above n is set.  ValueError otherwise."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+        raise ValueError(f"pack_mask_words: n {n!r} must be an integer >= 1")
+    ids = list(token_ids)
+    for t in ids:
+        if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, np.integer)) or not 0 <= t < n:
+            raise ValueError(f"pack_mask_words: token id {t!r} must be an integer in 0 .. {n - 1}")
+    if len(set(int(t) for t in ids)) != len(ids):
+        raise ValueError("pack_mask_words: a token id stands twice")
+    words = np.zeros(mask_words(n), dtype=np.uint32)
+    if ids:
+        t = np.asarray(ids, dtype=np.int64)
+        np.bitwise_or.at(words, t >> 5, np.left_shift(np.uint32(1), (t & 31).astype(np.uint32)))
+    return words
+
+
+def check_token_mask(allowed_token_ids, guided_choice, vocab_size: int):
+    """(allowed_token_ids, guided_choice) checked against the vocabulary, as lists of ints (None where not given), or
+    ValueError: both at once; allowed_token_ids not a non-empty list of distinct integers in 0 .. vocab_size - 1 (a bool
+    is no integer); guided_choice not 1..MAX_GUIDED_CHOICES distinct sequences of 1..MAX_CHOICE_TOKENS such ids (within
+    a choice an id may repeat), or a choice that is a prefix of another: the trie would have to decide between stopping
+    and going on."""
+    if allowed_token_ids is None and guided_choice is None:
+        return None, None
+    if allowed_token_ids is not None and guided_choice is not None:
+        raise ValueError("allowed_token_ids and guided_choice cannot be combined: a request takes one of them")
+    if isinstance(vocab_size, bool) or not isinstance(vocab_size, int) or vocab_size < 1:
+        raise ValueError("allowed_token_ids / guided_choice need the size of the vocabulary the model scores")
+
+    def ids_of(what, seq, most=None):
+        if not isinstance(seq, (list, tuple)) or not seq or (most is not None and len(seq) > most):
+            raise ValueError(f"{what} must be a list of 1{'' if most is None else f'..{most}'} token ids")
+        for t in seq:
+            if isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < vocab_size:
+                raise ValueError(f"{what}: token id {t!r} must be an integer in 0 .. {vocab_size - 1}")
+        return list(seq)
+
+    if allowed_token_ids is not None:
+        allowed = ids_of("allowed_token_ids", allowed_token_ids)
+        if len(set(allowed)) != len(allowed):
+            raise ValueError("allowed_token_ids: a token id stands twice")
+        return allowed, None
+    if not isinstance(guided_choice, (list, tuple)) or not 1 <= len(guided_choice) <= MAX_GUIDED_CHOICES:
+        raise ValueError(f"guided_choice must be a list of 1..{MAX_GUIDED_CHOICES} token id sequences")
+    choices = [ids_of(f"guided_choice[{i}]", c, MAX_CHOICE_TOKENS) for i, c in enumerate(guided_choice)]
+    if len(set(tuple(c) for c in choices)) != len(choices):
+        raise ValueError("guided_choice: a choice stands twice")
+    ordered = sorted(choices)                   # a prefix sorts directly in front of one of its extensions
+    for a, b in zip(ordered, ordered[1:]):
+        if b[:len(a)] == a:
+            raise ValueError(f"guided_choice: {a} is a prefix of {b}: the request could not tell stopping from going on")
+    return None, choices
+
+
+class TokenMask:
+    """A request's token masks and where it stands in them, on the host; built ONCE, at admission.  allowed_token_ids:
+    one node whose mask holds every step, never finished.  guided_choice: a trie over the choices' token sequences, the
+    mask of a node being its children's ids; `advance` follows the delivered token to the child and `finished` turns
+    true at a leaf — the end of exactly one choice, no choice being a prefix of another (check_token_mask).
+    `current()` is the SAME array object every time for the same node: a step deduplicates masks by identity."""
+    __slots__ = ("n", "words", "children", "node", "finished")
+
+    def __init__(self, n: int, allowed_token_ids=None, guided_choice=None):
+        if (allowed_token_ids is None) == (guided_choice is None):
+            raise ValueError("TokenMask: one of allowed_token_ids and guided_choice")
+        self.n, self.node, self.finished = n, 0, False
+        if allowed_token_ids is not None:
+            self.words, self.children = [pack_mask_words(allowed_token_ids, n)], None
+            return
+        children = [{}]                         # per node: token -> child node
+        for choice in guided_choice:
+            at = 0
+            for t in choice:
+                nxt = children[at].get(t)
+                if nxt is None:
+                    nxt = children[at][t] = len(children)
+                    children.append({})
+                at = nxt
+        self.children = children
+        self.words = [pack_mask_words(c.keys(), n) if c else None for c in children]
+
+    def current(self) -> np.ndarray:
+        """The mask words (uint32 [(n + 31) // 32]) of the node the request stands on."""
+        if self.finished:
+            raise ValueError("TokenMask: the choice is complete, nothing more may be chosen")
+        return self.words[self.node]
+
+    def advance(self, token: int) -> None:
+        """The request delivered `token`: on to the child (allowed_token_ids: the one node stays)."""
+        if self.children is None:
+            return
+        nxt = self.children[self.node].get(token) if not self.finished else None
+        if nxt is None:
+            raise ValueError(f"TokenMask: token {token!r} is not among the tokens the request may choose here")
+        self.node = nxt
+        self.finished = not self.children[nxt]
+
+
+def sample_rows_masked(logits: Tensor, sample_params: Tensor, bias_ids: Tensor, bias_values: Tensor, cu_bias: Tensor,
+                       allow_words: Tensor, mask_row: Tensor, hist_ids: Optional[Tensor] = None,
+                       hist_counts: Optional[Tensor] = None, cu_hist: Optional[Tensor] = None,
+                       penalties: Optional[Tensor] = None, *, top_k: Optional[int] = None, want: Optional[Tensor] = None,
+                       out: Optional[Tensor] = None, cut_out: Optional[Tensor] = None, u_out: Optional[Tensor] = None):
+    """`sample_rows_constrained` / `sample_rows_logprobs` under per-row token masks, still one launch
+    (include/hydra_hip.h: hx_sample_rows_masked).  allow_words: int32 / uint32 [n_masks, (n + 31) // 32], bit t & 31 of
+    word t >> 5 of a mask set when token t may be chosen (`pack_mask_words`); mask_row int32 [rows]: the index of the
+    row's mask, < 0 or >= n_masks for a row without one.  A masked row gives bit for bit what the sibling gives for the
+    same row with -inf written into the logits at the tokens its mask leaves out; an unmasked row what it gives there.
+    top_k None: unscored, returns ids int64 [rows] (`out` if given) as sample_rows_constrained does.  Otherwise
+    sample_rows_logprobs' four views over the packed layout, `want` as there."""
+    from hydrainfer_amd._C.kernel.norm import LOGPROB_MAX_TOP_K, logprob_rows_bytes, logprob_rows_views
+    _lib.require_gpu(logits, sample_params, bias_ids, bias_values, cu_bias, allow_words, mask_row, hist_ids, hist_counts,
+                     cu_hist, penalties, want, out, cut_out, u_out)
+    what = "sample_rows_masked"
+    scored = top_k is not None
+    if scored and (not isinstance(top_k, int) or isinstance(top_k, bool) or not 0 <= top_k <= LOGPROB_MAX_TOP_K):
+        raise _lib.HydraHipError(f"{what}: top_k {top_k!r} outside 0..{LOGPROB_MAX_TOP_K}")
+    if not scored and want is not None:
+        raise _lib.HydraHipError(f"{what}: want comes with top_k (an unscored launch scores no row)")
+    rows, total, ids = _check_sample_arguments(what, logits, sample_params, hist_ids, hist_counts, cu_hist, penalties,
+                                               None if scored else out, cut_out, u_out, ids_in_packed=scored)
+    bias_total = _check_bias_arguments(what, logits, rows, bias_ids, bias_values, cu_bias)
+    words = mask_words(logits.shape[1])
+    if allow_words.dtype not in (torch.int32, torch.uint32) or allow_words.dim() != 2 or not allow_words.is_contiguous() \
+            or (allow_words.shape[0] > 0 and allow_words.shape[1] != words) or allow_words.device != logits.device:
+        raise _lib.HydraHipError(f"{what}: allow_words must be a contiguous int32 / uint32 tensor of shape [n_masks, {words}] "
+                                 "on the logits' device")
+    n_masks = allow_words.shape[0]
+    for name, t in (("mask_row", mask_row), ("want", want)):
+        if (t is not None or name == "mask_row") and (t.dtype != torch.int32 or tuple(t.shape) != (rows,)
+                                                      or not t.is_contiguous() or t.device != logits.device):
+            raise _lib.HydraHipError(f"{what}: {name} must be a contiguous int32 tensor of shape [{rows}] on the logits' "
+                                     "device")
+    lp = top_ids = top_lp = None
+    if scored:
+        if out is None:
+            out = torch.empty(logprob_rows_bytes(rows, top_k), dtype=torch.uint8, device=logits.device)
+        elif out.device != logits.device or out.data_ptr() % 8:
+            raise _lib.HydraHipError(f"{what}: out must be an 8-byte aligned buffer on the logits' device")
+        ids, lp, top_ids, top_lp = logprob_rows_views(out, rows, top_k)
+    ptr = (lambda t: t.data_ptr()) if total else (lambda t: None)
+    bptr = (lambda t: t.data_ptr()) if bias_total else (lambda t: None)
+    _lib.check(_lib.lib().hx_sample_rows_masked(
+        ids.data_ptr(), cut_out.data_ptr() if cut_out is not None else None, u_out.data_ptr() if u_out is not None else None,
+        logits.data_ptr(), rows, logits.shape[1], logits.stride(0), ptr(hist_ids), ptr(hist_counts), ptr(cu_hist), total,
+        ptr(penalties), bptr(bias_ids), bptr(bias_values), bptr(cu_bias), bias_total, sample_params.data_ptr(),
+        lp.data_ptr() if scored else None, top_ids.data_ptr() if scored and top_k else None,
+        top_lp.data_ptr() if scored and top_k else None, top_k if scored else 0,
+        want.data_ptr() if want is not None else None, allow_words.data_ptr() if n_masks else None, n_masks,
+        mask_row.data_ptr(), _lib.dtype_code(logits), _lib.current_stream()), what)
+    return (ids, lp, top_ids, top_lp) if scored else ids
+
+
+class MaskedStep(_PackedStep):
+    """A masked step's packed tables: ConstrainedStep's buffer with [want (rows) | mask_row (rows) | the step's distinct
+    masks (n_masks * words)] appended — `views` cuts it (on the host or on the device) into sample_rows_masked's table
+    arguments, in its order, with `want` last."""
+    __slots__ = ("buffer", "rows", "total", "bias_total", "n_masks", "words")
+
+    def __init__(self, buffer: np.ndarray, rows: int, total: int, bias_total: int, n_masks: int, words: int):
+        self.buffer, self.rows, self.total, self.bias_total = buffer, rows, total, bias_total
+        self.n_masks, self.words = n_masks, words
+
+    def views(self, t: Optional[Tensor] = None):
+        """(sample_params, bias_ids, bias_values, cu_bias, allow_words, mask_row, hist_ids, hist_counts, cu_hist,
+        penalties, want) inside `t`, a tensor holding the buffer (default: a host copy)."""
+        if t is None:
+            t = torch.from_numpy(self.buffer)
+        e = t.numel() - 2 * self.rows - self.n_masks * self.words                # where ConstrainedStep's layout ends
+        records, bias_ids, bias_values, cu_bias, hist_ids, hist_counts, cu_hist, penalties = \
+            ConstrainedStep(None, self.rows, self.total, self.bias_total).views(t[:e])
+        m = e + 2 * self.rows
+        return (records, bias_ids, bias_values, cu_bias, t[m:].view(self.n_masks, self.words), t[e + self.rows:m],
+                hist_ids, hist_counts, cu_hist, penalties, t[e:e + self.rows])
+
+
+def pack_masked_step(entries) -> MaskedStep:
+    """entries: one (PenaltyHistory or None, (frequency, presence, repetition), record, bias, want, mask) per logits row,
+    in row order — the first four as in `pack_constrained_step`; want: < 0 for a row that is not scored; mask: None or
+    the words of `TokenMask.current()`.  Rows that hand in the SAME array (two requests on one node, one request's node
+    step after step) share one mask of the step: masks are told apart by identity, not by content."""
+    rows = len(entries)
+    step = pack_constrained_step([e[:4] for e in entries])
+    slot, masks = {}, []
+    mask_row = np.full(rows, -1, dtype=np.int32)
+    for r, e in enumerate(entries):
+        mask = e[5]
+        if mask is not None:
+            j = slot.get(id(mask))
+            if j is None:
+                j = slot[id(mask)] = len(masks)
+                masks.append(mask)
+            mask_row[r] = j
+    words = len(masks[0]) if masks else 0
+    if any(len(m) != words for m in masks):
+        raise ValueError("pack_masked_step: the step's masks differ in width")
+    c = step.buffer.size
+    buf = np.empty(c + 2 * rows + len(masks) * words, dtype=np.int32)
+    buf[:c] = step.buffer
+    buf[c:c + rows] = [e[4] for e in entries]
+    buf[c + rows:c + 2 * rows] = mask_row
+    at = c + 2 * rows
+    for m in masks:
+        buf[at:at + words] = np.asarray(m, dtype=np.uint32).view(np.int32)
+        at += words
+    return MaskedStep(buf, rows, step.total, step.bias_total, len(masks), words)

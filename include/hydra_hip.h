@@ -370,6 +370,33 @@ int hx_sample_rows_logprobs(int64_t* ids, float* cut_out, float* u_out, const vo
                             const int32_t* cu_bias, int64_t bias_total, const void* sample_params, float* logprobs,
                             int32_t* top_ids, float* top_logprobs, int top_k, const int32_t* want, int dtype,
                             hx_stream stream);
+/* hx_sample_rows_masked: hx_sample_rows_logprobs under per-row TOKEN MASKS (allowed_token_ids, guided_choice), still one
+ * launch and one read of the logits (extension; added WITHOUT raising HX_ABI_VERSION: nothing that existed changed).
+ * allow_words: uint32 [n_masks, words], words = (n + 31) / 32 — the bitmask format grammar engines exchange: bit t & 31 of
+ * word t >> 5 of a mask is set when token t may be chosen; bits at positions >= n in the last word are ignored.
+ * mask_row: int32 [rows], the index of the row's mask in allow_words; a value < 0 or >= n_masks: the row is unmasked and
+ * nothing of allow_words is read for it.  Step 1a, after the row is staged as fp32 and BEFORE the bias table: every
+ * element of a masked row whose bit is clear becomes -inf (a bias entry on such a token keeps it -inf: biases are
+ * finite or -inf).  The mask's words are read from global memory once per row; no LDS is added.
+ * Scoring is optional per launch as well as per row: with logprobs == NULL no row is scored, and top_ids, top_logprobs,
+ * top_k and want are not read.
+ * The contract:
+ *   A masked row gives, bit for bit, the ids, cut_out, u_out, logprobs, top_ids and top_logprobs that
+ *   hx_sample_rows_logprobs gives for the same row with -inf written into the logits at the masked positions; with
+ *   logprobs == NULL the ids, cut_out and u_out of hx_sample_rows_constrained.
+ *   An unmasked row gives exactly what those entries give for it.
+ *   A row whose surviving elements are all -inf is hx_sample_rows' degenerate row: id 0, cut NaN.  That id may lie
+ *   OUTSIDE the mask: the kernel does not special-case it, the caller must not let it happen (a mask with no bit set
+ *   below n; a mask whose every token is banned by a -inf bias).
+ * Errors: with logprobs != NULL hx_sample_rows_logprobs' rules, else hx_sample_rows_constrained's; n_masks < 0 or
+ * > 0x7fffffff: HX_ERR_SHAPE; mask_row NULL, or allow_words NULL with n_masks > 0: HX_ERR_NULL — nothing is launched. */
+int hx_sample_rows_masked(int64_t* ids, float* cut_out, float* u_out, const void* logits, int64_t rows, int64_t n,
+                          int64_t ld, const int32_t* hist_ids, const int32_t* hist_counts, const int32_t* cu_hist,
+                          int64_t total, const float* penalties, const int32_t* bias_ids, const float* bias_values,
+                          const int32_t* cu_bias, int64_t bias_total, const void* sample_params, float* logprobs,
+                          int32_t* top_ids, float* top_logprobs, int top_k, const int32_t* want,
+                          const uint32_t* allow_words, int64_t n_masks, const int32_t* mask_row, int dtype,
+                          hx_stream stream);
 /* The same product for M <= 32 with the activations held in REGISTERS (csrc/gemm_xreg.hip): a
  * workgroup spans the whole K of its split, so K <= 4096 needs ONE slab (no K split) and K = 11008
  * three instead of eleven — the fp32 slab traffic of a decode layer drops from 25 MB to 6.5 MB.
