@@ -93,6 +93,11 @@ __device__ __forceinline__ float smp_block_sum(float s, float* part) {
   constexpr bool MASKED = false;                                                                       \
   const uint32_t* const allow_words = nullptr; const int32_t n_masks = 0; const int32_t* const mask_row = nullptr;
 
+// the Philox counter of a row, as the body names it: in the four kernels that take the offset itself, words [6] and [7]
+// of the row's record (`rec`, the body's own)
+#define SMP_OFFSET_LO rec[6]
+#define SMP_OFFSET_HI rec[7]
+
 template <typename T>
 __global__ __launch_bounds__(SMP_THREADS) void sample_rows_kernel(
     int64_t* __restrict__ ids, float* __restrict__ cut_out, float* __restrict__ u_out, const u16* __restrict__ logits,
@@ -160,6 +165,35 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_rows_masked_kernel(
   constexpr bool MASKED = true;
 #include "sampling_body.inc"
 }
+
+// hx_sample_rows_resident: sample_rows_kernel without a history (total is the constant 0: step 2 is not compiled), for
+// records that STAY on the device across the steps of a captured decode graph.  Words [6] and [7] are a 64-bit
+// offset_base and the counter is offset_base + positions[row], modulo 2^64 — a request's generated-token count minus its
+// position is constant in decode, so no word of its record changes from step to step and the launch changes no state.
+#undef SMP_OFFSET_LO
+#undef SMP_OFFSET_HI
+__device__ __forceinline__ uint64_t smp_resident_offset(const uint32_t* rec, int32_t position) {
+  return (((uint64_t)rec[7] << 32) | (uint64_t)rec[6]) + (uint64_t)(int64_t)position;   // (sign-extended: a carry or a borrow)
+}
+#define SMP_OFFSET_LO ((uint32_t)smp_resident_offset(rec, positions[row]))
+#define SMP_OFFSET_HI ((uint32_t)(smp_resident_offset(rec, positions[row]) >> 32))
+
+template <typename T>
+__global__ __launch_bounds__(SMP_THREADS) void sample_rows_resident_kernel(
+    int64_t* __restrict__ ids, float* __restrict__ cut_out, float* __restrict__ u_out, const u16* __restrict__ logits,
+    int32_t n, int64_t ld, const uint32_t* __restrict__ sample_params, const int32_t* __restrict__ positions) {
+  constexpr bool CONSTRAINED = false;
+  SMP_NO_SCORES
+  SMP_NO_MASK
+  const int32_t* const bias_ids = nullptr; const float* const bias_values = nullptr; const int32_t* const cu_bias = nullptr;
+  const int32_t bias_total = 0;
+  const int32_t* const hist_ids = nullptr; const int32_t* const hist_counts = nullptr; const int32_t* const cu_hist = nullptr;
+  const float* const penalties = nullptr;
+  constexpr int32_t total = 0;
+#include "sampling_body.inc"
+}
+#undef SMP_OFFSET_LO
+#undef SMP_OFFSET_HI
 
 }  // namespace hx
 
@@ -229,6 +263,39 @@ static int sample_rows(SampleKernel which, const SampleArgs& a) {
   const int rc = sample_rows_check(which, a);
   if (rc != HX_OK) return rc;
   return a.dtype == HX_F16 ? launch_sample_rows<F16>(which, a) : launch_sample_rows<BF16>(which, a);
+}
+
+// The resident entry: hx_sample_rows' checks with total == 0, and the positions.  A row wider than 12288 elements needs
+// the kernel's dynamic-LDS limit raised, which is no stream operation and may not happen while `stream` is being
+// captured: it is raised — to the widest row, so one call serves every n — on every launch outside a capture, and a
+// capture relies on such a launch having gone before (GraphedDecoder._capture runs the step twice first).
+template <typename T>
+static int launch_sample_rows_resident(const SampleArgs& a, const int32_t* positions) {
+  const size_t lds = (size_t)((a.n + 7) / 8 * 8) * sizeof(float);
+  if (lds > 48 * 1024) {
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    hipError_t e = hipStreamIsCapturing(a.stream, &capturing);
+    if (e != hipSuccess) return hip_rc(e);
+    if (capturing == hipStreamCaptureStatusNone) {
+      e = hipFuncSetAttribute((const void*)sample_rows_resident_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)(SAMPLE_MAX_N * sizeof(float)));
+      if (e != hipSuccess) return hip_rc(e);
+    }
+  }
+  launcher(sample_rows_resident_kernel<T>, (unsigned)a.rows, SMP_THREADS, lds, a.stream)(
+      a.ids, a.cut_out, a.u_out, (const u16*)a.logits, (int32_t)a.n, a.ld, (const uint32_t*)a.sample_params, positions);
+  return check_launch();
+}
+
+extern "C" int hx_sample_rows_resident(int64_t* ids, float* cut_out, float* u_out, const void* logits, int64_t rows,
+                                       int64_t n, int64_t ld, const void* sample_params, const int32_t* positions,
+                                       int dtype, hx_stream stream) {
+  const SampleArgs a{ids, cut_out, u_out, logits, rows, n, ld, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
+                     nullptr, 0, sample_params, nullptr, nullptr, nullptr, 0, nullptr, dtype, (hipStream_t)stream};
+  const int rc = sample_rows_check(SMP_PLAIN, a);
+  if (rc != HX_OK) return rc;
+  if (!positions) return HX_ERR_NULL;
+  return dtype == HX_F16 ? launch_sample_rows_resident<F16>(a, positions) : launch_sample_rows_resident<BF16>(a, positions);
 }
 
 extern "C" int hx_sample_rows(int64_t* ids, float* cut_out, float* u_out, const void* logits, int64_t rows, int64_t n,

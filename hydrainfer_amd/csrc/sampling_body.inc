@@ -1,6 +1,8 @@
 // sampling_body.inc — the body of sampling.hip's kernel, included into sample_rows_kernel (CONSTRAINED = false),
 // sample_rows_constrained_kernel (CONSTRAINED = true), sample_rows_logprobs_kernel (CONSTRAINED and SCORED) and
-// sample_rows_masked_kernel (CONSTRAINED, SCORED and MASKED).  Expects the
+// sample_rows_masked_kernel (CONSTRAINED, SCORED and MASKED), and into sample_rows_resident_kernel (none of the three, no
+// history: total is the constant 0).  The Philox counter is read through SMP_OFFSET_LO / SMP_OFFSET_HI, which the including
+// kernel defines: words [6] and [7] of the record, or (resident) those words as a base plus the row's position.  Expects the
 // kernels' arguments (bias_ids, bias_values, cu_bias, bias_total included: null and 0 in sample_rows_kernel, where no
 // statement that names them is compiled; logprobs, top_ids, top_logprobs, score_k, want likewise where SCORED is false;
 // allow_words, n_masks, mask_row likewise where MASKED is false), T, CONSTRAINED, SCORED and MASKED in scope.
@@ -18,7 +20,7 @@
   const uint32_t* rec = sample_params + row * 8;
   const float temperature = __uint_as_float(rec[0]), top_p = __uint_as_float(rec[1]);
   const int32_t top_k = (int32_t)rec[2];
-  const float u = (float)(smp_philox0(rec[6], rec[7], rec[4], rec[5]) >> 8) * 0x1p-24f;
+  const float u = (float)(smp_philox0(SMP_OFFSET_LO, SMP_OFFSET_HI, rec[4], rec[5]) >> 8) * 0x1p-24f;
   const bool sampled = temperature > 0.f;                          // (a NaN or a negative temperature: greedy)
   // SCORED: the row's scores are wanted (the same in every thread); a greedy row is then scored as T = 1 over all of it
   // (MASKED: scoring is optional per launch as well — with logprobs null no row is scored and want is not read)

@@ -144,6 +144,8 @@ class BatchFillExecutor:
     def _decode_rows(self, batch: BatchRequest):
         """(token, position, slot, kv_len, block_table) per request if the whole batch is decode.
         A token still on the device is encoded as -(row + 1) of the pending launch."""
+        if getattr(self.graph_decoder, "sampled", False):
+            return self._decode_rows_sampled(batch)
         rows, max_blocks = [], 0
         bs = self.kv_manager.block_size
         pending_launch = self.pending[0] if self.pending is not None else None
@@ -167,10 +169,43 @@ class BatchFillExecutor:
                 max_blocks = len(bt)
         return rows if self.graph_decoder.fits(len(rows), max_blocks) else None
 
+    def _decode_rows_sampled(self, batch: BatchRequest):
+        """_decode_rows for a decoder with a sampled variant (GraphedDecoder(sampled=True)): a request with
+        temperature > 0 stays eligible when every other condition holds, and the rows come with their records — None for
+        a greedy request, else (temperature, top_p, top_k, seed, n_out - position): the decoder's launch adds the row's
+        position, so the draw's offset is n_out, what the eager step computes (placeholders of tokens still on the
+        device count in output_token_ids).  -> (rows, records) or None."""
+        rows, records, max_blocks = [], [], 0
+        bs = self.kv_manager.block_size
+        pending_launch = self.pending[0] if self.pending is not None else None
+        for rcb, inst in batch:
+            sp = rcb.sampling_params
+            if (len(inst.token_ids) != 1 or not inst.sample or sp.logprobs or rcb.penalty_history is not None
+                    or inst.score_targets is not None or rcb.token_constraints is not None
+                    or getattr(rcb, "token_mask", None) is not None):
+                return None
+            token = inst.token_ids[0]
+            if isinstance(token, PendingToken):
+                if token.launch != pending_launch:
+                    return None
+                token = -(token.row + 1)
+            bt = rcb.virtual_kv_cache.block_table
+            c = inst.cache_ids[0]
+            position = inst.position_ids[0]
+            rows.append((token, position, bt[c // bs] * bs + c % bs, c + 1, bt, rcb.sid))
+            records.append((sp.temperature, sp.top_p, sp.top_k, sp.seed, len(rcb.output_token_ids) - position)
+                           if sp.temperature > 0 else None)
+            if len(bt) > max_blocks:
+                max_blocks = len(bt)
+        return (rows, records) if self.graph_decoder.fits(len(rows), max_blocks) else None
+
     def _launch_decode(self, batch: BatchRequest, rows) -> None:
         """Enqueue the step, hand every request a placeholder for its new token, THEN read the
         previous step's tokens: the GPU already has the next step queued while the host catches up."""
-        launch = self.graph_decoder.launch(rows)
+        if isinstance(rows, tuple):            # (rows, records) of _decode_rows_sampled
+            launch = self.graph_decoder.launch(*rows)
+        else:
+            launch = self.graph_decoder.launch(rows)
         entries = []
         for row, (rcb, inst) in enumerate(batch):
             placeholder = PendingToken(launch, row)

@@ -22,9 +22,15 @@ only the DEVICE needs it for that.  The graph therefore starts by taking each ro
 from the host-written id or from `prev_tokens[src_row]` (the previous launch's samples, kept in a
 static buffer the graph itself updates at its end), so the host can build and enqueue launch N+1
 while launch N is still running and read N's tokens afterwards (`launch` / `fetch`).  The host work
-of a step (scheduler, tables, staging) no longer leaves the GPU idle."""
+of a step (scheduler, tables, staging) no longer leaves the GPU idle.
+
+Sampled decoding from the graph (`sampled=True`, opt-in): a second variant of the step, keyed (B, bucket, "sampled"), ends
+in hx_sample_rows_resident instead of the argmax.  Its records live in a RESIDENT table indexed by launch row; a
+record's offset word is `n_out - position`, which decode never changes, and the kernel adds the row's position — the
+array the step already reads — so neither a look-ahead launch nor a cohort step restages anything (DESIGN.md,
+"Sampled decoding from the captured step")."""
 import os
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -35,6 +41,7 @@ from hydrainfer_amd._C.kernel.norm import StepHead
 from hydrainfer_amd.layer.causal_attention import RANKED_THR, AttentionParameters, decode_rank_descriptor
 from hydrainfer_amd.memory.kv_cache import KVCache
 from hydrainfer_amd.model.llama import LanguageModelParameters
+from hydrainfer_amd.sampling import (SAMPLE_MAX_N, SAMPLE_RECORD_WORDS, pack_resident_records, sample_rows_resident)
 
 
 class DecodeStager:
@@ -188,7 +195,8 @@ class DecodeStager:
 
 class GraphedDecoder:
     def __init__(self, language_model, kv_cache_block_manager, max_batch: int = 64,
-                 max_blocks_per_seq: int = 256, pad_to: int = 4, executor: str = None):
+                 max_blocks_per_seq: int = 256, pad_to: int = 4, executor: str = None, sampled: bool = False,
+                 keep_draws: bool = False):
         # how a captured step is replayed: "graph" = a hipGraph (default here), "plan" = a launch plan
         # (hydrainfer_amd/launch_plan.py: the step's launches issued in stream order by a native loop).  The plan costs
         # ~0.65 ms of HOST time per 7B step (170 launches x 3.8 us) where a graph launch costs ~0.1: irrelevant for a
@@ -234,6 +242,25 @@ class GraphedDecoder:
         n_layers = self.model.shape.num_hidden_layers
         self.kv_caches = [KVCache.from_token_cache(self.kv.get_layer_cache(l)) for l in range(n_layers)]
         self.graphs: Dict[Tuple[int, int], tuple] = {}
+        # sampled decoding from the graph: the records of the launch rows, resident; a padding row keeps the greedy record.
+        # A vocabulary wider than the sampling kernel's row, or logits it does not read: no sampled variant — `sampled`
+        # stays False and the executor keeps such batches eager
+        self.sampled = bool(sampled) and self.model.shape.vocab_size <= SAMPLE_MAX_N \
+            and self.model.dtype in (torch.float16, torch.bfloat16)
+        self.keep_draws = keep_draws and self.sampled      # tests: the sampled graphs also write each row's u
+        self.last_sampled = False                          # the variant of the most recent launch (launch_cohort repeats it)
+        if self.sampled:
+            greedy = torch.from_numpy(pack_resident_records([None] * B))
+            self.records = greedy.to(self.dev)
+            # what the table holds, by row (the host's copy), and the pinned double buffer new records go through —
+            # used alternately with `staging` and guarded by the same events
+            self.resident: List[Optional[tuple]] = [None] * B
+            self.record_staging = [greedy.clone().pin_memory() for _ in range(2)]
+            self.record_stage = [t.numpy() for t in self.record_staging]
+        if self.keep_draws:
+            self.draws = torch.zeros(B, dtype=torch.float32, device=self.dev)
+            self.host_draws = [torch.zeros(B, dtype=torch.float32).pin_memory() for _ in range(2)]
+            self.draw_rows = {}            # launch id -> number of live rows (sampled launches only)
 
     def fits(self, n_seqs: int, max_blocks: int) -> bool:
         """n_seqs rows whose longest block table has max_blocks entries."""
@@ -262,8 +289,10 @@ class GraphedDecoder:
                                     kv_max_seq_len=kv_max, decode_rank=rank) for kc in self.kv_caches]
         return LanguageModelParameters(attention_params=attn, all_sequences_decode=True)
 
-    def _body(self, B: int, params):
-        """One decode step as library launches only (+ the lm_head GEMM): recordable in a launch plan."""
+    def _body(self, B: int, params, sampled: bool = False):
+        """One decode step as library launches only (+ the lm_head GEMM): recordable in a launch plan.  sampled: the
+        step ends in hx_sample_rows_resident over the resident records instead of the argmax, and its logits come back
+        as a third result."""
         ids, pos = self._views(B)[:2]
         src = self._views(B)[6]
         lib = _lib.lib()
@@ -282,8 +311,14 @@ class GraphedDecoder:
         # launch's feed and the D2H copy of the tokens read it after this launch, in stream order
         out = self.prev_tokens[:B]
         self.model.sample_out = out
+        logits = None
         try:
-            res = self.model(fed, pos, params)
+            if sampled:
+                logits = self.model.forward_logits(fed, pos, params)
+                res = sample_rows_resident(logits, self.records[:B], pos, out=out,
+                                           u_out=self.draws[:B] if self.keep_draws else None)
+            else:
+                res = self.model(fed, pos, params)
         finally:
             self.model.sample_out = None
             params.step_head = None      # consumed: a later direct model(...) call with these params must not feed again
@@ -296,9 +331,10 @@ class GraphedDecoder:
             err = torch.empty(1, dtype=torch.int32, device=self.dev)
             _lib.check(lib.hx_collect_errors(err.data_ptr(), sync.data_ptr(), sync.numel() // sync.shape[-1],
                                              sync.shape[-1], 1, None, _lib.current_stream()), "collect_errors")
-        return out, err
+        return (out, err, logits) if sampled else (out, err)
 
-    def _capture(self, B: int, bucket: int):
+    def _capture(self, B: int, bucket: int, variant: str = None):
+        sampled = variant == "sampled"
         params = self._params(B, bucket if bucket else 4096)
         saved = self.prev_tokens.clone()
         side = torch.cuda.Stream(device=self.dev)
@@ -306,25 +342,27 @@ class GraphedDecoder:
         with torch.cuda.stream(side):
             for _ in range(2):             # warm-up outside capture: workspace growth, lazy init
                 self.prev_tokens.copy_(saved)
-                self._body(B, params)
+                self._body(B, params, sampled)
             self.prev_tokens.copy_(saved)
         torch.cuda.current_stream(self.dev).wait_stream(side)
         graph = None
         if self.executor == "plan":
             graph = launch_plan.LaunchPlan(self.dev)
             try:
-                out, err = graph.capture(lambda: self._body(B, params))
+                out, err, *logits = graph.capture(lambda: self._body(B, params, sampled))
             except launch_plan.PlanNotRecordable:
                 graph = None       # a step with torch ops in it (library GEMMs, a shape off the hx fast path): hipGraph
                 self.executor = "graph"
         if graph is None:
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                out, err = self._body(B, params)
-        return graph, out, err
+                out, err, *logits = self._body(B, params, sampled)
+        return (graph, out, err, *logits)
 
-    def _fill(self, rows: List[tuple], B: int) -> int:
-        """Stage the step (DecodeStager.stage) and enqueue the kernel that applies it to the resident buffer."""
+    def _fill(self, rows: List[tuple], B: int, records=None) -> int:
+        """Stage the step (DecodeStager.stage) and enqueue the kernel that applies it to the resident buffer.  records:
+        None, or the sampled step's record per live row — rows of the resident table that hold something else are
+        rewritten, through the pinned buffer of this fill, by one more launch."""
         which = self.fills % 2
         self.fills += 1
         self.copy_done[which].synchronize()      # no-op until the buffer has been used once
@@ -333,6 +371,14 @@ class GraphedDecoder:
         # for ~0.1 ms per step)
         _lib.check(_lib.lib().hx_stage_decode(self.static.data_ptr(), self.static.numel(), self.staging[which].data_ptr(),
                                               self.stager.head_words, _lib.current_stream()), "stage_decode")
+        if records is not None:
+            want = list(records) + [None] * (B - len(records))          # a padding row is greedy
+            if want != self.resident[:B]:
+                pack_resident_records(want, self.record_stage[which][:B])
+                _lib.check(_lib.lib().hx_copy_words2(self.records.data_ptr(), self.record_staging[which].data_ptr(),
+                                                     SAMPLE_RECORD_WORDS * B, None, None, 0, _lib.current_stream()),
+                           "copy_words2")
+                self.resident[:B] = want
         self.copy_done[which].record()
         return kv_max
 
@@ -341,9 +387,10 @@ class GraphedDecoder:
         for n in batch_sizes:
             B = (n + self.pad_to - 1) // self.pad_to * self.pad_to
             key = (B, self._kv_bucket(B, kv_max))
-            if key not in self.graphs:
-                self._fill(rows, B)
-                self.graphs[key] = self._capture(*key)
+            for key in (key, key + ("sampled",)) if self.sampled else (key,):
+                if key not in self.graphs:
+                    self._fill(rows, B)
+                    self.graphs[key] = self._capture(*key)
         torch.cuda.synchronize(self.dev)
 
     def launch_cohort(self, n: int, pos, slots, starts, grown) -> int:
@@ -356,19 +403,44 @@ class GraphedDecoder:
         _lib.check(_lib.lib().hx_stage_decode(self.static.data_ptr(), self.static.numel(), self.staging[which].data_ptr(),
                                               self.stager.head_words, _lib.current_stream()), "stage_decode")
         self.copy_done[which].record()
-        return self._replay(n, B, kv_max)
+        # the variant of the launch the cohort was formed behind: the same rows in the same order, so their records
+        # are in the table already, and the positions staged above move every row's offset on by one
+        return self._replay(n, B, kv_max, self.last_sampled)
 
-    def launch(self, rows: List[tuple]) -> int:
-        """Enqueue one decode step; returns a launch id for `fetch`.  Does not wait for the GPU."""
+    def launch(self, rows: List[tuple], records=None) -> int:
+        """Enqueue one decode step; returns a launch id for `fetch`.  Does not wait for the GPU.  records (a decoder
+        built with sampled=True): per row None — greedy — or (temperature, top_p, top_k, seed, n_out - position); None or
+        all None is the greedy step as it ever was."""
         n = len(rows)
         B = (n + self.pad_to - 1) // self.pad_to * self.pad_to
-        return self._replay(n, B, self._fill(rows, B))
+        if records is not None and all(r is None for r in records):
+            records = None
+        if records is not None and not self.sampled:
+            raise HydraHipError("sampling records for a decoder without a sampled variant (sampled=False, a vocabulary "
+                                f"above {SAMPLE_MAX_N}, or logits that are not fp16 / bf16)")
+        self.last_sampled = records is not None
+        return self._replay(n, B, self._fill(rows, B, records), self.last_sampled)
 
-    def _replay(self, n: int, B: int, kv_max: int) -> int:
-        key = (B, self._kv_bucket(B, kv_max))
+    def sample_logits(self, B: int, bucket: int):
+        """Tests: the logits tensor the sampled graph (B, bucket) writes — the graph's own buffer, valid until the next
+        replay."""
+        return self.graphs[(B, bucket, "sampled")][3]
+
+    def fetch_draws(self, launch_id: int):
+        """Tests (keep_draws=True): the per-row u of a sampled launch, fp32 (waits for it); None for a greedy launch.
+        Only the two most recent launches are kept."""
+        assert launch_id > self.launches - 2, "draws of an older launch have been overwritten"
+        n = self.draw_rows.get(launch_id)
+        if n is None:
+            return None
+        self.events[launch_id % 2].synchronize()
+        return self.host_draws[launch_id % 2][:n].numpy().copy()
+
+    def _replay(self, n: int, B: int, kv_max: int, sampled: bool = False) -> int:
+        key = (B, self._kv_bucket(B, kv_max)) + (("sampled",) if sampled else ())
         if key not in self.graphs:
             self.graphs[key] = self._capture(*key)
-        graph, out, err = self.graphs[key]
+        graph, out, err = self.graphs[key][:3]
         graph.replay()
         self.launches += 1
         slot = self.launches % 2
@@ -378,6 +450,12 @@ class GraphedDecoder:
                                              err.data_ptr() if err is not None else None, 1 if err is not None else 0,
                                              _lib.current_stream()), "copy_words2")
         self.launch_has_err[self.launches] = err is not None
+        if self.keep_draws:
+            self.draw_rows.pop(self.launches - 2, None)
+            if sampled:
+                _lib.check(_lib.lib().hx_copy_words2(self.host_draws[slot].data_ptr(), self.draws.data_ptr(), n, None, None,
+                                                     0, _lib.current_stream()), "copy_words2")
+                self.draw_rows[self.launches] = n
         self.events[slot].record()
         self.launch_rows[self.launches] = n
         return self.launches
@@ -406,5 +484,5 @@ class GraphedDecoder:
                                 "with the add+RMSNorm as separate launches (fuse_norm = False)")
         return self.host_tokens[slot][:n].tolist()
 
-    def run(self, rows: List[Tuple[int, int, int, int, List[int]]]) -> List[int]:
-        return self.fetch(self.launch(rows))
+    def run(self, rows: List[Tuple[int, int, int, int, List[int]]], records=None) -> List[int]:
+        return self.fetch(self.launch(rows, records))

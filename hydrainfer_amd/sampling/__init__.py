@@ -32,7 +32,11 @@ Token masks (`allowed_token_ids`, `guided_choice`): `sample_rows_masked` (hx_sam
 a per-row bitmask of the tokens a row may choose — 32 tokens per int32 word, 1 = allowed, the format grammar engines
 exchange — applied as -inf ahead of everything else; `TokenMask` holds a request's masks (one node, or a trie over its
 choices' token sequences) and where it stands, and `pack_masked_step` appends `want`, the rows' mask indices and the step's
-distinct masks to `pack_constrained_step`'s buffer."""
+distinct masks to `pack_constrained_step`'s buffer.
+
+Sampled decoding from a captured decode step: `sample_rows_resident` (hx_sample_rows_resident) is `sample_rows` without a
+history whose records stay on the device — `pack_resident_records` writes `n_out - position` where the offset stood, the
+launch adds the row's position (engine/graph_decode.py)."""
 import math
 from array import array
 from typing import Optional, Sequence, Tuple
@@ -265,6 +269,43 @@ def pack_sample_records(records, out: Optional[np.ndarray] = None) -> np.ndarray
     out[:, 2] = [r[2] for r in records]
     out[:, 3] = np.asarray([r[5] if len(r) > 5 else 0.0 for r in records], dtype=np.float32).view(np.int32)
     out[:, 4:].view(np.uint64)[:] = np.asarray([(r[3], r[4]) for r in records], dtype=np.uint64).reshape(rows, 2)
+    return out
+
+
+def pack_resident_records(records, out: Optional[np.ndarray] = None) -> np.ndarray:
+    """records: per launch row None (the greedy record) or (temperature, top_p, top_k, seed, offset_base) -> int32
+    [rows, 8], the layout hx_sample_rows_resident reads (into `out` if given): `pack_sample_records`' with words [6] and
+    [7] holding offset_base as a 64-bit two's-complement number — the row then draws with offset_base + its position,
+    so a decode request's record is (.., n_out - position) for as long as it lives.  Word [3] is 0."""
+    rows = len(records)
+    if out is None:
+        out = np.zeros((rows, SAMPLE_RECORD_WORDS), dtype=np.int32)
+    recs = [GREEDY_RECORD if r is None else r for r in records]
+    out[:, :2] = np.asarray([(r[0], r[1]) for r in recs], dtype=np.float32).reshape(rows, 2).view(np.int32)
+    out[:, 2] = [r[2] for r in recs]
+    out[:, 3] = 0
+    wide = out[:, 4:].view(np.int64)
+    wide[:, 0] = [r[3] for r in recs]           # (a seed is at most 2^63 - 1)
+    wide[:, 1] = [r[4] for r in recs]
+    return out
+
+
+def sample_rows_resident(logits: Tensor, sample_params: Tensor, positions: Tensor, out: Optional[Tensor] = None,
+                         cut_out: Optional[Tensor] = None, u_out: Optional[Tensor] = None) -> Tensor:
+    """`sample_rows` without a history for records that stay on the device (include/hydra_hip.h:
+    hx_sample_rows_resident): sample_params int32 [rows, 8] from `pack_resident_records`, positions int32 [rows]; row r
+    draws with offset = its record's offset_base + positions[r].  Ids, cut and u are `sample_rows`' for a record that
+    carries that offset, bit for bit.  Nothing here allocates when `out` is given: the launch a captured decode step
+    ends in."""
+    _lib.require_gpu(logits, sample_params, positions, out, cut_out, u_out)
+    rows, _, out = _check_sample_arguments("sample_rows_resident", logits, sample_params, None, None, None, None, out, cut_out,
+                                           u_out)
+    if positions.dtype != torch.int32 or tuple(positions.shape) != (rows,) or not positions.is_contiguous():
+        raise _lib.HydraHipError(f"sample_rows_resident: positions must be a contiguous int32 tensor of shape [{rows}]")
+    _lib.check(_lib.lib().hx_sample_rows_resident(
+        out.data_ptr(), cut_out.data_ptr() if cut_out is not None else None, u_out.data_ptr() if u_out is not None else None,
+        logits.data_ptr(), rows, logits.shape[1], logits.stride(0), sample_params.data_ptr(), positions.data_ptr(),
+        _lib.dtype_code(logits), _lib.current_stream()), "sample_rows_resident")
     return out
 
 

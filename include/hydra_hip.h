@@ -319,6 +319,22 @@ int hx_penalized_argmax_rows(int64_t* ids, float* scores_out, const void* logits
 int hx_sample_rows(int64_t* ids, float* cut_out, float* u_out, const void* logits, int64_t rows, int64_t n, int64_t ld,
                    const int32_t* hist_ids, const int32_t* hist_counts, const int32_t* cu_hist, int64_t total,
                    const float* penalties, const void* sample_params, int dtype, hx_stream stream);
+/* hx_sample_rows_resident: hx_sample_rows without a history (its total == 0 case) for records that stay RESIDENT on the
+ * device, as a captured decode step needs them (extension; added WITHOUT raising HX_ABI_VERSION: nothing that existed
+ * changed).  One difference: words [6] and [7] of a record are not the offset but a 64-bit two's-complement offset_base,
+ * and row r draws with
+ *     offset = offset_base + (int64)positions[r]        modulo 2^64 (the carry into the high word included)
+ * positions: int32 [rows], the step's position array.  In decode a request's position and its generated-token count both
+ * grow by one per step, so offset_base = n_out - position is constant for the life of the request: a record written once
+ * stays valid step after step, and the launch changes no state (a discarded or replayed step desynchronises nothing).
+ * Words [0..5] are hx_sample_rows'; word [3] is ignored.  ids, cut_out and u_out are bit for bit what hx_sample_rows
+ * gives for the same logits with total == 0 and a record that carries that offset — greedy rows (T == 0), degenerate
+ * rows and NULL cut_out / u_out included.  Errors: hx_sample_rows' rules; positions NULL: HX_ERR_NULL — nothing is
+ * launched.  A row wider than 12288 elements needs the kernel's dynamic-LDS limit raised: every call outside a stream
+ * capture does that; a call on a capturing stream does not (it is no stream operation), so one call outside a capture
+ * must have gone before on this device. */
+int hx_sample_rows_resident(int64_t* ids, float* cut_out, float* u_out, const void* logits, int64_t rows, int64_t n,
+                            int64_t ld, const void* sample_params, const int32_t* positions, int dtype, hx_stream stream);
 /* hx_sample_rows_constrained: hx_sample_rows with a per-row logit bias table and a min_p cut, still one launch and one
  * read of the logits (extension; added WITHOUT raising HX_ABI_VERSION: nothing that existed changed).  Everything
  * hx_sample_rows documents holds word for word, with two additions.
