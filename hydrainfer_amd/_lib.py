@@ -149,6 +149,12 @@ _SIGNATURES = {
     "hx_moe_permute": (c_int, [c_void_p] * 3 + [c_int64] * 3 + [c_int, c_void_p]),
     "hx_moe_unpermute": (c_int, [c_void_p] * 4 + [c_int64] * 3 + [c_int, c_void_p]),
     "hx_moe_sum_out": (c_int, [c_void_p] * 2 + [c_int64] * 3 + [c_int, c_void_p]),
+    "hx_moe_gate_topk": (c_int, [c_void_p] * 4 + [c_int64] * 4 + [c_int] * 3 + [c_int64] * 2 + [c_int, c_float, c_void_p]),
+    "hx_moe_segments_elems": (c_int64, [c_int64] * 3),
+    "hx_moe_segments": (c_int, [c_void_p] * 2 + [c_int64] * 3 + [c_void_p]),
+    "hx_moe_gate_up_silu": (c_int, [c_void_p] * 4 + [c_int64] * 5 + [c_int, c_void_p]),
+    "hx_moe_down": (c_int, [c_void_p] * 4 + [c_int64] * 5 + [c_int, c_void_p]),
+    "hx_moe_combine": (c_int, [c_void_p] * 4 + [c_int64] * 3 + [c_int, c_void_p]),
     "hx_decode_advance": (c_int, [c_void_p] * 6 + [c_int32, c_int32, c_int32, c_void_p]),
     "hx_decode_advance_ranked": (c_int, [c_void_p] * 6 + [c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "hx_decode_rank": (c_int, [c_void_p, c_int32, c_void_p, c_void_p]),

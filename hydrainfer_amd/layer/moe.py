@@ -1,0 +1,108 @@
+"""Sparse MoE feed-forward block — mirrors DeepseekV3MoE (hydrainfer/model/deepseek_v3.py:95-155): softmax / greedy
+router, routed experts, shared experts.
+
+MI355X-first differences (rounding-neutral with respect to the reference's ops, tests/moe_block_ref.py):
+  * the routed experts' weights are STACKED ([E, 2I, h] gate rows then up rows, [E, h, I]) and run as two grouped
+    weight-streaming launches (csrc/moe_experts.hip) instead of a Python loop of index-gather + three GEMMs per expert;
+  * nothing is read back to the host (the reference's tokens_per_expert.cpu(), :130): the block captures into a hipGraph;
+  * the shared experts' gate and up projections are one fused [2 I_s, h] GEMM.
+HIP only: the router, the segments, both expert GEMMs and the combine are libhydra_hip launches; there is no fallback."""
+from typing import Callable, Dict, Optional
+
+import torch
+from torch import Tensor
+
+from hydrainfer_amd._C.kernel.activation import silu_and_mul
+from hydrainfer_amd._C.kernel.moe import experts as moe_experts
+
+
+def _dense_linear(x: Tensor, w: Tensor) -> Tensor:
+    """x @ w^T on the dense ops of the decoder: the weight-streaming HIP GEMM at decode sizes, the library GEMM above."""
+    from hydrainfer_amd._C.kernel import gemm as hip_gemm
+    if x.shape[0] <= 64 and hip_gemm.supported(x, w):
+        return hip_gemm.linear_decode(x, w)
+    return torch.matmul(x, w.t())
+
+
+class SparseMoE:
+    def __init__(self, router_weight: Tensor, w_gate_up: Tensor, w_down: Tensor, shared_gate_up: Optional[Tensor],
+                 shared_down: Optional[Tensor], num_experts_per_tok: int, norm_topk_prob: bool = False,
+                 routed_scaling_factor: float = 1.0, linear: Optional[Callable[[Tensor, Tensor], Tensor]] = None):
+        E, two_i, h = w_gate_up.shape
+        if w_down.shape != (E, h, two_i // 2) or router_weight.shape != (E, h):
+            raise ValueError("SparseMoE: router_weight [E, h], w_gate_up [E, 2I, h], w_down [E, h, I]")
+        if (shared_gate_up is None) != (shared_down is None):
+            raise ValueError("SparseMoE: the shared experts need both weights")
+        self.router_weight, self.w_gate_up, self.w_down = router_weight, w_gate_up, w_down
+        self.shared_gate_up, self.shared_down = shared_gate_up, shared_down
+        self.num_experts_per_tok, self.norm_topk_prob = int(num_experts_per_tok), bool(norm_topk_prob)
+        self.routed_scaling_factor = float(routed_scaling_factor)
+        self.linear = linear or _dense_linear
+        self.last_topk_ids: Optional[Tensor] = None      # [n, topk] int32 of the last forward (tests, statistics)
+
+    @property
+    def n_experts(self) -> int:
+        return self.w_gate_up.shape[0]
+
+    def shared_experts(self, x: Tensor) -> Optional[Tensor]:
+        """DeepseekV3MLP of intermediate size I * n_shared_experts (:110-112) on the dense ops."""
+        if self.shared_gate_up is None:
+            return None
+        inter = self.shared_gate_up.shape[0] // 2
+        gu = self.linear(x, self.shared_gate_up)
+        return self.linear(silu_and_mul(gu[:, :inter], gu[:, inter:]), self.shared_down)
+
+    def forward(self, x: Tensor) -> Tensor:
+        if x.dim() != 2:
+            raise ValueError("SparseMoE.forward: x must be [n_tokens, hidden]")
+        if not x.is_contiguous():
+            x = x.contiguous()
+        w, ids = moe_experts.gate_topk(x, self.router_weight, self.num_experts_per_tok, self.norm_topk_prob,
+                                       self.routed_scaling_factor)
+        self.last_topk_ids = ids
+        shared = self.shared_experts(x)
+        if shared is not None and not shared.is_contiguous():
+            shared = shared.contiguous()
+        return moe_experts.experts_forward(x, self.w_gate_up, self.w_down, w, ids, shared)
+
+    __call__ = forward
+
+    @classmethod
+    def from_reference_state_dict(cls, prefix: str, sd: Dict[str, Tensor], num_experts_per_tok: int,
+                                  norm_topk_prob: bool = False, routed_scaling_factor: float = 1.0, dtype=None, device=None,
+                                  linear=None) -> "SparseMoE":
+        """prefix: up to and including "mlp." — reads {prefix}experts.{e}.{gate,up,down}_proj.weight, {prefix}gate.weight
+        and {prefix}shared_experts.{gate,up,down}_proj.weight (absent: no shared experts)."""
+        def t(name):
+            v = sd[prefix + name]
+            return v.to(dtype=dtype or v.dtype, device=device or v.device)
+        n_e = 0
+        while f"{prefix}experts.{n_e}.gate_proj.weight" in sd:
+            n_e += 1
+        if n_e == 0:
+            raise KeyError(f"no {prefix}experts.0.gate_proj.weight in the state dict")
+        wgu = torch.stack([torch.cat([t(f"experts.{e}.gate_proj.weight"), t(f"experts.{e}.up_proj.weight")], dim=0)
+                           for e in range(n_e)]).contiguous()
+        wdown = torch.stack([t(f"experts.{e}.down_proj.weight") for e in range(n_e)]).contiguous()
+        sgu = sdown = None
+        if prefix + "shared_experts.gate_proj.weight" in sd:
+            sgu = torch.cat([t("shared_experts.gate_proj.weight"), t("shared_experts.up_proj.weight")], dim=0).contiguous()
+            sdown = t("shared_experts.down_proj.weight").contiguous()
+        return cls(t("gate.weight").contiguous(), wgu, wdown, sgu, sdown, num_experts_per_tok, norm_topk_prob,
+                   routed_scaling_factor, linear)
+
+    def to_reference_state_dict(self, prefix: str) -> Dict[str, Tensor]:
+        inter = self.w_gate_up.shape[1] // 2
+        sd = {prefix + "gate.weight": self.router_weight.cpu()}
+        wgu, wdown = self.w_gate_up.cpu(), self.w_down.cpu()
+        for e in range(self.n_experts):
+            sd[f"{prefix}experts.{e}.gate_proj.weight"] = wgu[e, :inter]
+            sd[f"{prefix}experts.{e}.up_proj.weight"] = wgu[e, inter:]
+            sd[f"{prefix}experts.{e}.down_proj.weight"] = wdown[e]
+        if self.shared_gate_up is not None:
+            si = self.shared_gate_up.shape[0] // 2
+            sgu = self.shared_gate_up.cpu()
+            sd[prefix + "shared_experts.gate_proj.weight"] = sgu[:si]
+            sd[prefix + "shared_experts.up_proj.weight"] = sgu[si:]
+            sd[prefix + "shared_experts.down_proj.weight"] = self.shared_down.cpu()
+        return sd

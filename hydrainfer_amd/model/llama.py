@@ -418,6 +418,14 @@ class LlamaForCausalLM:
         return bool(n_rows <= 64 and t.is_cuda and t.dtype in (torch.float16, torch.bfloat16) and t.is_contiguous()
                     and t.shape[1] % 8 == 0 and t.shape[1] <= 8192)
 
+    def _mlp(self, l: int, x: Tensor) -> Tensor:
+        """Layer l's feed-forward on the general path: down(silu(gate(x)) * up(x)).  A subclass with another MLP
+        (model/deepseek_moe.py) overrides this."""
+        inter = self.shape.intermediate_size
+        gu = self.linear(x, self.state[f"l{l}.wgu"])
+        act = silu_and_mul(gu[:, :inter], gu[:, inter:])
+        return self.linear(act, self.state[f"l{l}.wdown"])
+
     def forward_hidden(self, input_ids_or_embeds: Tensor, position_ids: Tensor,
                        model_params: LanguageModelParameters) -> Tensor:
         sh, st = self.shape, self.state
@@ -448,7 +456,7 @@ class LlamaForCausalLM:
             return self._decode_hidden_hip_gemm(h, position_ids, model_params, plan, x0, sync)
         n = h.shape[0]
         H, HK, D = sh.num_attention_heads, sh.num_key_value_heads, sh.head_dim
-        q_size, kv_size, inter = self.q_size, self.kv_size, sh.intermediate_size
+        q_size, kv_size = self.q_size, self.kv_size
         eps = sh.rms_norm_eps
         L = sh.num_hidden_layers
 
@@ -485,9 +493,7 @@ class LlamaForCausalLM:
                 # last layer of a prefill: only sampled tokens go through the MLP
                 h = h[model_params.selected_token_ids].contiguous()
                 x = x[model_params.selected_token_ids].contiguous()
-            gu = self.linear(x, st[f"l{l}.wgu"])
-            act = silu_and_mul(gu[:, :inter], gu[:, inter:])
-            m = self.linear(act, st[f"l{l}.wdown"])
+            m = self._mlp(l, x)
             nxt = st[f"l{l + 1}.norm1"] if l + 1 < L else st["norm"]
             if x.shape != h.shape:
                 x = torch.empty_like(h)

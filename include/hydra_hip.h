@@ -860,6 +860,48 @@ int hx_moe_sum_out(const void* in, void* out, int64_t n_tokens, int64_t topk, in
                    int dtype, hx_stream stream);
 
 /* ------------------------------------------------------------------------
+ * Sparse MoE feed-forward (csrc/moe_experts.hip): router, segments, grouped expert GEMMs, combine.
+ * replaces: hydrainfer/model/deepseek_v3.py:61-93 (MoEGate.forward), :114-121 (DeepseekV3MoE.forward),
+ *           :124-155 (moe_infer: a Python loop over experts around a tokens_per_expert.cpu() host sync)
+ * n tokens, E <= 256 routed experts, topk <= 8, hidden h and expert intermediate I multiples of 128, T = fp16 / bf16;
+ * stacked contiguous weights w_gate_up [E, 2I, h] (gate rows, then up rows) and w_down [E, h, I]; slot s = t * topk + k.
+ * No entry synchronises or reads anything back; every grid depends on (E, I, h, n, topk) only, so a step captures into
+ * a hipGraph; results are deterministic (no floating-point atomics).
+ * ---------------------------------------------------------------------- */
+#define HX_MOE_SCORE_SOFTMAX 0
+#define HX_MOE_SCORE_SIGMOID 1
+/* deepseek_v3.py:61-93 with scoring_func = "softmax", topk_method = "greedy": logits[t, e] = sum_h float(x[t, h]) *
+ * float(router_weight[e, h]) in fp32 (router_weight [E, h] in x's dtype or fp32), fp32 softmax over the experts, top-k
+ * with ties to the lower index (the rule of hx_topk_softmax), weights = w / (sum_k w + 1e-20) * routed_scaling_factor
+ * when norm_topk_prob and topk > 1 (:88), else w * routed_scaling_factor.  topk_weights f32 / topk_ids i32 [n, topk].
+ * scoring != HX_MOE_SCORE_SOFTMAX or group-limited routing (n_group > 1 or topk_group > 1): HX_ERR_UNSUPPORTED —
+ * hx_grouped_topk_sigmoid is the entry for that. */
+int hx_moe_gate_topk(float* topk_weights, int32_t* topk_ids, const void* x, const void* router_weight,
+                     int64_t n_tokens, int64_t hidden, int64_t n_experts, int64_t topk, int x_dtype,
+                     int weight_dtype, int scoring, int64_t n_group, int64_t topk_group, int norm_topk_prob,
+                     float routed_scaling_factor, hx_stream stream);
+/* deepseek_v3.py:125-130 (scatter_, argsort, .cpu()) on the device, one small launch: seg (int32,
+ * hx_moe_segments_elems() elements) = [ exclusive offsets E + 1 | per-expert row counts E | the n * topk slots grouped
+ * by expert ].  Order inside a group is unspecified (a slot's result does not depend on its place); an id outside
+ * [0, E) puts its slot in no group, and the rows of that slot are then written by neither GEMM. */
+int64_t hx_moe_segments_elems(int64_t n_tokens, int64_t topk, int64_t n_experts);
+int hx_moe_segments(int32_t* seg, const int32_t* topk_ids, int64_t n_tokens, int64_t topk, int64_t n_experts,
+                    hx_stream stream);
+/* deepseek_v3.py:138-140 with GateUpDownMLP, first half: for every routed slot s = (t, k), e = topk_ids[t, k]:
+ * act[s, j] = T(float(T(silu(float(g)))) * float(u)), g = T(sum_h x[t, h] * Wg_e[j, h]), u = T(sum_h x[t, h] * Wu_e[j, h])
+ * (fp32 accumulation, one rounding, as nn.Linear).  x [n, h], act [n * topk, I] in slot order: no permuted copy of x. */
+int hx_moe_gate_up_silu(void* act, const void* x, const void* w_gate_up, const int32_t* seg, int64_t n_tokens,
+                        int64_t topk, int64_t n_experts, int64_t hidden, int64_t inter, int dtype, hx_stream stream);
+/* ... second half (down_proj): y[s, c] = T(sum_j act[s, j] * Wd_e[c, j]), y [n * topk, h]. */
+int hx_moe_down(void* y, const void* act, const void* w_down, const int32_t* seg, int64_t n_tokens, int64_t topk,
+                int64_t n_experts, int64_t hidden, int64_t inter, int dtype, hx_stream stream);
+/* deepseek_v3.py:148-154 and :120: out[t, c] = T( float(T( sum_k topk_weights[t, k] * float(y[t * topk + k, c]) )) +
+ * float(shared[t, c]) ), products and sum in fp32, k order; shared [n, h] (the shared experts' output) may be NULL:
+ * out = T(sum). */
+int hx_moe_combine(void* out, const void* y, const float* topk_weights, const void* shared, int64_t n_tokens,
+                   int64_t topk, int64_t hidden, int dtype, hx_stream stream);
+
+/* ------------------------------------------------------------------------
  * Focal image-token pruning without a score tensor (csrc/focal_prune.hip).
  * replaces: hydrainfer/layer/token_prunning.py:5-37 (focal_prunning) fed with the pre-softmax scaled logits of
  *           hydrainfer/layer/multihead_attention.py:59-62 (`attention_scores`, a view of `score` taken before the softmax)
