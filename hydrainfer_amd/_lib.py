@@ -155,6 +155,8 @@ _SIGNATURES = {
     "hx_moe_gate_up_silu": (c_int, [c_void_p] * 4 + [c_int64] * 5 + [c_int, c_void_p]),
     "hx_moe_down": (c_int, [c_void_p] * 4 + [c_int64] * 5 + [c_int, c_void_p]),
     "hx_moe_combine": (c_int, [c_void_p] * 4 + [c_int64] * 3 + [c_int, c_void_p]),
+    "hx_moe_gate_up_silu_fp8w": (c_int, [c_void_p] * 5 + [c_int64] * 5 + [c_int, c_void_p]),
+    "hx_moe_down_fp8w": (c_int, [c_void_p] * 5 + [c_int64] * 5 + [c_int, c_void_p]),
     "hx_decode_advance": (c_int, [c_void_p] * 6 + [c_int32, c_int32, c_int32, c_void_p]),
     "hx_decode_advance_ranked": (c_int, [c_void_p] * 6 + [c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "hx_decode_rank": (c_int, [c_void_p, c_int32, c_void_p, c_void_p]),

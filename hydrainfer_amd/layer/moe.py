@@ -5,7 +5,10 @@ MI355X-first differences (rounding-neutral with respect to the reference's ops, 
   * the routed experts' weights are STACKED ([E, 2I, h] gate rows then up rows, [E, h, I]) and run as two grouped
     weight-streaming launches (csrc/moe_experts.hip) instead of a Python loop of index-gather + three GEMMs per expert;
   * nothing is read back to the host (the reference's tokens_per_expert.cpu(), :130): the block captures into a hipGraph;
-  * the shared experts' gate and up projections are one fused [2 I_s, h] GEMM.
+  * the shared experts' gate and up projections are one fused [2 I_s, h] GEMM;
+  * the routed experts may be held as FP8 block-scaled bytes (float8_e4m3fn + one fp32 scale per 128 x 128 block, the
+    published DeepSeek-V3 format: csrc/moe_experts_fp8.hip) — opt-in, by quantize_experts() or by handing over such a state
+    dict; router and shared experts stay in T.
 HIP only: the router, the segments, both expert GEMMs and the combine are libhydra_hip launches; there is no fallback."""
 from typing import Callable, Dict, Optional
 
@@ -27,10 +30,18 @@ def _dense_linear(x: Tensor, w: Tensor) -> Tensor:
 class SparseMoE:
     def __init__(self, router_weight: Tensor, w_gate_up: Tensor, w_down: Tensor, shared_gate_up: Optional[Tensor],
                  shared_down: Optional[Tensor], num_experts_per_tok: int, norm_topk_prob: bool = False,
-                 routed_scaling_factor: float = 1.0, linear: Optional[Callable[[Tensor, Tensor], Tensor]] = None):
+                 routed_scaling_factor: float = 1.0, linear: Optional[Callable[[Tensor, Tensor], Tensor]] = None,
+                 w_gate_up_scale: Optional[Tensor] = None, w_down_scale: Optional[Tensor] = None):
         E, two_i, h = w_gate_up.shape
         if w_down.shape != (E, h, two_i // 2) or router_weight.shape != (E, h):
             raise ValueError("SparseMoE: router_weight [E, h], w_gate_up [E, 2I, h], w_down [E, h, I]")
+        if (w_gate_up_scale is None) != (w_down_scale is None):
+            raise ValueError("SparseMoE: fp8 experts need the scales of both weights")
+        if w_gate_up_scale is not None and (
+                w_gate_up.dtype != moe_experts.FP8 or w_down.dtype != moe_experts.FP8
+                or w_gate_up_scale.shape != (E, two_i // 128, h // 128) or w_down_scale.shape != (E, h // 128, two_i // 256)):
+            raise ValueError("SparseMoE: fp8 experts are float8_e4m3fn with scales [E, 2I/128, h/128] and [E, h/128, I/128]")
+        self.w_gate_up_scale, self.w_down_scale = w_gate_up_scale, w_down_scale
         if (shared_gate_up is None) != (shared_down is None):
             raise ValueError("SparseMoE: the shared experts need both weights")
         self.router_weight, self.w_gate_up, self.w_down = router_weight, w_gate_up, w_down
@@ -43,6 +54,17 @@ class SparseMoE:
     @property
     def n_experts(self) -> int:
         return self.w_gate_up.shape[0]
+
+    @property
+    def experts_fp8(self) -> bool:
+        return self.w_gate_up_scale is not None
+
+    def quantize_experts(self) -> "SparseMoE":
+        """The routed experts to FP8 block-scaled bytes, in place; the 16-bit tensors are dropped.  Idempotent."""
+        if not self.experts_fp8:
+            self.w_gate_up, self.w_gate_up_scale = moe_experts.quantize_fp8_block(self.w_gate_up)
+            self.w_down, self.w_down_scale = moe_experts.quantize_fp8_block(self.w_down)
+        return self
 
     def shared_experts(self, x: Tensor) -> Optional[Tensor]:
         """DeepseekV3MLP of intermediate size I * n_shared_experts (:110-112) on the dense ops."""
@@ -63,7 +85,8 @@ class SparseMoE:
         shared = self.shared_experts(x)
         if shared is not None and not shared.is_contiguous():
             shared = shared.contiguous()
-        return moe_experts.experts_forward(x, self.w_gate_up, self.w_down, w, ids, shared)
+        return moe_experts.experts_forward(x, self.w_gate_up, self.w_down, w, ids, shared, self.w_gate_up_scale,
+                                           self.w_down_scale)
 
     __call__ = forward
 
@@ -72,24 +95,42 @@ class SparseMoE:
                                   norm_topk_prob: bool = False, routed_scaling_factor: float = 1.0, dtype=None, device=None,
                                   linear=None) -> "SparseMoE":
         """prefix: up to and including "mlp." — reads {prefix}experts.{e}.{gate,up,down}_proj.weight, {prefix}gate.weight
-        and {prefix}shared_experts.{gate,up,down}_proj.weight (absent: no shared experts)."""
-        def t(name):
+        and {prefix}shared_experts.{gate,up,down}_proj.weight (absent: no shared experts).  Experts published as
+        float8_e4m3fn come with {...}_proj.weight_scale_inv ([N / 128, K / 128] fp32): bytes and scales are stacked as they
+        are (gate before up, the scales too), nothing is dequantised and `dtype` does not apply to them."""
+        def t(name, cast=True):
             v = sd[prefix + name]
-            return v.to(dtype=dtype or v.dtype, device=device or v.device)
+            return v.to(dtype=(dtype if cast else None) or v.dtype, device=device or v.device)
         n_e = 0
         while f"{prefix}experts.{n_e}.gate_proj.weight" in sd:
             n_e += 1
         if n_e == 0:
             raise KeyError(f"no {prefix}experts.0.gate_proj.weight in the state dict")
-        wgu = torch.stack([torch.cat([t(f"experts.{e}.gate_proj.weight"), t(f"experts.{e}.up_proj.weight")], dim=0)
-                           for e in range(n_e)]).contiguous()
-        wdown = torch.stack([t(f"experts.{e}.down_proj.weight") for e in range(n_e)]).contiguous()
+        fp8 = {sd[f"{prefix}experts.{e}.{p}_proj.weight"].dtype == moe_experts.FP8
+               for e in range(n_e) for p in ("gate", "up", "down")}
+        if len(fp8) != 1:
+            raise ValueError(f"{prefix}experts: float8_e4m3fn and 16-bit expert weights in one layer")
+        fp8 = fp8.pop()
+        gus = downs = None
+
+        def stack(suffix):
+            # float8 tensors are stacked through their bytes (torch.cat / stack of float8 is not everywhere available)
+            def b(name):
+                v = t(name, not fp8)
+                return v.view(torch.uint8) if v.dtype == moe_experts.FP8 else v
+            gu = torch.stack([torch.cat([b(f"experts.{e}.gate_proj.{suffix}"), b(f"experts.{e}.up_proj.{suffix}")], dim=0)
+                              for e in range(n_e)]).contiguous()
+            dn = torch.stack([b(f"experts.{e}.down_proj.{suffix}") for e in range(n_e)]).contiguous()
+            return (gu.view(moe_experts.FP8), dn.view(moe_experts.FP8)) if gu.dtype == torch.uint8 else (gu, dn)
+        wgu, wdown = stack("weight")
+        if fp8:
+            gus, downs = stack("weight_scale_inv")
         sgu = sdown = None
         if prefix + "shared_experts.gate_proj.weight" in sd:
             sgu = torch.cat([t("shared_experts.gate_proj.weight"), t("shared_experts.up_proj.weight")], dim=0).contiguous()
             sdown = t("shared_experts.down_proj.weight").contiguous()
         return cls(t("gate.weight").contiguous(), wgu, wdown, sgu, sdown, num_experts_per_tok, norm_topk_prob,
-                   routed_scaling_factor, linear)
+                   routed_scaling_factor, linear, gus, downs)
 
     def to_reference_state_dict(self, prefix: str) -> Dict[str, Tensor]:
         inter = self.w_gate_up.shape[1] // 2
@@ -99,6 +140,12 @@ class SparseMoE:
             sd[f"{prefix}experts.{e}.gate_proj.weight"] = wgu[e, :inter]
             sd[f"{prefix}experts.{e}.up_proj.weight"] = wgu[e, inter:]
             sd[f"{prefix}experts.{e}.down_proj.weight"] = wdown[e]
+        if self.experts_fp8:
+            gus, downs = self.w_gate_up_scale.cpu(), self.w_down_scale.cpu()
+            for e in range(self.n_experts):
+                sd[f"{prefix}experts.{e}.gate_proj.weight_scale_inv"] = gus[e, :inter // 128]
+                sd[f"{prefix}experts.{e}.up_proj.weight_scale_inv"] = gus[e, inter // 128:]
+                sd[f"{prefix}experts.{e}.down_proj.weight_scale_inv"] = downs[e]
         if self.shared_gate_up is not None:
             si = self.shared_gate_up.shape[0] // 2
             sgu = self.shared_gate_up.cpu()

@@ -28,7 +28,9 @@ class MoeShape(LlamaShape):
 
 class DeepseekMoeForCausalLM(LlamaForCausalLM):
     """state: the parent's names for attention, norms, embeddings and the dense layers; for a sparse layer l
-    l{l}.moe.router [E, h], l{l}.moe.wgu [E, 2I, h], l{l}.moe.wdown [E, h, I], l{l}.moe.sgu [2 I_s, h], l{l}.moe.sdown."""
+    l{l}.moe.router [E, h], l{l}.moe.wgu [E, 2I, h], l{l}.moe.wdown [E, h, I], l{l}.moe.sgu [2 I_s, h], l{l}.moe.sdown.
+    FP8 block-scaled routed experts (layer/moe.py): wgu / wdown are float8_e4m3fn and l{l}.moe.wgu_scale [E, 2I/128, h/128],
+    l{l}.moe.wdown_scale [E, h/128, I/128] (fp32) stand beside them."""
 
     def __init__(self, shape: MoeShape, dtype: torch.dtype, device, state: Dict[str, Tensor]):
         super().__init__(shape, dtype, device, state)
@@ -36,7 +38,8 @@ class DeepseekMoeForCausalLM(LlamaForCausalLM):
         for l in range(shape.first_k_dense_replace, shape.num_hidden_layers):
             s = lambda n: state.get(f"l{l}.moe.{n}")
             self.moe[l] = SparseMoE(s("router"), s("wgu"), s("wdown"), s("sgu"), s("sdown"), shape.num_experts_per_tok,
-                                    shape.norm_topk_prob, shape.routed_scaling_factor, linear=self.linear)
+                                    shape.norm_topk_prob, shape.routed_scaling_factor, linear=self.linear,
+                                    w_gate_up_scale=s("wgu_scale"), w_down_scale=s("wdown_scale"))
 
     # ------------------------------------------------------------------ the MLP hook and the decode plan
     def _mlp(self, l: int, x: Tensor) -> Tensor:
@@ -58,11 +61,23 @@ class DeepseekMoeForCausalLM(LlamaForCausalLM):
         super().release()
         self.moe = {}
 
+    def quantize_experts(self) -> "DeepseekMoeForCausalLM":
+        """The routed experts of every sparse layer to FP8 block-scaled bytes (SparseMoE.quantize_experts); the state
+        holds the bytes and the scales afterwards, the 16-bit tensors are dropped.  Idempotent."""
+        for l, m in self.moe.items():
+            m.quantize_experts()
+            self.state[f"l{l}.moe.wgu"], self.state[f"l{l}.moe.wdown"] = m.w_gate_up, m.w_down
+            self.state[f"l{l}.moe.wgu_scale"], self.state[f"l{l}.moe.wdown_scale"] = m.w_gate_up_scale, m.w_down_scale
+        return self
+
     # ------------------------------------------------------------------ construction
     @classmethod
     def random_init(cls, shape: MoeShape, dtype: torch.dtype, device, seed: int = 0, std: float = 0.02,
-                    router_std: float = 0.2, expert_std: float = None) -> "DeepseekMoeForCausalLM":
-        """N(0, std) linears and embeddings, N(0, router_std) routers, N(0, expert_std or std) routed and shared experts."""
+                    router_std: float = 0.2, expert_std: float = None, expert_dtype: str = None) -> "DeepseekMoeForCausalLM":
+        """N(0, std) linears and embeddings, N(0, router_std) routers, N(0, expert_std or std) routed and shared experts.
+        expert_dtype="fp8": the same draw, then quantize_experts()."""
+        if expert_dtype not in (None, "fp8"):
+            raise ValueError(f"random_init: expert_dtype {expert_dtype!r} (None or 'fp8')")
         g = torch.Generator(device=device).manual_seed(seed)
         h, L = shape.hidden_size, shape.num_hidden_layers
         q, kv = shape.num_attention_heads * shape.head_dim, shape.num_key_value_heads * shape.head_dim
@@ -89,13 +104,15 @@ class DeepseekMoeForCausalLM(LlamaForCausalLM):
                     st[f"l{l}.moe.sdown"] = w(h, Is, s=es)
             st[f"l{l}.norm1"] = torch.ones(h, dtype=dtype, device=device)
             st[f"l{l}.norm2"] = torch.ones(h, dtype=dtype, device=device)
-        return cls(shape, dtype, device, st)
+        model = cls(shape, dtype, device, st)
+        return model.quantize_experts() if expert_dtype == "fp8" else model
 
     @classmethod
     def from_reference_state_dict(cls, shape: MoeShape, sd: Dict[str, Tensor], dtype, device,
                                   prefix: str = "") -> "DeepseekMoeForCausalLM":
         """Names of hydrainfer/model/deepseek_v3.py: model.layers.N.mlp.experts.E.gate_proj.weight, ...mlp.gate.weight,
-        ...mlp.shared_experts.*; dense layers and attention as in the parent."""
+        ...mlp.shared_experts.*; dense layers and attention as in the parent.  Experts published as float8_e4m3fn with
+        ...weight_scale_inv are taken as they are: neither the bytes nor the scales are cast to `dtype`."""
         def t(name):
             return sd[prefix + name].to(dtype).to(device)
         st = {"embed": t("model.embed_tokens.weight"), "lm_head": t("lm_head.weight"), "norm": t("model.norm.weight")}
@@ -111,6 +128,8 @@ class DeepseekMoeForCausalLM(LlamaForCausalLM):
                 m = SparseMoE.from_reference_state_dict(prefix + p + "mlp.", sd, shape.num_experts_per_tok, dtype=dtype,
                                                         device=device)
                 st[f"l{l}.moe.router"], st[f"l{l}.moe.wgu"], st[f"l{l}.moe.wdown"] = m.router_weight, m.w_gate_up, m.w_down
+                if m.experts_fp8:
+                    st[f"l{l}.moe.wgu_scale"], st[f"l{l}.moe.wdown_scale"] = m.w_gate_up_scale, m.w_down_scale
                 if m.shared_gate_up is not None:
                     st[f"l{l}.moe.sgu"], st[f"l{l}.moe.sdown"] = m.shared_gate_up, m.shared_down
             st[f"l{l}.norm1"] = t(p + "input_layernorm.weight")
@@ -142,12 +161,15 @@ class DeepseekMoeForCausalLM(LlamaForCausalLM):
     # ------------------------------------------------------------------ byte models
     def weight_bytes(self, n_tokens: int = 1) -> int:
         """Bytes a decode step of n_tokens rows must stream at most: every dense linear, router and shared expert, the
-        lm_head, and per sparse layer min(E, n_tokens * topk) routed experts (the distinct experts a step can hit)."""
+        lm_head, and per sparse layer min(E, n_tokens * topk) routed experts (the distinct experts a step can hit) — at
+        one byte per element plus 4 bytes per 128 x 128 block where the layer's experts are FP8 block-scaled."""
         sh, es = self.shape, self.state["lm_head"].element_size()
-        n = sum(v.numel() for k, v in self.state.items() if k != "embed" and v.dim() == 2)
+        total = es * sum(v.numel() for k, v in self.state.items() if k != "embed" and v.dim() == 2)
         hit = min(sh.n_routed_experts, n_tokens * sh.num_experts_per_tok)
-        n += len(self.moe) * hit * 3 * sh.hidden_size * sh.moe_intermediate_size
-        return n * es
+        per_expert = 3 * sh.hidden_size * sh.moe_intermediate_size
+        for m in self.moe.values():
+            total += hit * (per_expert + 4 * per_expert // (128 * 128) if m.experts_fp8 else per_expert * es)
+        return total
 
     def weight_bytes_resident(self) -> int:
         """Bytes of HBM the weights occupy: one layout of everything, all experts included."""

@@ -900,6 +900,24 @@ int hx_moe_down(void* y, const void* act, const void* w_down, const int32_t* seg
  * out = T(sum). */
 int hx_moe_combine(void* out, const void* y, const float* topk_weights, const void* shared, int64_t n_tokens,
                    int64_t topk, int64_t hidden, int dtype, hx_stream stream);
+/* The two grouped GEMMs over FP8 block-scaled expert weights (csrc/moe_experts_fp8.hip): the format DeepSeek-V3-family
+ * checkpoints publish.  wq_gate_up [E, 2I, h] / wq_down [E, h, I]: one byte per element, OCP float8_e4m3fn (a byte 0x7F /
+ * 0xFF is a NaN weight), contiguous, 16-byte aligned; w_scale fp32 [E, 2I/128, h/128] resp. [E, h/128, I/128]
+ * (`weight_scale_inv`: weight = float(q) * scale, one scale per 128 x 128 block; gate rows then up rows, scales too).
+ * Weight-only: x / act / y stay T = `dtype` (HX_F16 / HX_BF16), seg is hx_moe_segments' output.  With
+ *   lin(row n of expert e, token row v) = T( sum_b w_scale[e, n / 128, b] * ( sum_{k in 128-block b} float(v[k]) * float(q[e, n, k]) ) )
+ * — the inner sums fp32 MFMA accumulation of exact products, a block's scale multiplying the block's fp32 partial sum in
+ * fp32 (one fma into the running sum), ONE rounding to T at the end, no weight ever rounded to T after scaling — act and
+ * y are what hx_moe_gate_up_silu / hx_moe_down define with lin in place of their dot products: the same silu * mul
+ * rounding points, the same slot order, the same grids; an expert with no rows reads no weight bytes and no scales.
+ * Status as the 16-bit entries: NULL (w_scale included) HX_ERR_NULL, the shape rules HX_ERR_SHAPE, fp32 HX_ERR_DTYPE;
+ * nothing is launched on a refusal. */
+int hx_moe_gate_up_silu_fp8w(void* act, const void* x, const void* wq_gate_up, const float* w_scale, const int32_t* seg,
+                             int64_t n_tokens, int64_t topk, int64_t n_experts, int64_t hidden, int64_t inter, int dtype,
+                             hx_stream stream);
+int hx_moe_down_fp8w(void* y, const void* act, const void* wq_down, const float* w_scale, const int32_t* seg,
+                     int64_t n_tokens, int64_t topk, int64_t n_experts, int64_t hidden, int64_t inter, int dtype,
+                     hx_stream stream);
 
 /* ------------------------------------------------------------------------
  * Focal image-token pruning without a score tensor (csrc/focal_prune.hip).
