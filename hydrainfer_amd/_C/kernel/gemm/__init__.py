@@ -60,6 +60,93 @@ def linear_decode_partial(x: Tensor, weight: Tensor, partial: Tensor) -> int:
 
 
 # ------------------------------------------------------------------------------------------------
+# FP8 block-scaled weights (csrc/gemm_skinny_fp8.hip): float8_e4m3fn bytes [N, K] + one fp32 scale per 128 x 128 block, the
+# published `weight_scale_inv` format.  quantize_fp8_block / dequantize_fp8_block live in _C/kernel/moe/experts.py.
+# ------------------------------------------------------------------------------------------------
+FP8_MAX_ROWS = 64
+
+
+def _fp8_weight(wq: Tensor, scale: Tensor, what: str, k_multiple: int) -> None:
+    """Refuses what is no FP8 block-scaled [N, K] weight with its scales, whatever the batch."""
+    from hydrainfer_amd._C.kernel.moe.experts import BLOCK, FP8
+    if wq.dtype not in (FP8, torch.uint8):
+        raise _lib.HydraHipError(f"{what}: the weight must be float8_e4m3fn (or uint8) bytes, got {wq.dtype}")
+    if wq.dim() != 2 or wq.stride(1) != 1 or wq.stride(0) % 16 or wq.stride(0) < wq.shape[1]:
+        raise _lib.HydraHipError(f"{what}: the weight must be [N, K] bytes with contiguous rows at a stride that is a multiple of 16")
+    N, K = wq.shape
+    if N == 0 or K == 0 or N % BLOCK or K % k_multiple:
+        raise _lib.HydraHipError(f"{what}: needs N % 128 == 0 and K % {k_multiple} == 0, got [{N}, {K}]")
+    if scale is None:
+        raise _lib.HydraHipError(f"{what}: fp8 bytes need their block scales")
+    if scale.dtype != torch.float32:
+        raise _lib.HydraHipError(f"{what}: the scale must be float32, got {scale.dtype}")
+    if tuple(scale.shape) != (N // BLOCK, K // BLOCK) or not scale.is_contiguous():
+        raise _lib.HydraHipError(f"{what}: the scale must be contiguous [{N // BLOCK}, {K // BLOCK}], got {list(scale.shape)}")
+    if scale.device != wq.device:
+        raise _lib.HydraHipError(f"{what}: the scale must be on the weight's device")
+
+
+def fp8_supported(x: Tensor, wq: Tensor, scale: Tensor) -> bool:
+    """Does linear_decode_fp8 take this batch?  Raises for a (wq, scale) pair that is no FP8 block-scaled weight or an x
+    that does not belong to it; False for what the kernel leaves to the dequantising path: more than 64 rows, K that is
+    no multiple of 256, or rows of x it cannot stage."""
+    _fp8_weight(wq, scale, "linear_decode_fp8", 128)
+    if x.dim() != 2 or x.shape[1] != wq.shape[1] or x.dtype not in (torch.float16, torch.bfloat16):
+        raise _lib.HydraHipError("linear_decode_fp8: x must be fp16 / bf16 [M, K] for a weight of [N, K] bytes")
+    return 1 <= x.shape[0] <= FP8_MAX_ROWS and wq.shape[1] % 256 == 0 and x.stride(1) == 1 and x.stride(0) % 8 == 0
+
+
+def linear_decode_fp8(x: Tensor, wq: Tensor, scale: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """out[M, N] = T( sum_b scale[n / 128, b] * (x[m, block b] . float(wq[n, block b])) ), M <= 64 (hx_linear_decode_fp8w:
+    fp32 sums of exact products, the scale on a block's fp32 partial sum, one rounding; no weight is rounded after scaling)."""
+    _lib.require_gpu(x, wq, scale, out)
+    if not fp8_supported(x, wq, scale):
+        raise _lib.HydraHipError("linear_decode_fp8: needs 1 <= M <= 64, K % 256 == 0 and rows of x with contiguous elements "
+                                 "at a stride that is a multiple of 8")
+    M, K = x.shape
+    N = wq.shape[0]
+    if out is None:
+        out = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    elif out.shape != (M, N) or out.dtype != x.dtype or out.stride(1) != 1 or out.stride(0) % 4:
+        raise _lib.HydraHipError("linear_decode_fp8: out must be [M, N] of x's dtype, contiguous rows, row stride % 4 == 0")
+    l = _lib.lib()
+    nbytes = l.hx_linear_decode_workspace_bytes(M, N, K)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    _lib.check(l.hx_linear_decode_fp8w(out.data_ptr(), x.data_ptr(), wq.data_ptr(), scale.data_ptr(), M, N, K, x.stride(0),
+                                       wq.stride(0), out.stride(0), ws.data_ptr(), nbytes, _lib.dtype_code(x),
+                                       _lib.current_stream()), "linear_decode_fp8")
+    return out
+
+
+def fp8_plan(M: int, N: int, K: int):
+    """(waves per workgroup, 16-row groups per wave) of the launch linear_decode_fp8 makes for M rows over [N, K] bytes
+    under the current options (hx_debug_linear_fp8_plan; host only)."""
+    out = (ctypes.c_int32 * 2)()
+    _lib.check(_lib.lib().hx_debug_linear_fp8_plan(M, N, K, out), "debug_linear_fp8_plan")
+    return out[0], out[1]
+
+
+def dequant_fp8_block(wq: Tensor, scale: Tensor, dtype: torch.dtype, out: Optional[Tensor] = None) -> Tensor:
+    """out[N, K] = T(float(wq) * scale of its block): one fp32 multiply, one rounding (hx_dequant_fp8_block)."""
+    _lib.require_gpu(wq, scale, out)
+    _fp8_weight(wq, scale, "dequant_fp8_block", 128)
+    if dtype not in (torch.float16, torch.bfloat16):
+        raise _lib.HydraHipError(f"dequant_fp8_block: fp16 / bf16 output, got {dtype}")
+    if not wq.is_contiguous():
+        raise _lib.HydraHipError("dequant_fp8_block: the weight must be contiguous")
+    N, K = wq.shape
+    if out is None:
+        out = torch.empty((N, K), dtype=dtype, device=wq.device)
+    elif out.shape != (N, K) or out.dtype != dtype or out.stride(1) != 1 or out.stride(0) % 8 or out.device != wq.device:
+        raise _lib.HydraHipError("dequant_fp8_block: out must be [N, K] of `dtype` on the weight's device, contiguous rows, "
+                                 "row stride % 8 == 0")
+    _lib.check(_lib.lib().hx_dequant_fp8_block(out.data_ptr(), wq.data_ptr(), scale.data_ptr(), N, K, out.stride(0),
+                                               _lib.HX_F16 if dtype == torch.float16 else _lib.HX_BF16,
+                                               _lib.current_stream()), "dequant_fp8_block")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 def pack_weight(weight: Tensor) -> Tensor:
     """weight [N, K] -> flat [N*K] in MFMA-fragment order (hx_pack_decode_weight)."""
     _lib.require_gpu(weight)

@@ -98,6 +98,9 @@ _SIGNATURES = {
     "hx_linear_decode_workspace_bytes": (c_int64, [c_int64] * 3),
     "hx_linear_decode": (c_int, [c_void_p] * 3 + [c_int64] * 6 + [c_void_p, c_int64, c_int, c_void_p]),
     "hx_linear_decode_partial": (c_int, [c_void_p] * 3 + [c_int64] * 6 + [c_int, c_void_p]),
+    "hx_linear_decode_fp8w": (c_int, [c_void_p] * 4 + [c_int64] * 6 + [c_void_p, c_int64, c_int, c_void_p]),
+    "hx_debug_linear_fp8_plan": (c_int, [c_int64] * 3 + [POINTER(c_int32)]),
+    "hx_dequant_fp8_block": (c_int, [c_void_p] * 3 + [c_int64] * 3 + [c_int, c_void_p]),
     "hx_pack_decode_weight": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p]),
     "hx_linear_decode_partial_packed": (c_int, [c_void_p] * 3 + [c_int64] * 5 + [c_int, c_void_p]),
     "hx_linear_decode_xreg_supported": (c_int, [c_int64] * 3),

@@ -14,6 +14,7 @@ int& last_hip_error() {
 bool decode_supported(int head_dim);
 int decode_set_option(const char* name, int value);
 int gemm_set_option(const char* name, int value);
+int gemm_fp8_set_option(const char* name, int value);
 int fwd_set_option(const char* name, int value);
 int xreg_set_option(const char* name, int value);
 void fwd_set_stamps(void* buf);
@@ -50,6 +51,7 @@ extern "C" int hx_debug_set_option(const char* name, int value) {
   if (!strcmp(name, "fwd_xcd_remap")) { g_fwd_xcd = value ? 1 : 0; return HX_OK; }
   int rc = decode_set_option(name, value);
   if (rc == HX_ERR_UNSUPPORTED) rc = gemm_set_option(name, value);
+  if (rc == HX_ERR_UNSUPPORTED) rc = gemm_fp8_set_option(name, value);
   if (rc == HX_ERR_UNSUPPORTED) rc = fwd_set_option(name, value);
   if (rc == HX_ERR_UNSUPPORTED) rc = xreg_set_option(name, value);
 #if HX_EXPERIMENTS

@@ -8,7 +8,8 @@ MI355X-first differences (rounding-neutral with respect to the reference's ops, 
   * the shared experts' gate and up projections are one fused [2 I_s, h] GEMM;
   * the routed experts may be held as FP8 block-scaled bytes (float8_e4m3fn + one fp32 scale per 128 x 128 block, the
     published DeepSeek-V3 format: csrc/moe_experts_fp8.hip) — opt-in, by quantize_experts() or by handing over such a state
-    dict; router and shared experts stay in T.
+    dict — and so may the shared experts (quantize_shared(); csrc/gemm_skinny_fp8.hip through the dense ops); the router
+    stays in T.
 HIP only: the router, the segments, both expert GEMMs and the combine are libhydra_hip launches; there is no fallback."""
 from typing import Callable, Dict, Optional
 
@@ -19,9 +20,15 @@ from hydrainfer_amd._C.kernel.activation import silu_and_mul
 from hydrainfer_amd._C.kernel.moe import experts as moe_experts
 
 
-def _dense_linear(x: Tensor, w: Tensor) -> Tensor:
-    """x @ w^T on the dense ops of the decoder: the weight-streaming HIP GEMM at decode sizes, the library GEMM above."""
+def _dense_linear(x: Tensor, w: Tensor, scale: Optional[Tensor] = None) -> Tensor:
+    """x @ w^T on the dense ops of the decoder: the weight-streaming HIP GEMM at decode sizes, the library GEMM above.
+    scale given: w is FP8 block-scaled bytes — the FP8 decode GEMM, or above 64 rows the library GEMM over T(q * s)
+    (LlamaForCausalLM.linear, which keeps one scratch tensor for that copy; here it is a fresh one)."""
     from hydrainfer_amd._C.kernel import gemm as hip_gemm
+    if scale is not None:
+        if hip_gemm.fp8_supported(x, w, scale):
+            return hip_gemm.linear_decode_fp8(x, w, scale)
+        return torch.matmul(x, hip_gemm.dequant_fp8_block(w, scale, x.dtype).t())
     if x.shape[0] <= 64 and hip_gemm.supported(x, w):
         return hip_gemm.linear_decode(x, w)
     return torch.matmul(x, w.t())
@@ -30,8 +37,10 @@ def _dense_linear(x: Tensor, w: Tensor) -> Tensor:
 class SparseMoE:
     def __init__(self, router_weight: Tensor, w_gate_up: Tensor, w_down: Tensor, shared_gate_up: Optional[Tensor],
                  shared_down: Optional[Tensor], num_experts_per_tok: int, norm_topk_prob: bool = False,
-                 routed_scaling_factor: float = 1.0, linear: Optional[Callable[[Tensor, Tensor], Tensor]] = None,
-                 w_gate_up_scale: Optional[Tensor] = None, w_down_scale: Optional[Tensor] = None):
+                 routed_scaling_factor: float = 1.0, linear: Optional[Callable[..., Tensor]] = None,
+                 w_gate_up_scale: Optional[Tensor] = None, w_down_scale: Optional[Tensor] = None,
+                 shared_gate_up_scale: Optional[Tensor] = None, shared_down_scale: Optional[Tensor] = None):
+        """linear(x, w, scale=None): the dense x @ w^T; it is handed a scale only for FP8 shared experts."""
         E, two_i, h = w_gate_up.shape
         if w_down.shape != (E, h, two_i // 2) or router_weight.shape != (E, h):
             raise ValueError("SparseMoE: router_weight [E, h], w_gate_up [E, 2I, h], w_down [E, h, I]")
@@ -44,8 +53,22 @@ class SparseMoE:
         self.w_gate_up_scale, self.w_down_scale = w_gate_up_scale, w_down_scale
         if (shared_gate_up is None) != (shared_down is None):
             raise ValueError("SparseMoE: the shared experts need both weights")
+        if (shared_gate_up_scale is None) != (shared_down_scale is None):
+            raise ValueError("SparseMoE: fp8 shared experts need the scales of both weights")
+        if shared_gate_up_scale is not None:
+            if shared_gate_up is None:
+                raise ValueError("SparseMoE: shared expert scales without shared experts")
+            for w, sc, name in ((shared_gate_up, shared_gate_up_scale, "shared_gate_up"), (shared_down, shared_down_scale, "shared_down")):
+                if (w.dtype != moe_experts.FP8 or w.dim() != 2 or sc.dtype != torch.float32
+                        or tuple(sc.shape) != (w.shape[0] // 128, w.shape[1] // 128) or w.shape[0] % 128 or w.shape[1] % 128):
+                    raise ValueError(f"SparseMoE: fp8 {name} is float8_e4m3fn [N, K] with an fp32 scale [N/128, K/128]")
+            if shared_gate_up.shape[0] % 256:
+                raise ValueError("SparseMoE: fp8 shared experts need an intermediate size that is a multiple of 128")
+        elif shared_gate_up is not None and moe_experts.FP8 in (shared_gate_up.dtype, shared_down.dtype):
+            raise ValueError("SparseMoE: float8_e4m3fn shared experts need their block scales (shared_gate_up_scale, shared_down_scale)")
         self.router_weight, self.w_gate_up, self.w_down = router_weight, w_gate_up, w_down
         self.shared_gate_up, self.shared_down = shared_gate_up, shared_down
+        self.shared_gate_up_scale, self.shared_down_scale = shared_gate_up_scale, shared_down_scale
         self.num_experts_per_tok, self.norm_topk_prob = int(num_experts_per_tok), bool(norm_topk_prob)
         self.routed_scaling_factor = float(routed_scaling_factor)
         self.linear = linear or _dense_linear
@@ -66,11 +89,27 @@ class SparseMoE:
             self.w_down, self.w_down_scale = moe_experts.quantize_fp8_block(self.w_down)
         return self
 
+    @property
+    def shared_fp8(self) -> bool:
+        return self.shared_gate_up_scale is not None
+
+    def quantize_shared(self) -> "SparseMoE":
+        """The shared experts to FP8 block-scaled bytes, in place; the 16-bit tensors are dropped.  Idempotent."""
+        if self.shared_gate_up is not None and not self.shared_fp8:
+            if self.shared_gate_up.shape[0] % 256:
+                raise ValueError("quantize_shared: the shared experts' intermediate size must be a multiple of 128")
+            self.shared_gate_up, self.shared_gate_up_scale = moe_experts.quantize_fp8_block(self.shared_gate_up)
+            self.shared_down, self.shared_down_scale = moe_experts.quantize_fp8_block(self.shared_down)
+        return self
+
     def shared_experts(self, x: Tensor) -> Optional[Tensor]:
         """DeepseekV3MLP of intermediate size I * n_shared_experts (:110-112) on the dense ops."""
         if self.shared_gate_up is None:
             return None
         inter = self.shared_gate_up.shape[0] // 2
+        if self.shared_fp8:
+            gu = self.linear(x, self.shared_gate_up, self.shared_gate_up_scale)
+            return self.linear(silu_and_mul(gu[:, :inter], gu[:, inter:]), self.shared_down, self.shared_down_scale)
         gu = self.linear(x, self.shared_gate_up)
         return self.linear(silu_and_mul(gu[:, :inter], gu[:, inter:]), self.shared_down)
 
@@ -97,7 +136,9 @@ class SparseMoE:
         """prefix: up to and including "mlp." — reads {prefix}experts.{e}.{gate,up,down}_proj.weight, {prefix}gate.weight
         and {prefix}shared_experts.{gate,up,down}_proj.weight (absent: no shared experts).  Experts published as
         float8_e4m3fn come with {...}_proj.weight_scale_inv ([N / 128, K / 128] fp32): bytes and scales are stacked as they
-        are (gate before up, the scales too), nothing is dequantised and `dtype` does not apply to them."""
+        are (gate before up, the scales too), nothing is dequantised and `dtype` does not apply to them.  The same holds
+        for shared experts published as float8_e4m3fn: a missing ...weight_scale_inv is a KeyError that names it, gate and
+        up projections of different dtypes are refused."""
         def t(name, cast=True):
             v = sd[prefix + name]
             return v.to(dtype=(dtype if cast else None) or v.dtype, device=device or v.device)
@@ -125,12 +166,29 @@ class SparseMoE:
         wgu, wdown = stack("weight")
         if fp8:
             gus, downs = stack("weight_scale_inv")
-        sgu = sdown = None
+        sgu = sdown = sgus = sdowns = None
         if prefix + "shared_experts.gate_proj.weight" in sd:
-            sgu = torch.cat([t("shared_experts.gate_proj.weight"), t("shared_experts.up_proj.weight")], dim=0).contiguous()
-            sdown = t("shared_experts.down_proj.weight").contiguous()
+            s_fp8 = {p: sd[f"{prefix}shared_experts.{p}_proj.weight"].dtype == moe_experts.FP8 for p in ("gate", "up", "down")}
+            if s_fp8["gate"] != s_fp8["up"]:
+                raise ValueError(f"{prefix}shared_experts: gate_proj and up_proj differ in dtype (one is float8_e4m3fn)")
+            if s_fp8["gate"] != s_fp8["down"]:
+                raise ValueError(f"{prefix}shared_experts: float8_e4m3fn and 16-bit projections in one layer")
+            if s_fp8["gate"]:
+                def q(p):
+                    name = f"{prefix}shared_experts.{p}_proj.weight_scale_inv"
+                    if name not in sd:
+                        raise KeyError(f"{name}: the float8_e4m3fn weight beside it needs its block scales")
+                    return (t(f"shared_experts.{p}_proj.weight", False).view(torch.uint8),
+                            sd[name].to(device=device or sd[name].device))
+                (qg, sg), (qu, su), (qd, sdn) = q("gate"), q("up"), q("down")
+                sgu = torch.cat([qg, qu], dim=0).contiguous().view(moe_experts.FP8)
+                sdown = qd.contiguous().view(moe_experts.FP8)
+                sgus, sdowns = torch.cat([sg, su], dim=0).contiguous(), sdn.contiguous()
+            else:
+                sgu = torch.cat([t("shared_experts.gate_proj.weight"), t("shared_experts.up_proj.weight")], dim=0).contiguous()
+                sdown = t("shared_experts.down_proj.weight").contiguous()
         return cls(t("gate.weight").contiguous(), wgu, wdown, sgu, sdown, num_experts_per_tok, norm_topk_prob,
-                   routed_scaling_factor, linear, gus, downs)
+                   routed_scaling_factor, linear, gus, downs, sgus, sdowns)
 
     def to_reference_state_dict(self, prefix: str) -> Dict[str, Tensor]:
         inter = self.w_gate_up.shape[1] // 2
@@ -152,4 +210,9 @@ class SparseMoE:
             sd[prefix + "shared_experts.gate_proj.weight"] = sgu[:si]
             sd[prefix + "shared_experts.up_proj.weight"] = sgu[si:]
             sd[prefix + "shared_experts.down_proj.weight"] = self.shared_down.cpu()
+            if self.shared_fp8:
+                sgus = self.shared_gate_up_scale.cpu()
+                sd[prefix + "shared_experts.gate_proj.weight_scale_inv"] = sgus[:si // 128]
+                sd[prefix + "shared_experts.up_proj.weight_scale_inv"] = sgus[si // 128:]
+                sd[prefix + "shared_experts.down_proj.weight_scale_inv"] = self.shared_down_scale.cpu()
         return sd

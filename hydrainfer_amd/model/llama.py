@@ -73,9 +73,20 @@ def build_cos_sin(shape: LlamaShape, dtype: torch.dtype, device) -> Tensor:
 class LlamaForCausalLM:
     """Weights live in fused device tensors; `state` maps fused names to tensors."""
 
+    # FP8 block-scaled dense linears (state[key] float8_e4m3fn + state[key + "_scale"]): only a subclass whose decode
+    # step runs on the general path offers them (model/deepseek_moe.py) — the in-register decode plan packs 16-bit weights
+    fp8_dense = False
+
     def __init__(self, shape: LlamaShape, dtype: torch.dtype, device, state: Dict[str, Tensor]):
         self.shape, self.dtype, self.device = shape, dtype, torch.device(device)
         self.state = state
+        if not self.fp8_dense:
+            fp8 = sorted(k for k, v in state.items() if k.endswith("_scale") or v.dtype == torch.float8_e4m3fn)
+            if fp8:
+                raise ValueError(f"{type(self).__name__}: FP8 block-scaled weights ({', '.join(fp8[:4])}{', ...' if len(fp8) > 4 else ''}) "
+                                 "are not supported by this model's decode plan, which packs 16-bit weights; "
+                                 "DeepseekMoeForCausalLM runs them")
+        self.fp8_scratch: Optional[Tensor] = None   # T [elements of the largest FP8 dense weight]: linear()'s dequantised copy
         self.cos_sin = build_cos_sin(shape, dtype, self.device)
         self.q_size = shape.num_attention_heads * shape.head_dim
         self.kv_size = shape.num_key_value_heads * shape.head_dim
@@ -150,7 +161,7 @@ class LlamaForCausalLM:
     def release(self) -> None:
         """Drops every weight tensor (bench.py frees the 7B model before its 13B leg)."""
         self.state, self.packed, self.packed_x, self.dw, self.dw_lds = {}, {}, {}, {}, {}
-        self.xreg_sync = self.decode_layouts = None
+        self.xreg_sync = self.decode_layouts = self.fp8_scratch = None
 
     def handover_failed(self) -> bool:
         """True if an in-kernel hand-over of the last decode step gave up waiting (word 1 of a norm-fused
@@ -212,13 +223,33 @@ class LlamaForCausalLM:
                                f"max_rows={self.decode_rows_prepared}) was called) and the row-major weight is released")
         return hip_gemm.linear_decode_partial(x, self.state[key], ws)
 
-    def linear(self, x: Tensor, w: Tensor) -> Tensor:
+    def linear(self, x: Tensor, w: Tensor, scale: Optional[Tensor] = None) -> Tensor:
+        """x @ w^T.  scale given: w is FP8 block-scaled bytes (float8_e4m3fn, one fp32 scale per 128 x 128 block).  Up to
+        64 rows run on csrc/gemm_skinny_fp8.hip, which applies a block's scale to the block's fp32 partial sum and never
+        rounds a scaled weight.  Larger batches (prefill) dequantise the weight into the model's scratch tensor
+        (hx_dequant_fp8_block) and call the library GEMM: they multiply by T(q * s), a scaled weight ROUNDED to T — at
+        most half an ulp of T per weight away from what decode multiplies by."""
         if w.device.type == "meta":
             raise RuntimeError("decode-only model (prepare_decode(keep_row_major=False)): prefill / row-major GEMMs "
                                "are not available on this node")
+        if scale is not None:
+            if not self.fp8_dense:
+                raise ValueError(f"{type(self).__name__}.linear: FP8 block-scaled weights are not supported by this model")
+            if self.use_hip_gemm and hip_gemm.fp8_supported(x, w, scale):
+                return hip_gemm.linear_decode_fp8(x, w, scale)
+            return torch.matmul(x, self._dequantised(w, scale, x.dtype).t())
         if self.use_hip_gemm and x.shape[0] <= 64 and hip_gemm.supported(x, w):
             return hip_gemm.linear_decode(x, w)
         return torch.matmul(x, w.t())
+
+    def _dequantised(self, w: Tensor, scale: Tensor, dtype: torch.dtype) -> Tensor:
+        """T(q * s) of an FP8 weight as a [N, K] view of ONE scratch tensor: sized to the largest FP8 2-d weight of the
+        state, allocated at first use, reused by every call in stream order (its reader is the GEMM that follows)."""
+        buf = self.fp8_scratch
+        if buf is None or buf.dtype != dtype or buf.numel() < w.numel():
+            n = max([v.numel() for v in self.state.values() if v.dim() == 2 and v.dtype == torch.float8_e4m3fn] + [w.numel()])
+            buf = self.fp8_scratch = torch.empty(n, dtype=dtype, device=w.device)
+        return hip_gemm.dequant_fp8_block(w, scale, dtype, out=buf[:w.numel()].view(w.shape))
 
     # ------------------------------------------------------------------ construction
     @classmethod
@@ -422,9 +453,9 @@ class LlamaForCausalLM:
         """Layer l's feed-forward on the general path: down(silu(gate(x)) * up(x)).  A subclass with another MLP
         (model/deepseek_moe.py) overrides this."""
         inter = self.shape.intermediate_size
-        gu = self.linear(x, self.state[f"l{l}.wgu"])
+        gu = self.linear(x, self.state[f"l{l}.wgu"], self.state.get(f"l{l}.wgu_scale"))
         act = silu_and_mul(gu[:, :inter], gu[:, inter:])
-        return self.linear(act, self.state[f"l{l}.wdown"])
+        return self.linear(act, self.state[f"l{l}.wdown"], self.state.get(f"l{l}.wdown_scale"))
 
     def forward_hidden(self, input_ids_or_embeds: Tensor, position_ids: Tensor,
                        model_params: LanguageModelParameters) -> Tensor:
@@ -467,7 +498,7 @@ class LlamaForCausalLM:
             rms_norm(x, h, st["l0.norm1"], eps)
         for l in range(L):
             ap = model_params.attention_params[l]
-            qkv = self.linear(x, st[f"l{l}.wqkv"])
+            qkv = self.linear(x, st[f"l{l}.wqkv"], st.get(f"l{l}.wqkv_scale"))
             q = qkv[:, :q_size].view(n, H, D)
             k = qkv[:, q_size:q_size + kv_size].view(n, HK, D)
             v = qkv[:, q_size + kv_size:].view(n, HK, D)
@@ -485,7 +516,7 @@ class LlamaForCausalLM:
                 mha_varlen_fwd(o, q, kc, vc, ap.q_cu_seq_lens, ap.kv_cu_seq_lens, ap.block_tables,
                                ap.cu_blocks_lens, None, ap.q_max_seq_len, ap.kv_max_seq_len,
                                D ** -0.5, 0, -1, 0, 0)
-            a = self.linear(o.view(n, q_size), st[f"l{l}.wo"])
+            a = self.linear(o.view(n, q_size), st[f"l{l}.wo"], st.get(f"l{l}.wo_scale"))
             # h += a ; x = norm2(h)
             add_rms_norm(x, h, a, st[f"l{l}.norm2"], eps)
             if (not model_params.all_sequences_decode) and l == L - 1 \

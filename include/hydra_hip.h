@@ -217,6 +217,34 @@ int hx_pack_decode_weight(void* packed, const void* weight, int64_t N, int64_t K
 int hx_linear_decode_partial_packed(float* partial, const void* x, const void* packed_weight,
                                     int64_t M, int64_t N, int64_t K, int64_t ldx,
                                     int64_t partial_bytes, int dtype, hx_stream stream);
+/* The decode-batch linear layer over an FP8 block-scaled weight (csrc/gemm_skinny_fp8.hip): the format DeepSeek-V3-family
+ * checkpoints publish for their dense linears.  wq [N, K]: one byte per element, OCP float8_e4m3fn (a byte 0x7F / 0xFF is
+ * a NaN weight), row stride ldw BYTES (a multiple of 16, >= K), 16-byte aligned; w_scale: contiguous fp32 [N / 128, K / 128]
+ * (`weight_scale_inv`: weight = float(q) * scale, one scale per 128 x 128 block).  Weight-only: x [M, K] (row stride ldx
+ * elements, a multiple of 8) and out [M, N] (row stride ldo elements, a multiple of 4) are T = `dtype` (HX_F16 / HX_BF16).
+ * M 1 .. 64, N % 128 == 0, K % 256 == 0; workspace >= hx_linear_decode_workspace_bytes(M, N, K), 16-byte aligned.
+ *   out[m][n] = T( sum over splits s (of 1024 k, in order) of
+ *                  sum over the 128-k blocks b of split s (in order) of
+ *                  w_scale[n / 128][b] * ( sum_{k in b} float(x[m][k]) * float(q[n][k]) ) )
+ * — every sum an fp32 sum of exact products (MFMA accumulation inside a block), a block's scale applied to that block's
+ * fp32 partial sum with ONE fma into the split's running sum, ONE rounding to T (in the slab reduce, deterministic, no
+ * atomics); a weight is never rounded after it has been scaled.  Nothing outside [N, K] of wq (row gaps included) and
+ * nothing outside w_scale reaches a result.
+ * Status as hx_linear_decode: non-positive sizes and the shape / stride rules HX_ERR_SHAPE, NULL (w_scale included)
+ * HX_ERR_NULL, fp32 HX_ERR_DTYPE, a small workspace HX_ERR_WORKSPACE, misaligned bases HX_ERR_STRIDE; nothing is launched
+ * on a refusal.  "gemm_fp8_waves" / "gemm_fp8_rows_per_wave" (hx_debug_set_option; 0 = automatic) force the launch's
+ * waves per workgroup / 16-row groups per wave — results are identical for every built pair; a pair that is not built for
+ * the batch's row blocks is HX_ERR_UNSUPPORTED.  hx_debug_linear_fp8_plan (host only) writes the (waves, row groups per
+ * wave) the launch of (M, N, K) makes under the current options into out[0..1].
+ * hx_dequant_fp8_block: out[n][k] = T(float(q[n][k]) * w_scale[n / 128][k / 128]) — one fp32 multiply, one rounding — for the
+ * library GEMM of batches above 64 rows.  wq contiguous [N, K], N % 128 == 0, K % 128 == 0; out row stride ldo elements
+ * (a multiple of 8, >= K), 16-byte aligned. */
+int hx_linear_decode_fp8w(void* out, const void* x, const void* wq, const float* w_scale, int64_t M, int64_t N, int64_t K,
+                          int64_t ldx, int64_t ldw, int64_t ldo, void* workspace, int64_t workspace_bytes, int dtype,
+                          hx_stream stream);
+int hx_debug_linear_fp8_plan(int64_t M, int64_t N, int64_t K, int32_t* out);
+int hx_dequant_fp8_block(void* out, const void* wq, const float* w_scale, int64_t N, int64_t K, int64_t ldo, int dtype,
+                         hx_stream stream);
 /* Step-edge fusions of a decode loop (extensions, bit-identical to the ops they replace).
  * hx_embed_rms_norm: h_out[r] = table[ids[r]] (torch.nn.functional.embedding; ids int32 or int64, out-of-range
  * ids clamp) and x_out[r] = rms_norm(h_out[r]) * weight, one launch (hydrainfer/model/llama.py:80-83 + layer/norm.py).
