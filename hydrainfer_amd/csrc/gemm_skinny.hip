@@ -64,23 +64,10 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(const GemmParams p
   // skipped at the store)
   const int rg0 = blockIdx.x * (NW * R) + w;
 
-  // ---- 1. x slice -> registers.  The LDS image always spans kMaxKs k-steps; k beyond this
-  // split's range and rows beyond M are zero, so a short last split needs no predication.
-  constexpr int kCpr = kMaxKs * 4;                         // 16-byte chunks per LDS row
-  constexpr int XPT = MB * 16 * kCpr / kThreads;           // chunks per thread
-  u16x8 xr[XPT];
-  {
-    const u16* xb = reinterpret_cast<const u16*>(p.x) + (int64_t)ks0 * 32;
-#pragma unroll
-    for (int j = 0; j < XPT; ++j) {
-      const int i = threadIdx.x + j * kThreads;
-      const int row = i / kCpr, ch = i % kCpr;
-      const bool ok = row < p.M && ch * 8 < KR;
-      // always a valid address; the zero-fill select happens at the LDS write so that no
-      // loaded value is consumed before the weight prefetch has been issued
-      xr[j] = *reinterpret_cast<const u16x8*>(xb + (int64_t)(ok ? row : 0) * p.ldx + (ok ? ch * 8 : 0));
-    }
-  }
+  // ---- 1. x slice -> registers
+  const u16* xb = reinterpret_cast<const u16*>(p.x) + (int64_t)ks0 * 32;
+  constexpr bool kNoXLoads = false;
+#include "gemm_skinny_x_load.inc"
 
   // ---- 2. W prefetch.  Load layout: instruction j of a chunk covers rows 8*(j&1) + (lane>>3)
   // and the 128-byte column block j>>1 (2 k-steps); lane&7 selects the 16-byte piece.
@@ -106,21 +93,13 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(const GemmParams p
   __builtin_amdgcn_sched_barrier(0);
 
   // ---- 3. x slice -> LDS
-#pragma unroll
-  for (int j = 0; j < XPT; ++j) {
-    const int i = threadIdx.x + j * kThreads;
-    const int row = i / kCpr, ch = i % kCpr;
-    const bool ok = row < p.M && ch * 8 < KR;
-    *reinterpret_cast<u16x8*>(smem + row * kRS + ch * 16) = ok ? xr[j] : u16x8{0, 0, 0, 0, 0, 0, 0, 0};
-  }
+#include "gemm_skinny_x_store.inc"
   __syncthreads();
 
-  // wave-private transpose image: [16 rows][128 B], 16-byte slot s of row r stored at slot
-  // s ^ ((r >> 1) & 7): row writes (8 lanes x 16 B per row, two rows per 16-lane group) and
-  // A-fragment reads (lane (r,g) <- row r, slot 4*st+g) are both bank-conflict free.
-  char* tl = smem + MB * 16 * kRS + w * 2048;
-  const int wr_off0 = lrow * 128 + 16 * (lpiece ^ ((lrow >> 1) & 7));
-  const int wr_off1 = (lrow + 8) * 128 + 16 * (lpiece ^ (((lrow + 8) >> 1) & 7));
+  // the wave-private transpose images lie behind the x slice
+  char* images = smem + MB * 16 * kRS;
+#include "wstream_image.inc"
+  constexpr int nmb = MB;                        // every 16-row block of the x image takes part
   const char* xl = smem + c * kRS + g * 16;
   f32x4 acc[MB];
 #pragma unroll
@@ -130,21 +109,11 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(const GemmParams p
   for (int it = 0; it < 2 * R; ++it) {
     const int rgi = it >> 1, ch = it & 1;
     const char* xp = xl + ch * (kChunk * 64);
+    const u16x8 (&wbuf)[kChunk] = buf[it & 1];
+    f32x4 (&accb)[MB] = acc;
 #pragma unroll
     for (int cb = 0; cb < kChunk / 2; ++cb) {
-      *reinterpret_cast<u16x8*>(tl + wr_off0) = buf[it & 1][2 * cb];
-      *reinterpret_cast<u16x8*>(tl + wr_off1) = buf[it & 1][2 * cb + 1];
-      __builtin_amdgcn_wave_barrier();
-#pragma unroll
-      for (int st = 0; st < 2; ++st) {
-        const u16x8 af = *reinterpret_cast<const u16x8*>(tl + r * 128 + 16 * ((4 * st + g) ^ ((r >> 1) & 7)));
-#pragma unroll
-        for (int mb = 0; mb < MB; ++mb) {
-          const u16x8 xf = *reinterpret_cast<const u16x8*>(xp + mb * 16 * kRS + (2 * cb + st) * 64);
-          acc[mb] = Mfma<T>::mma(af, xf, acc[mb]);
-        }
-      }
-      __builtin_amdgcn_wave_barrier();
+#include "wstream_block16.inc"
     }
     if (it + 2 < 2 * R) load(buf[it & 1], it + 2);
     if (ch == 1) {
@@ -192,20 +161,9 @@ __global__ __launch_bounds__(NW * 64) void gemm_packed_kernel(const void* __rest
   const int n_rg_all = p.N >> 4;
   const int rg0 = blockIdx.x * (NW * R) + w;
 
-  constexpr int kCpr = kMaxKs * 4;
-  constexpr int XPT = MB * 16 * kCpr / kThreads;
-  u16x8 xr[XPT];
-  {
-    const u16* xb = reinterpret_cast<const u16*>(p.x) + (int64_t)ks0 * 32;
-#pragma unroll
-    for (int j = 0; j < XPT; ++j) {
-      const int i = threadIdx.x + j * kThreads;
-      const int row = i / kCpr, ch = i % kCpr;
-      const bool ok = row < p.M && ch * 8 < KR;
-      if (DBG & 4) xr[j] = u16x8{1, 2, 3, 4, 5, 6, 7, 8};   // ablation: no x loads
-      else xr[j] = *reinterpret_cast<const u16x8*>(xb + (int64_t)(ok ? row : 0) * p.ldx + (ok ? ch * 8 : 0));
-    }
-  }
+  const u16* xb = reinterpret_cast<const u16*>(p.x) + (int64_t)ks0 * 32;
+  constexpr bool kNoXLoads = DBG & 4;            // ablation: no x loads
+#include "gemm_skinny_x_load.inc"
   // the fragments of (split, rg) are one run of nks KiB at KiB offset ks0 * n_rg + rg * nks: the
   // row groups of a split are adjacent, so the waves of a launch sweep consecutive memory (a
   // layout with each row group's whole K contiguous puts concurrent waves 128 KiB apart — all on
@@ -226,13 +184,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_packed_kernel(const void* __rest
   load(buf[0], 0);
   load(buf[1], 1);
   __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-  for (int j = 0; j < XPT; ++j) {
-    const int i = threadIdx.x + j * kThreads;
-    const int row = i / kCpr, ch = i % kCpr;
-    const bool ok = row < p.M && ch * 8 < KR;
-    *reinterpret_cast<u16x8*>(smem + row * kRS + ch * 16) = ok ? xr[j] : u16x8{0, 0, 0, 0, 0, 0, 0, 0};
-  }
+#include "gemm_skinny_x_store.inc"
   __syncthreads();
 
   const char* xl = smem + c * kRS + g * 16;

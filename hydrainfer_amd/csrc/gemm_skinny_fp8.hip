@@ -6,25 +6,26 @@
 //     partial[s][m][n] = sum over 128-k blocks b of split s of scale[n / 128][b] * ( sum_{k in b} x[m][k] * float(q[n][k]) )
 //     out[m][n]        = T( sum_s partial[s][m][n] )                                      (launch_slab_reduce, fixed order)
 //
-// The plan is gemm_skinny_kernel's — grid = (N tiles, K splits of <= 1024 k), the x slice staged once in LDS (same image,
-// same row stride), every wave streaming whole 16-row groups with full-line non-temporal loads through its private
-// XOR-swizzled 2 KiB transpose image, fp32 slabs for the slab reduce — with what moe_gemm_fp8w_kernel (moe_experts_fp8.hip)
-// changed:
+// The plan is gemm_skinny_kernel's — grid = (N tiles, K splits of <= 1024 k), the x slice staged once in LDS, every wave
+// streaming whole 16-row groups with full-line non-temporal loads through its private XOR-swizzled 2 KiB transpose image,
+// fp32 slabs for the slab reduce.  Shared with it as text: the x staging (gemm_skinny_x_load.inc / _store.inc: same
+// image, same row stride) and the image's geometry (wstream_image.inc); shared with moe_gemm_fp8w_kernel
+// (moe_experts_fp8.hip): the way of one scale block through the image (wstream_block_fp8.inc) and the widening
+// (fp8_widen.h).  What is this kernel's own:
 //   * a load instruction is 8 rows x 128 BYTES = 8 rows x one whole 128-k scale block; two of them fill the image with
-//     16 rows x 128 k, so an image holds exactly one scale block;
-//   * the A fragment of MFMA step st is a ds_read_b64 of the image widened to T by v_cvt_scalef32_pk_{bf16,f16}_fp8 with
-//     scale 1 (exact for every finite e4m3 value, NaN bytes stay NaN);
-//   * the four MFMA steps of a block accumulate into a temporary that starts at zero; the block's scale folds it into the
-//     running sum with one fma.  A weight is never rounded after it has been scaled;
+//     16 rows x 128 k, so an image holds exactly one scale block (the block text widens a ds_read_b64 of it per MFMA step,
+//     runs the block's four steps into a temporary that starts at zero and folds it into the running sum with one fma by
+//     the block's scale: a weight is never rounded after it has been scaled);
+//   * a register buffer is still 16 KiB and two are in flight; at one byte per weight a buffer is a whole (row group,
+//     split): R row groups per wave are R buffers, and nothing is summed across buffers;
 //   * a wave's 16 rows lie inside one 128-row scale block, so the scales of a (row group, split) are at most 8
 //     wave-uniform floats: scalar loads, issued a whole buffer of work ahead of their use (the first buffer's with its
 //     weight loads, the second's behind the x staging, so that they are not held in SGPRs across it).
-// A register buffer is still 16 KiB and two are in flight; at one byte per weight a buffer is a whole (row group, split):
-// R row groups per wave are R buffers, and nothing is summed across buffers.
-// Second translation unit beside gemm_skinny.hip, whose text and device code it does not touch; it shares the split rule
-// (gemm_skinny_splits), the workspace size and the slab reduce with it through their host entry points.
+// A translation unit of its own beside gemm_skinny.hip; it shares the split rule (gemm_skinny_splits), the workspace size
+// and the slab reduce with it through their host entry points.
 #include <cstring>
 #include "attn_common.h"
+#include "fp8_widen.h"
 
 namespace hx {
 int gemm_skinny_splits(int64_t K);
@@ -54,25 +55,6 @@ constexpr int kNB = kSplitK / kBlk;       // scale blocks per buffer
 constexpr int kNJ = 2 * kNB;              // load instructions per buffer (8 rows x 128 k each)
 constexpr int kRS = kSplitK * 2 + 32;     // LDS row stride of the x image in bytes (gemm_skinny.hip's kRS)
 
-// 8 e4m3 bytes -> 8 T, in byte order (moe_experts_fp8.hip)
-template <typename T> struct Fp8Widen;
-template <> struct Fp8Widen<BF16> {
-  template <bool HI> static __device__ __forceinline__ uint32_t pk(uint32_t w) {
-    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, HI));
-  }
-};
-template <> struct Fp8Widen<F16> {
-  template <bool HI> static __device__ __forceinline__ uint32_t pk(uint32_t w) {
-    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, HI));
-  }
-};
-template <typename T>
-__device__ __forceinline__ u16x8 widen(u32x2 q) {
-  const u32x4 o = {Fp8Widen<T>::template pk<false>(q[0]), Fp8Widen<T>::template pk<true>(q[0]),
-                   Fp8Widen<T>::template pk<false>(q[1]), Fp8Widen<T>::template pk<true>(q[1])};
-  return __builtin_bit_cast(u16x8, o);
-}
-
 // R = 16-row groups per wave (one register buffer each); NW = waves per workgroup.  Compile-time constants: the
 // load / compute schedule is straight-line code (gemm_skinny_kernel).
 template <typename T, int MB, int R, int NW>
@@ -92,20 +74,10 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_fp8w_kernel(const Fp8Gemm
   // wave's row groups: rg0 + j * NW, j < R (groups past the end are clamped for loads and skipped at the store)
   const int rg0 = blockIdx.x * (NW * R) + w;
 
-  // ---- 1. x slice -> registers (gemm_skinny_kernel: the image spans 1024 k; k past the split and rows past M are zero)
-  constexpr int kCpr = kSplitK / 8;                        // 16-byte chunks per LDS row
-  constexpr int XPT = MB * 16 * kCpr / kThreads;           // chunks per thread
-  u16x8 xr[XPT];
-  {
-    const u16* xb = reinterpret_cast<const u16*>(p.x) + k0;
-#pragma unroll
-    for (int j = 0; j < XPT; ++j) {
-      const int i = threadIdx.x + j * kThreads;
-      const int row = i / kCpr, ch = i % kCpr;
-      const bool ok = row < p.M && ch * 8 < KR;
-      xr[j] = *reinterpret_cast<const u16x8*>(xb + (int64_t)(ok ? row : 0) * p.ldx + (ok ? ch * 8 : 0));
-    }
-  }
+  // ---- 1. x slice -> registers
+  const u16* xb = reinterpret_cast<const u16*>(p.x) + k0;
+  constexpr bool kNoXLoads = false;
+#include "gemm_skinny_x_load.inc"
 
   // ---- 2. W prefetch.  Instruction j of a buffer covers rows 8 * (j & 1) + (lane >> 3) and the 128-byte scale block
   // j >> 1; lane & 7 selects the 16-byte piece.  Blocks past the split re-read its last one (their MFMAs are skipped), row
@@ -137,55 +109,29 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_fp8w_kernel(const Fp8Gemm
   __builtin_amdgcn_sched_barrier(0);
 
   // ---- 3. x slice -> LDS
-#pragma unroll
-  for (int j = 0; j < XPT; ++j) {
-    const int i = threadIdx.x + j * kThreads;
-    const int row = i / kCpr, ch = i % kCpr;
-    const bool ok = row < p.M && ch * 8 < KR;
-    *reinterpret_cast<u16x8*>(smem + row * kRS + ch * 16) = ok ? xr[j] : u16x8{0, 0, 0, 0, 0, 0, 0, 0};
-  }
+#include "gemm_skinny_x_store.inc"
   __syncthreads();
   // the second buffer's scales: a whole buffer of work ahead of their use, and not held in SGPRs across the staging
   if constexpr (R > 1) load_scales(sc[1], 1);
 
-  // wave-private transpose image: [16 rows][128 e4m3 bytes], 16-byte slot s of row r stored at slot s ^ ((r >> 1) & 7)
-  char* tl = smem + MB * 16 * kRS + w * 2048;
-  const int wr_off0 = lrow * 128 + 16 * (lpiece ^ ((lrow >> 1) & 7));
-  const int wr_off1 = (lrow + 8) * 128 + 16 * (lpiece ^ (((lrow + 8) >> 1) & 7));
-  // 8-byte unit 4 st + g of row r: 16-byte piece 2 st + (g >> 1), swizzled like the writes, half g & 1
-  const char* al = tl + r * 128 + 8 * (g & 1);
-  const int a_sw = (r >> 1) & 7, a_p = g >> 1;
-  const char* xl = smem + c * kRS + g * 16;
+  // the wave-private transpose images lie behind the x slice; an image holds 16 rows x 128 e4m3 bytes = one scale block
+  char* images = smem + MB * 16 * kRS;
+#include "wstream_image.inc"
+  constexpr int nmb = MB;                        // every 16-row block of the x image takes part
+  const char* xp = smem + c * kRS + g * 16;      // one buffer = the whole split: every buffer reads x from its first k
 
 #pragma unroll
   for (int it = 0; it < R; ++it) {
     f32x4 acc[MB];
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) acc[mb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const u32x4 (&wbuf)[kNJ] = buf[it & 1];
+    const float (&wscale)[kNB] = sc[it & 1];
+    f32x4 (&accb)[MB] = acc;
 #pragma unroll
     for (int cb = 0; cb < kNB; ++cb) {
       if (cb < nblk) {
-        *reinterpret_cast<u32x4*>(tl + wr_off0) = buf[it & 1][2 * cb];
-        *reinterpret_cast<u32x4*>(tl + wr_off1) = buf[it & 1][2 * cb + 1];
-        __builtin_amdgcn_wave_barrier();
-        f32x4 tmp[MB];
-#pragma unroll
-        for (int mb = 0; mb < MB; ++mb) tmp[mb] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int st = 0; st < 4; ++st) {
-          const u16x8 af = widen<T>(*reinterpret_cast<const u32x2*>(al + 16 * ((2 * st + a_p) ^ a_sw)));
-#pragma unroll
-          for (int mb = 0; mb < MB; ++mb) {
-            const u16x8 xf = *reinterpret_cast<const u16x8*>(xl + mb * 16 * kRS + (4 * cb + st) * 64);
-            tmp[mb] = Mfma<T>::mma(af, xf, tmp[mb]);
-          }
-        }
-        const float sv = sc[it & 1][cb];
-#pragma unroll
-        for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) acc[mb][i] = __builtin_fmaf(tmp[mb][i], sv, acc[mb][i]);
-        __builtin_amdgcn_wave_barrier();
+#include "wstream_block_fp8.inc"
       }
     }
     if (it + 2 < R) { load(buf[it & 1], it + 2); load_scales(sc[it & 1], it + 2); }

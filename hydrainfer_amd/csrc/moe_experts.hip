@@ -22,17 +22,12 @@
 // LDS-integer-atomic order (order inside a group is free: a slot's result does not depend on its place).  Chosen over a
 // scan in the GEMM prologues because it serves every n (prefill too) with one code path and keeps ~1400 GEMM workgroups
 // from each repeating the same scan in front of their first weight load.
-#include <algorithm>
 #include <cfloat>
-#include "attn_common.h"
+#include "moe_gemm.h"
 
 namespace {
 
 using namespace hx;
-
-constexpr int kMaxE = 256;       // routed experts
-constexpr int kMaxTopk = 8;
-constexpr int kTile = 64;        // token rows per tile
 
 // ---------------------------------------------------------------------------------------------------------------------
 // a. router.  One 256-thread workgroup per token: x row -> LDS (fp32), wave w takes experts w, w + 4, ... (lanes stride
@@ -166,172 +161,27 @@ __global__ __launch_bounds__(256) void moe_segments_kernel(int32_t* __restrict__
 // MB = 16-row blocks of a tile = what min(n, 64) rows need — a function of n, not of the routing.  An expert holds at
 // most n rows when a token's ids are distinct (every router's output); a longer segment is walked in tiles all the same.
 // ---------------------------------------------------------------------------------------------------------------------
-template <int MB, int GU>
-struct MoeGemmCfg {
-  static constexpr int KL = (GU || MB == 4) ? 512 : 1024;   // k per LDS chunk
-  static constexpr int SK = GU ? KL : KL / 2;               // k per stream and chunk
-  static constexpr int NJ = SK / 32;                        // load instructions per stream and chunk (8 rows x 64 k each)
-  static constexpr int RS = KL * 2 + 32;                    // LDS row stride in bytes (B-fragment ds_read_b128: conflict free)
-  static constexpr int kRows = MB * 16;                     // token rows per tile
-  static constexpr size_t kLds = (size_t)kRows * RS + 4 * 2048 + 2 * kTile * 4;
-};
-
+// The body is moe_gemm_body.inc, shared with moe_gemm_fp8w_kernel (moe_experts_fp8.hip); this is its 16-bit form: a load
+// instruction is 8 rows x 64 k, a block goes through the image by wstream_block16.inc, there are no scales, and the x
+// staging fetches all 16 MB rows of a tile.
+#define HX_MOE_BLOCK_INC "wstream_block16.inc"
 template <typename T, int MB, int GU>
 __global__ __launch_bounds__(256, 2) void moe_gemm_kernel(u16* __restrict__ out, const u16* __restrict__ xin,
                                                        const u16* __restrict__ wgt, const int32_t* __restrict__ seg,
                                                        const int N, const int K, const int n_experts, const int n_slots,
                                                        const int topk) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  using C = MoeGemmCfg<MB, GU>;
-  constexpr int KL = C::KL, SK = C::SK, NJ = C::NJ, RS = C::RS, kRows = C::kRows;
-  constexpr int kCpr = KL / 8;                   // 16-byte pieces per LDS row
-  constexpr int XPT = kRows * kCpr / 256;        // pieces per thread and chunk
-  constexpr int XRND = XPT < 8 ? XPT : 8;        // ... fetched 8 at a time
-  const int e = blockIdx.y;
-  // ---- the expert's segment, before anything else: no rows, no weight bytes
-  int off = seg[e];
-  int rows_e = seg[e + 1] - off;
-  rows_e = min(max(rows_e, 0), n_slots);                 // (a foreign seg buffer cannot send the gather out of bounds)
-  off = min(max(off, 0), n_slots - rows_e);
-  if (rows_e == 0) return;
-  const int32_t* slots = seg + 2 * n_experts + 1 + off;
-
-  const int lane = threadIdx.x & 63;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int r = lane & 15, g = lane >> 4, c = lane & 15;
-  const int lrow = lane >> 3, lpiece = lane & 7;
-  int32_t* srow = reinterpret_cast<int32_t*>(smem + kRows * RS + 4 * 2048);   // [64] source row of x per tile row
-  int32_t* drow = srow + kTile;                                                 // [64] destination slot
-  char* tl = smem + kRows * RS + w * 2048;        // wave-private transpose image (gemm_skinny_kernel)
-  const int wr_off0 = lrow * 128 + 16 * (lpiece ^ ((lrow >> 1) & 7));
-  const int wr_off1 = (lrow + 8) * 128 + 16 * (lpiece ^ (((lrow + 8) >> 1) & 7));
-  const char* xl = smem + c * RS + g * 16;
-
-  const int n0 = (blockIdx.x * 4 + w) << 4;       // the wave's 16 output rows
-  const int64_t wrows = GU ? 2 * (int64_t)N : (int64_t)N;
-  const u16* wbase = wgt + ((int64_t)e * wrows + n0 + lrow) * K + 8 * lpiece;
-  const int n_it = (K + KL - 1) / KL;
-
-  // weight load of stream s at LDS chunk `it`: instruction j covers rows 8 * (j & 1) + (lane >> 3) and the 128-byte
-  // column block j >> 1; column blocks past K re-read a valid one (their MFMAs are skipped)
-  auto load = [&](u16x8 (&buf)[NJ], int it, int s) {
-    const int k0 = it * KL + (GU ? 0 : s * SK);
-    const int last_cb = max(min((K - k0) >> 6, NJ / 2), 1) - 1;
-    const int k0c = min(k0, K - 64);
-    const u16* wp = wbase + (GU ? (int64_t)s * N * K : 0) + k0c;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      const int cb = min(j >> 1, last_cb);
-      buf[j] = __builtin_nontemporal_load(reinterpret_cast<const u16x8*>(wp + (int64_t)(8 * (j & 1)) * K + 64 * cb));
-    }
-  };
-  // pieces [j0, j0 + XRND) of this thread's share of the gathered rows of chunk `it` (always a valid address; rows past
-  // the tile and k past K are zero-filled at the LDS write)
-  auto xload = [&](u16x8 (&xr)[XRND], int it, int j0) {
-#pragma unroll
-    for (int j = 0; j < XRND; ++j) {
-      const int i = threadIdx.x + (j0 + j) * 256;
-      const int row = i / kCpr, k = it * KL + (i % kCpr) * 8;
-      const int src = srow[row];
-      const bool ok = src >= 0 && k < K;
-      xr[j] = *reinterpret_cast<const u16x8*>(xin + (int64_t)(ok ? src : 0) * K + (ok ? k : 0));
-    }
-  };
-  auto xstore = [&](const u16x8 (&xr)[XRND], int it, int j0) {
-#pragma unroll
-    for (int j = 0; j < XRND; ++j) {
-      const int i = threadIdx.x + (j0 + j) * 256;
-      const int row = i / kCpr, ch = i % kCpr;
-      const bool ok = srow[row] >= 0 && it * KL + ch * 8 < K;
-      *reinterpret_cast<u16x8*>(smem + row * RS + ch * 16) = ok ? xr[j] : u16x8{0, 0, 0, 0, 0, 0, 0, 0};
-    }
-  };
-
-  for (int t0 = 0; t0 < rows_e; t0 += kRows) {
-    const int rows = min(kRows, rows_e - t0);
-    const int nmb = (rows + 15) >> 4;
-    __syncthreads();                               // the previous tile's readers of srow / drow
-    if (threadIdx.x < kTile) {
-      int s = -1;
-      if ((int)threadIdx.x < rows) s = min(max(slots[t0 + threadIdx.x], 0), n_slots - 1);
-      drow[threadIdx.x] = s;
-      srow[threadIdx.x] = s < 0 ? -1 : (GU ? s / topk : s);
-    }
-    __syncthreads();
-
-    f32x4 acc[GU ? 2 : 1][MB];
-#pragma unroll
-    for (int a = 0; a < (GU ? 2 : 1); ++a)
-#pragma unroll
-      for (int mb = 0; mb < MB; ++mb) acc[a][mb] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    for (int it = 0; it < n_it; ++it) {
-      u16x8 xr[XRND];
-      u16x8 buf[2][NJ];
-      xload(xr, it, 0);
-      load(buf[0], it, 0);
-      load(buf[1], it, 1);
-      // keep the weight loads in flight under the x staging (gemm_skinny_kernel: hipcc sinks them below the LDS writes)
-      __builtin_amdgcn_sched_barrier(0);
-      __syncthreads();                             // the previous chunk's B reads
-      xstore(xr, it, 0);
-#pragma unroll
-      for (int j0 = XRND; j0 < XPT; j0 += XRND) {
-        xload(xr, it, j0);
-        xstore(xr, it, j0);
-      }
-      __syncthreads();
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const int k0 = it * KL + (GU ? 0 : s * SK);
-        const int ncb = min(max((K - k0) >> 6, 0), NJ / 2);     // column blocks of this stream inside K
-        const char* xp = xl + (GU ? 0 : s * SK * 2);
-#pragma unroll
-        for (int cb = 0; cb < NJ / 2; ++cb) {
-          if (cb < ncb) {
-            *reinterpret_cast<u16x8*>(tl + wr_off0) = buf[s][2 * cb];
-            *reinterpret_cast<u16x8*>(tl + wr_off1) = buf[s][2 * cb + 1];
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int st = 0; st < 2; ++st) {
-              const u16x8 af = *reinterpret_cast<const u16x8*>(tl + r * 128 + 16 * ((4 * st + g) ^ ((r >> 1) & 7)));
-#pragma unroll
-              for (int mb = 0; mb < MB; ++mb) {
-                if (mb < nmb) {
-                  const u16x8 xf = *reinterpret_cast<const u16x8*>(xp + mb * 16 * RS + (2 * cb + st) * 64);
-                  acc[GU ? s : 0][mb] = Mfma<T>::mma(af, xf, acc[GU ? s : 0][mb]);
-                }
-              }
-            }
-            __builtin_amdgcn_wave_barrier();
-          }
-        }
-      }
-    }
-
-    // ---- epilogue: acc[.][mb][i] = out^T[n0 + 4 g + i][tile row 16 mb + c]
-#pragma unroll
-    for (int mb = 0; mb < MB; ++mb) {
-      const int m = mb * 16 + c;
-      if (mb < nmb && m < rows) {
-        u16x4 o;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          if (GU) {
-            const float gt = round_to<T>(acc[0][mb][i]);
-            const float up = round_to<T>(acc[GU ? 1 : 0][mb][i]);
-            const float a = round_to<T>(gt / (1.0f + __expf(-gt)));
-            o[i] = T::from_float(a * up);
-          } else {
-            o[i] = T::from_float(acc[0][mb][i]);
-          }
-        }
-        *reinterpret_cast<u16x4*>(out + (int64_t)drow[m] * N + n0 + 4 * g) = o;
-      }
-    }
-  }
+  using WElem = u16;
+  using WVec = u16x8;
+  constexpr int kKplLog2 = 6;
+  constexpr bool kScaled = false, kSkipEmptyRows = false;
+  const float* wsc = nullptr;
+#include "moe_gemm_body.inc"
 }
+#undef HX_MOE_BLOCK_INC
 
+struct Moe16 {
+  template <typename T, int MB, int GU> static constexpr auto kernel() { return moe_gemm_kernel<T, MB, GU>; }
+};
 
 // ---------------------------------------------------------------------------------------------------------------------
 // e. combine.  out[t, c] = T( float(T( sum_k w[t, k] * float(y[t topk + k, c]) )) + float(shared[t, c]) ): every product
@@ -370,31 +220,6 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(u16* __restrict__ out,
     for (int j = 0; j < 8; ++j) o[j] = T::from_float(acc[j]);
   }
   *reinterpret_cast<u16x8*>(out + t * hidden + c0) = o;
-}
-
-int check_shape(int64_t n, int64_t topk, int64_t n_experts, int64_t hidden, int64_t inter) {
-  if (n <= 0 || topk <= 0 || n_experts <= 0 || hidden <= 0 || inter <= 0) return HX_ERR_SHAPE;
-  if (n_experts > kMaxE || topk > kMaxTopk || hidden % 128 || inter % 128) return HX_ERR_SHAPE;
-  if (n * topk > (int64_t)1 << 24 || n_experts * 2 * inter * hidden >= (int64_t)1 << 40) return HX_ERR_SHAPE;
-  return HX_OK;
-}
-
-template <typename T, int GU>
-int launch_moe_gemm(void* out, const void* xin, const void* wgt, const int32_t* seg, int64_t N, int64_t K,
-                    int64_t n_experts, int64_t n_slots, int64_t topk, hipStream_t stream) {
-  const dim3 grid((unsigned)(N / 64), (unsigned)n_experts);
-  u16* o = (u16*)out;
-  const u16* x = (const u16*)xin;
-  const u16* w = (const u16*)wgt;
-  const int mb = (int)((std::min<int64_t>(n_slots / topk, kTile) + 15) / 16);   // n tokens
-  if (mb == 1)
-    return launch_lds(moe_gemm_kernel<T, 1, GU>, grid, 256, MoeGemmCfg<1, GU>::kLds, stream, o, x, w, seg, (int)N, (int)K,
-                      (int)n_experts, (int)n_slots, (int)topk);
-  if (mb == 2)
-    return launch_lds(moe_gemm_kernel<T, 2, GU>, grid, 256, MoeGemmCfg<2, GU>::kLds, stream, o, x, w, seg, (int)N, (int)K,
-                      (int)n_experts, (int)n_slots, (int)topk);
-  return launch_lds(moe_gemm_kernel<T, 4, GU>, grid, 256, MoeGemmCfg<4, GU>::kLds, stream, o, x, w, seg, (int)N, (int)K,
-                    (int)n_experts, (int)n_slots, (int)topk);
 }
 
 template <typename TX>
@@ -449,24 +274,20 @@ extern "C" int hx_moe_segments(int32_t* seg, const int32_t* topk_ids, int64_t n_
 extern "C" int hx_moe_gate_up_silu(void* act, const void* x, const void* w_gate_up, const int32_t* seg, int64_t n_tokens,
                                    int64_t topk, int64_t n_experts, int64_t hidden, int64_t inter, int dtype,
                                    hx_stream stream) {
-  if (!act || !x || !w_gate_up || !seg) return HX_ERR_NULL;
-  if (int rc = check_shape(n_tokens, topk, n_experts, hidden, inter)) return rc;
-  if (!aligned16(act) || !aligned16(x) || !aligned16(w_gate_up)) return HX_ERR_STRIDE;
+  if (int rc = moe_check_args(act, x, w_gate_up, nullptr, false, seg, n_tokens, topk, n_experts, hidden, inter, dtype)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == HX_F16) return launch_moe_gemm<F16, 1>(act, x, w_gate_up, seg, inter, hidden, n_experts, n_tokens * topk, topk, s);
-  if (dtype == HX_BF16) return launch_moe_gemm<BF16, 1>(act, x, w_gate_up, seg, inter, hidden, n_experts, n_tokens * topk, topk, s);
-  return HX_ERR_DTYPE;
+  const u16* w = (const u16*)w_gate_up;
+  if (dtype == HX_F16) return launch_moe_gemm<Moe16, F16, 1>(act, x, seg, inter, hidden, n_experts, n_tokens * topk, topk, s, w);
+  return launch_moe_gemm<Moe16, BF16, 1>(act, x, seg, inter, hidden, n_experts, n_tokens * topk, topk, s, w);
 }
 
 extern "C" int hx_moe_down(void* y, const void* act, const void* w_down, const int32_t* seg, int64_t n_tokens, int64_t topk,
                            int64_t n_experts, int64_t hidden, int64_t inter, int dtype, hx_stream stream) {
-  if (!y || !act || !w_down || !seg) return HX_ERR_NULL;
-  if (int rc = check_shape(n_tokens, topk, n_experts, hidden, inter)) return rc;
-  if (!aligned16(y) || !aligned16(act) || !aligned16(w_down)) return HX_ERR_STRIDE;
+  if (int rc = moe_check_args(y, act, w_down, nullptr, false, seg, n_tokens, topk, n_experts, hidden, inter, dtype)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == HX_F16) return launch_moe_gemm<F16, 0>(y, act, w_down, seg, hidden, inter, n_experts, n_tokens * topk, topk, s);
-  if (dtype == HX_BF16) return launch_moe_gemm<BF16, 0>(y, act, w_down, seg, hidden, inter, n_experts, n_tokens * topk, topk, s);
-  return HX_ERR_DTYPE;
+  const u16* w = (const u16*)w_down;
+  if (dtype == HX_F16) return launch_moe_gemm<Moe16, F16, 0>(y, act, seg, hidden, inter, n_experts, n_tokens * topk, topk, s, w);
+  return launch_moe_gemm<Moe16, BF16, 0>(y, act, seg, hidden, inter, n_experts, n_tokens * topk, topk, s, w);
 }
 
 extern "C" int hx_moe_combine(void* out, const void* y, const float* topk_weights, const void* shared, int64_t n_tokens,

@@ -200,3 +200,34 @@ def test_token_choice_entries_refuse_bad_arguments_with_the_same_status():
         assert len(cases) >= 14
         for what, args, status in cases:
             assert getattr(lib, name)(*args) == status, (name, what)
+
+
+# The four grouped expert GEMM entries share one argument check (csrc/moe_gemm.h).  Each keeps the order in which it has
+# always reported: the 16-bit entries a misaligned pointer (HX_ERR_STRIDE -3) before a dtype they do not do
+# (HX_ERR_DTYPE -1), the FP8 entries the dtype first.  Every call below is refused on the host, before any launch.
+#                 out  in   weight [scale] seg n topk E  h    I   dtype stream
+_MOE_16 = [_P, _P, _P, _P, 4, 2, 8, 256, 128, 2, None]
+_MOE_FP8 = [_P, _P, _P, _P, _P, 4, 2, 8, 256, 128, 2, None]
+_MOE_ENTRIES = {"hx_moe_gate_up_silu": (_MOE_16, -3), "hx_moe_down": (_MOE_16, -3),
+                "hx_moe_gate_up_silu_fp8w": (_MOE_FP8, -1), "hx_moe_down_fp8w": (_MOE_FP8, -1)}
+
+
+def test_moe_gemm_entries_keep_their_order_of_refusals():
+    lib = _lib.lib()
+    for name, (ok, both) in _MOE_ENTRIES.items():
+        fn, dtype = getattr(lib, name), len(ok) - 2
+
+        def call(*changes):
+            args = list(ok)
+            for pos, v in changes:
+                args[pos] = v
+            return fn(*args)
+        f32 = (dtype, 0)
+        for pos in (0, 1, 2):
+            assert call((pos, _P + 8)) == -3, (name, pos)                  # misaligned alone
+            assert call((pos, _P + 8), f32) == both, (name, pos)           # ... and a dtype the entry does not do
+        assert call(f32) == -1, name
+        if len(ok) == len(_MOE_FP8):
+            assert call((3, _P + 2)) == -3 and call((3, _P + 2), f32) == -1 and call((3, None)) == -4, name
+        # NULL and shape come first in both families
+        assert call((0, None), f32, (1, _P + 8)) == -4 and call((dtype - 2, 192), f32, (1, _P + 8)) == -2, name
