@@ -117,6 +117,8 @@ _SIGNATURES = {
     "hx_penalized_argmax_rows": (c_int, [c_void_p] * 3 + [c_int64] * 3 + [c_void_p] * 3 + [c_int64, c_void_p, c_int, c_void_p]),
     "hx_sample_rows": (c_int, [c_void_p] * 4 + [c_int64] * 3 + [c_void_p] * 3 + [c_int64, c_void_p, c_void_p, c_int, c_void_p]),
     "hx_sample_rows_resident": (c_int, [c_void_p] * 4 + [c_int64] * 3 + [c_void_p, c_void_p, c_int, c_void_p]),
+    "hx_sample_rows_resident_penalized": (c_int, [c_void_p] * 4 + [c_int64] * 3 + [c_void_p] * 4 + [c_int64, c_int64, c_int,
+                                                                                                   c_void_p]),
     "hx_sample_rows_constrained": (c_int, [c_void_p] * 4 + [c_int64] * 3 + [c_void_p] * 3 + [c_int64, c_void_p] + [c_void_p] * 3
                                    + [c_int64, c_void_p, c_int, c_void_p]),
     "hx_sample_rows_logprobs": (c_int, [c_void_p] * 4 + [c_int64] * 3 + [c_void_p] * 3 + [c_int64, c_void_p] + [c_void_p] * 3

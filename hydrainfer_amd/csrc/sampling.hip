@@ -33,6 +33,11 @@
 // hx_sample_rows_masked (allowed_token_ids, guided_choice) is the scored body with a step 1a: a row that names one of
 // the launch's token bitmasks (32 tokens per word, 1 = allowed) gets -inf at every token whose bit is clear, in the staged
 // row and ahead of everything else, from one read of the mask's 4 KB — no LDS beyond the row's own.
+//
+// hx_sample_rows_resident_penalized is the resident body with a step 2L: a row's history is a prefix of its slot of a
+// RESIDENT token log (tokens with repeats, appended by this kernel itself), counted per distinct token in the row's own
+// LDS words (integer atomics) and penalised by hx::penalized_value in one rounding — what a captured decode step needs
+// to penalise without the host ("Penalties from the captured step").
 #include <math.h>
 
 #include "hx_common.h"
@@ -93,6 +98,15 @@ __device__ __forceinline__ float smp_block_sum(float s, float* part) {
   constexpr bool MASKED = false;                                                                       \
   const uint32_t* const allow_words = nullptr; const int32_t n_masks = 0; const int32_t* const mask_row = nullptr;
 
+// and for its token log, in the kernels that keep none (LOGGED false: no statement that reads them is compiled)
+#define SMP_NO_LOG                                                                                     \
+  constexpr bool LOGGED = false;                                                                       \
+  const int32_t* const penalty_params = nullptr; int32_t* const token_log = nullptr;                   \
+  const int32_t log_slots = 0, log_cap = 0;
+// log entries a thread holds in step 2L: 1024 threads x 4 = HX_SAMPLE_LOG_MAX
+#define SMP_LOG_PER_THREAD 4
+static_assert(HX_SAMPLE_LOG_MAX == SMP_THREADS * SMP_LOG_PER_THREAD, "the longest log prefix is what 1024 threads hold");
+
 // the Philox counter of a row, as the body names it: in the four kernels that take the offset itself, words [6] and [7]
 // of the row's record (`rec`, the body's own)
 #define SMP_OFFSET_LO rec[6]
@@ -107,6 +121,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_rows_kernel(
   constexpr bool CONSTRAINED = false;
   SMP_NO_SCORES
   SMP_NO_MASK
+  SMP_NO_LOG
   const int32_t* const bias_ids = nullptr; const float* const bias_values = nullptr; const int32_t* const cu_bias = nullptr;
   const int32_t bias_total = 0;
 #include "sampling_body.inc"
@@ -125,6 +140,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_rows_constrained_kernel(
   constexpr bool CONSTRAINED = true;
   SMP_NO_SCORES
   SMP_NO_MASK
+  SMP_NO_LOG
 #include "sampling_body.inc"
 }
 
@@ -143,6 +159,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_rows_logprobs_kernel(
   constexpr bool CONSTRAINED = true;
   constexpr bool SCORED = true;
   SMP_NO_MASK
+  SMP_NO_LOG
 #include "sampling_body.inc"
 }
 
@@ -163,6 +180,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_rows_masked_kernel(
   constexpr bool CONSTRAINED = true;
   constexpr bool SCORED = true;
   constexpr bool MASKED = true;
+  SMP_NO_LOG
 #include "sampling_body.inc"
 }
 
@@ -183,6 +201,27 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_rows_resident_kernel(
     int64_t* __restrict__ ids, float* __restrict__ cut_out, float* __restrict__ u_out, const u16* __restrict__ logits,
     int32_t n, int64_t ld, const uint32_t* __restrict__ sample_params, const int32_t* __restrict__ positions) {
   constexpr bool CONSTRAINED = false;
+  SMP_NO_SCORES
+  SMP_NO_MASK
+  SMP_NO_LOG
+  const int32_t* const bias_ids = nullptr; const float* const bias_values = nullptr; const int32_t* const cu_bias = nullptr;
+  const int32_t bias_total = 0;
+  const int32_t* const hist_ids = nullptr; const int32_t* const hist_counts = nullptr; const int32_t* const cu_hist = nullptr;
+  const float* const penalties = nullptr;
+  constexpr int32_t total = 0;
+#include "sampling_body.inc"
+}
+
+// hx_sample_rows_resident_penalized: the resident kernel with step 2L — a row that names a slot of the resident token log
+// is penalised over the slot's first L words (L the row's offset) and appends its id as word L.  LOGGED is false in the
+// five kernels above, which keep their device code byte for byte.
+template <typename T>
+__global__ __launch_bounds__(SMP_THREADS) void sample_rows_resident_penalized_kernel(
+    int64_t* __restrict__ ids, float* __restrict__ cut_out, float* __restrict__ u_out, const u16* __restrict__ logits,
+    int32_t n, int64_t ld, const uint32_t* __restrict__ sample_params, const int32_t* __restrict__ positions,
+    const int32_t* __restrict__ penalty_params, int32_t* token_log, int32_t log_slots, int32_t log_cap) {
+  constexpr bool CONSTRAINED = false;
+  constexpr bool LOGGED = true;
   SMP_NO_SCORES
   SMP_NO_MASK
   const int32_t* const bias_ids = nullptr; const float* const bias_values = nullptr; const int32_t* const cu_bias = nullptr;
@@ -296,6 +335,43 @@ extern "C" int hx_sample_rows_resident(int64_t* ids, float* cut_out, float* u_ou
   if (rc != HX_OK) return rc;
   if (!positions) return HX_ERR_NULL;
   return dtype == HX_F16 ? launch_sample_rows_resident<F16>(a, positions) : launch_sample_rows_resident<BF16>(a, positions);
+}
+
+// The penalised resident entry: the resident entry's checks, the log's, and the same rule for the dynamic-LDS limit (the
+// log takes no LDS: the launch asks for the row's alone).
+template <typename T>
+static int launch_sample_rows_resident_penalized(const SampleArgs& a, const int32_t* positions, const int32_t* penalty_params,
+                                                 int32_t* token_log, int64_t log_slots, int64_t log_cap) {
+  const size_t lds = (size_t)((a.n + 7) / 8 * 8) * sizeof(float);
+  if (lds > 48 * 1024) {
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    hipError_t e = hipStreamIsCapturing(a.stream, &capturing);
+    if (e != hipSuccess) return hip_rc(e);
+    if (capturing == hipStreamCaptureStatusNone) {
+      e = hipFuncSetAttribute((const void*)sample_rows_resident_penalized_kernel<T>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)(SAMPLE_MAX_N * sizeof(float)));
+      if (e != hipSuccess) return hip_rc(e);
+    }
+  }
+  launcher(sample_rows_resident_penalized_kernel<T>, (unsigned)a.rows, SMP_THREADS, lds, a.stream)(
+      a.ids, a.cut_out, a.u_out, (const u16*)a.logits, (int32_t)a.n, a.ld, (const uint32_t*)a.sample_params, positions,
+      penalty_params, token_log, (int32_t)(log_slots > 0x7fffffff ? 0x7fffffff : log_slots), (int32_t)log_cap);
+  return check_launch();
+}
+
+extern "C" int hx_sample_rows_resident_penalized(int64_t* ids, float* cut_out, float* u_out, const void* logits, int64_t rows,
+                                                 int64_t n, int64_t ld, const void* sample_params, const int32_t* positions,
+                                                 const void* penalty_params, int32_t* token_log, int64_t log_slots,
+                                                 int64_t log_cap, int dtype, hx_stream stream) {
+  const SampleArgs a{ids, cut_out, u_out, logits, rows, n, ld, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
+                     nullptr, 0, sample_params, nullptr, nullptr, nullptr, 0, nullptr, dtype, (hipStream_t)stream};
+  if (log_slots < 1 || log_cap < 1 || log_cap > HX_SAMPLE_LOG_MAX) return HX_ERR_SHAPE;
+  const int rc = sample_rows_check(SMP_PLAIN, a);
+  if (rc != HX_OK) return rc;
+  if (!positions || !penalty_params || !token_log) return HX_ERR_NULL;
+  return dtype == HX_F16
+             ? launch_sample_rows_resident_penalized<F16>(a, positions, (const int32_t*)penalty_params, token_log, log_slots, log_cap)
+             : launch_sample_rows_resident_penalized<BF16>(a, positions, (const int32_t*)penalty_params, token_log, log_slots, log_cap);
 }
 
 extern "C" int hx_sample_rows(int64_t* ids, float* cut_out, float* u_out, const void* logits, int64_t rows, int64_t n,

@@ -5,7 +5,10 @@
 // kernel defines: words [6] and [7] of the record, or (resident) those words as a base plus the row's position.  Expects the
 // kernels' arguments (bias_ids, bias_values, cu_bias, bias_total included: null and 0 in sample_rows_kernel, where no
 // statement that names them is compiled; logprobs, top_ids, top_logprobs, score_k, want likewise where SCORED is false;
-// allow_words, n_masks, mask_row likewise where MASKED is false), T, CONSTRAINED, SCORED and MASKED in scope.
+// allow_words, n_masks, mask_row likewise where MASKED is false), T, CONSTRAINED, SCORED and MASKED in scope.  A sixth
+// inclusion, sample_rows_resident_penalized_kernel, is the resident one with LOGGED true: step 2L builds the row's history
+// from a resident token log and the row's id is appended to it (penalty_params, token_log, log_slots, log_cap: null and 0
+// where LOGGED is false, and no statement that names them is compiled).
   extern __shared__ __attribute__((aligned(16))) float zs[];      // the row as fp32, n elements (rounded up to 8)
   __shared__ float part_f[2][SMP_WAVES];
   __shared__ int part_i[2][SMP_WAVES];
@@ -109,6 +112,54 @@
     }
   }
 
+  // 2L. LOGGED: the row's history is the first L' = clamp(L, 0, log_cap) words of its slot of the resident token log, L
+  // the row's offset (the request's generated-token count); the row's id goes to word L once it is known (log_at).  The
+  // log holds tokens WITH repeats and penalized_value wants each distinct token's count once, in one rounding: the
+  // row's own word zs[t] serves as the integer counter of token t.  Every log entry keeps its (t, x = zs[t]) in
+  // registers, zs[t] becomes 0, every entry adds 1 to it (integer LDS atomics: no order of arrival shows), every entry
+  // reads the count back, and every entry of t writes the SAME penalized_value(x, count) — no LDS beyond the row's,
+  // five barriers, L' / 1024 entries a thread.  An entry outside [0, n) takes no part.
+  int32_t* log_at = nullptr;
+  if (LOGGED) {
+    const int32_t ls = penalty_params[row * 4 + 3];
+    if (ls >= 0 && ls < log_slots) {                               // the same in every thread of the workgroup
+      const int64_t L = (int64_t)(((uint64_t)(SMP_OFFSET_HI) << 32) | (uint64_t)(SMP_OFFSET_LO));
+      int32_t* lrow = token_log + (int64_t)ls * log_cap;
+      const int32_t len = (int32_t)(L < 0 ? 0 : L > log_cap ? log_cap : L);
+      if (L >= 0 && L < log_cap) log_at = lrow + L;
+      if (len > 0) {
+        const float f = __int_as_float(penalty_params[row * 4]), pp = __int_as_float(penalty_params[row * 4 + 1]),
+                    r = __int_as_float(penalty_params[row * 4 + 2]);
+        int32_t lt[SMP_LOG_PER_THREAD];
+        float lx[SMP_LOG_PER_THREAD];
+#pragma unroll
+        for (int q = 0; q < SMP_LOG_PER_THREAD; ++q) {
+          const int j = tid + q * SMP_THREADS;
+          const int32_t t = j < len ? lrow[j] : -1;
+          lt[q] = t >= 0 && t < n ? t : -1;
+          lx[q] = lt[q] >= 0 ? zs[lt[q]] : 0.f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < SMP_LOG_PER_THREAD; ++q)
+          if (lt[q] >= 0) zs[lt[q]] = __int_as_float(0);
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < SMP_LOG_PER_THREAD; ++q)
+          if (lt[q] >= 0) atomicAdd(reinterpret_cast<int*>(zs + lt[q]), 1);
+        __syncthreads();
+        int32_t lc[SMP_LOG_PER_THREAD];
+#pragma unroll
+        for (int q = 0; q < SMP_LOG_PER_THREAD; ++q) lc[q] = lt[q] >= 0 ? __float_as_int(zs[lt[q]]) : 0;
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < SMP_LOG_PER_THREAD; ++q)
+          if (lt[q] >= 0) zs[lt[q]] = penalized_value(lx[q], lc[q], f, pp, r);
+        __syncthreads();
+      }
+    }
+  }
+
   // 3. this thread's elements into registers (NaN where it owns none: every comparison below is false for them), and
   // the greedy id
   const int chunk = ((n + SMP_THREADS - 1) / SMP_THREADS) | 1;
@@ -152,6 +203,7 @@
   if (!sampled || best != best || !(fabsf(m) < INFINITY)) {        // greedy, or degenerate: a NaN, all -inf, a +inf
     if (tid == 0) {
       ids[row] = bi;
+      if (LOGGED && log_at) *log_at = bi;
       if (cut_out) cut_out[row] = __builtin_nanf("");
       if (u_out) u_out[row] = u;
     }
@@ -311,6 +363,7 @@
       }
     }
     ids[row] = base + (pick < 0 ? last : pick);
+    if (LOGGED && log_at) *log_at = base + (pick < 0 ? last : pick);
     if (cut_out) cut_out[row] = cut;
     if (u_out) u_out[row] = u;
     if (SCORED && scored) logprobs[row] = ((pick < 0 ? zlast : zpick) - m) - logf(zsum);

@@ -174,15 +174,28 @@ class BatchFillExecutor:
         temperature > 0 stays eligible when every other condition holds, and the rows come with their records — None for
         a greedy request, else (temperature, top_p, top_k, seed, n_out - position): the decoder's launch adds the row's
         position, so the draw's offset is n_out, what the eager step computes (placeholders of tokens still on the
-        device count in output_token_ids).  -> (rows, records) or None."""
-        rows, records, max_blocks = [], [], 0
+        device count in output_token_ids).  -> (rows, records) or None.
+
+        A decoder that has the penalised variant as well (GraphedDecoder(penalized=True)): a request under penalties stays
+        eligible when its max_tokens fit a row of the token log — decided once for its whole life — and the result is
+        (rows, records, penalties) when some row is penalised: per row None or (frequency, presence, repetition,
+        output_token_ids), the row's record carrying n_out - position for a greedy one too.  A penalised row the log
+        does not continue for is seeded from output_token_ids by the decoder: while a token of it is still on the device
+        the step runs eagerly (which reads the pending launch back first)."""
+        rows, records, penalties, max_blocks = [], [], [], 0
         bs = self.kv_manager.block_size
         pending_launch = self.pending[0] if self.pending is not None else None
+        dec = self.graph_decoder
+        log_cap = dec.penalty_log_cap if getattr(dec, "penalized", False) else 0
         for rcb, inst in batch:
             sp = rcb.sampling_params
-            if (len(inst.token_ids) != 1 or not inst.sample or sp.logprobs or rcb.penalty_history is not None
+            penalised = rcb.penalty_history is not None
+            if (len(inst.token_ids) != 1 or not inst.sample or sp.logprobs or (penalised and not (log_cap and sp.max_tokens <= log_cap))
                     or inst.score_targets is not None or rcb.token_constraints is not None
                     or getattr(rcb, "token_mask", None) is not None):
+                return None
+            if penalised and not dec.log_table.continues(rcb.sid, len(rcb.output_token_ids)) \
+                    and any(isinstance(t, PendingToken) for t in rcb.output_token_ids):
                 return None
             token = inst.token_ids[0]
             if isinstance(token, PendingToken):
@@ -194,10 +207,15 @@ class BatchFillExecutor:
             position = inst.position_ids[0]
             rows.append((token, position, bt[c // bs] * bs + c % bs, c + 1, bt, rcb.sid))
             records.append((sp.temperature, sp.top_p, sp.top_k, sp.seed, len(rcb.output_token_ids) - position)
-                           if sp.temperature > 0 else None)
+                           if sp.temperature > 0 else
+                           (0.0, 1.0, 0, 0, len(rcb.output_token_ids) - position) if penalised else None)
+            penalties.append((sp.frequency_penalty, sp.presence_penalty, sp.repetition_penalty, rcb.output_token_ids)
+                             if penalised else None)
             if len(bt) > max_blocks:
                 max_blocks = len(bt)
-        return (rows, records) if self.graph_decoder.fits(len(rows), max_blocks) else None
+        if not self.graph_decoder.fits(len(rows), max_blocks):
+            return None
+        return (rows, records, penalties) if any(p is not None for p in penalties) else (rows, records)
 
     def _launch_decode(self, batch: BatchRequest, rows) -> None:
         """Enqueue the step, hand every request a placeholder for its new token, THEN read the
@@ -228,6 +246,8 @@ class BatchFillExecutor:
             if rcb.eos_hit:
                 continue                       # a step that ran past an end-of-sequence token
             rcb.output_token_ids[index] = token
+            if rcb.penalty_history is not None:
+                rcb.penalty_history.append(token)   # (penalties from the graph: the host's table stays the truth for eager steps)
             dst = inst.sample_dst
             if dst is not None and dst.token_ids and dst.token_ids[0] is placeholder:
                 dst.token_ids = [token]
@@ -344,6 +364,9 @@ class BatchFillExecutor:
             placeholder = PendingToken(co.launch, r)
             if not rcb.eos_hit:                 # (a request that ended at the cohort's first resolve keeps what it has)
                 out.extend(t[r] for t in co.tok_log)
+                if rcb.penalty_history is not None:
+                    for t in co.tok_log:
+                        rcb.penalty_history.append(t[r])
                 out.append(placeholder)
                 rcb.metric.token_times.extend(co.t_log)
             inst = co.first_inst[r]

@@ -28,7 +28,13 @@ Sampled decoding from the graph (`sampled=True`, opt-in): a second variant of th
 in hx_sample_rows_resident instead of the argmax.  Its records live in a RESIDENT table indexed by launch row; a
 record's offset word is `n_out - position`, which decode never changes, and the kernel adds the row's position — the
 array the step already reads — so neither a look-ahead launch nor a cohort step restages anything (DESIGN.md,
-"Sampled decoding from the captured step")."""
+"Sampled decoding from the captured step").
+
+Penalties from the graph (`penalized=True`, opt-in, needs `sampled`): a third variant, keyed (B, bucket, "penalized"), ends
+in hx_sample_rows_resident_penalized.  A penalised request's generated tokens live in a RESIDENT token log, a slot per
+request (PenaltyLogTable), which the kernel itself appends to — so the look-ahead launch finds the newest token where it
+needs it, and the host uploads tokens only to seed a request the log does not hold ("Penalties from the
+captured step")."""
 import os
 from typing import Dict, List, Optional, Tuple
 
@@ -41,7 +47,9 @@ from hydrainfer_amd._C.kernel.norm import StepHead
 from hydrainfer_amd.layer.causal_attention import RANKED_THR, AttentionParameters, decode_rank_descriptor
 from hydrainfer_amd.memory.kv_cache import KVCache
 from hydrainfer_amd.model.llama import LanguageModelParameters
-from hydrainfer_amd.sampling import (SAMPLE_MAX_N, SAMPLE_RECORD_WORDS, pack_resident_records, sample_rows_resident)
+from hydrainfer_amd.sampling import (PENALTY_RECORD_WORDS, SAMPLE_LOG_MAX, SAMPLE_MAX_N, SAMPLE_RECORD_WORDS,
+                                     pack_penalty_records, pack_resident_records, sample_rows_resident,
+                                     sample_rows_resident_penalized)
 
 
 class DecodeStager:
@@ -193,10 +201,96 @@ class DecodeStager:
                 e[3] = self.step_no
 
 
+class PenaltyLogTable:
+    """The host side of the resident token log of penalised requests — plain Python, no device
+    (tests/test_graph_penalties_cpu.py drives it on the CPU).  A slot of the log belongs to a REQUEST (keyed by the
+    scheduler's sid, as DecodeStager.slot_of), not to a launch row: per sid it keeps [slot, next_L, last step seen], next_L
+    the generated-token count the request's next launch must come with for the log to hold its tokens already — the
+    kernel appended the newest one itself.  Any other count (a first appearance, a return from eager steps, a slot that
+    was taken away) makes the request be SEEDED with its tokens [0, L) from the host.  Slots are reused least recently
+    seen first, never one seen by this launch or the one before it (which may still be in flight): with at least twice
+    as many slots as launch rows there is always another."""
+
+    def __init__(self, n_slots: int, cap: int):
+        self.n_slots, self.cap = n_slots, cap
+        self.slot_of: Dict[object, list] = {}
+        self.free = list(range(n_slots - 1, -1, -1))
+        self.step_no = 0
+        self.last: List = []              # the sids of the most recent launch's penalised rows
+        self.n_seeds = 0                  # seeds so far (tests, the benchmark)
+
+    def continues(self, sid, L: int) -> bool:
+        """The log holds tokens [0, L) of this request: a launch at L uploads nothing."""
+        e = self.slot_of.get(sid)
+        return e is not None and e[1] == L
+
+    def _alloc(self) -> int:
+        if self.free:
+            return self.free.pop()
+        idle = [sid for sid, e in self.slot_of.items() if e[2] < self.step_no - 1]
+        if not idle:
+            raise HydraHipError(f"no free slot in a token log of {self.n_slots}: every one is in use by this launch or the last")
+        return self.slot_of.pop(min(idle, key=lambda sid: self.slot_of[sid][2]))[0]
+
+    def step(self, rows) -> Tuple[List[int], List[Tuple[int, List[int]]]]:
+        """rows: per launch row None or (sid, L, tokens) — L the request's generated-token count, tokens a sequence that
+        holds its generated tokens (read only when the row must be seeded; may be None otherwise).  -> (the rows' slots,
+        -1 for None; the seeds to upload as (slot, tokens [0, L))).  Raises, before anything changes, for an L outside
+        [0, cap], for a seed that is not L token ids — a placeholder of a token still on the device among them — and
+        when the launch needs more slots than are free or idle."""
+        seeds = {}
+        for i, row in enumerate(rows):
+            if row is None:
+                continue
+            sid, L, tokens = row
+            if not 0 <= L <= self.cap:
+                raise HydraHipError(f"a penalised row at generated-token count {L} in a token log of {self.cap} per request")
+            if not self.continues(sid, L):
+                seed = list(tokens[:L]) if tokens is not None else None
+                if seed is None or len(seed) != L or not all(isinstance(t, (int, np.integer)) for t in seed):
+                    raise HydraHipError(f"a penalised row must be seeded with its {L} generated tokens, all of them on the "
+                                        "host (a placeholder of a token still on the device is none)")
+                seeds[i] = seed
+        mine = {row[0] for row in rows if row is not None}
+        idle = sum(1 for sid, e in self.slot_of.items() if sid not in mine and e[2] < self.step_no)
+        if len(mine - self.slot_of.keys()) > len(self.free) + idle:
+            raise HydraHipError(f"no slot left in a token log of {self.n_slots}: the others belong to this launch or the last")
+        self.step_no += 1
+        for row in rows:                  # seen now: no row of this launch loses its slot to another one's
+            if row is not None and row[0] in self.slot_of:
+                self.slot_of[row[0]][2] = self.step_no
+        slots, uploads, self.last = [], [], []
+        for i, row in enumerate(rows):
+            if row is None:
+                slots.append(-1)
+                continue
+            sid, L, _ = row
+            e = self.slot_of.get(sid)
+            if e is None:
+                slot = self._alloc()
+                e = self.slot_of[sid] = [slot, L, self.step_no]
+            if i in seeds:
+                self.n_seeds += 1
+                if L:
+                    uploads.append((e[0], seeds[i]))
+            e[1], e[2] = L + 1, self.step_no
+            slots.append(e[0])
+            self.last.append(sid)
+        return slots, uploads
+
+    def step_cohort(self) -> None:
+        """The same rows as the previous launch, one token further (GraphedDecoder.launch_cohort): nothing to upload."""
+        self.step_no += 1
+        for sid in self.last:
+            e = self.slot_of[sid]
+            e[1] += 1
+            e[2] = self.step_no
+
+
 class GraphedDecoder:
     def __init__(self, language_model, kv_cache_block_manager, max_batch: int = 64,
                  max_blocks_per_seq: int = 256, pad_to: int = 4, executor: str = None, sampled: bool = False,
-                 keep_draws: bool = False):
+                 keep_draws: bool = False, penalized: bool = False, penalty_log_cap: int = 1024):
         # how a captured step is replayed: "graph" = a hipGraph (default here), "plan" = a launch plan
         # (hydrainfer_amd/launch_plan.py: the step's launches issued in stream order by a native loop).  The plan costs
         # ~0.65 ms of HOST time per 7B step (170 launches x 3.8 us) where a graph launch costs ~0.1: irrelevant for a
@@ -257,6 +351,25 @@ class GraphedDecoder:
             self.resident: List[Optional[tuple]] = [None] * B
             self.record_staging = [greedy.clone().pin_memory() for _ in range(2)]
             self.record_stage = [t.numpy() for t in self.record_staging]
+        # penalties from the graph: a third variant of the step ends in hx_sample_rows_resident_penalized over a token log
+        # that stays on the device — a slot per REQUEST (PenaltyLogTable), twice as many as launch rows — and a table of
+        # the launch rows' penalties and slots beside `records`.  Without a sampled variant: off, as `sampled` is
+        self.penalized = bool(penalized) and self.sampled
+        self.last_variant = None                           # None (greedy), "sampled" or "penalized"
+        if self.penalized:
+            if not 1 <= penalty_log_cap <= SAMPLE_LOG_MAX:
+                raise HydraHipError(f"penalty_log_cap {penalty_log_cap} outside 1 .. {SAMPLE_LOG_MAX}")
+            self.penalty_log_cap = cap = int(penalty_log_cap)
+            self.log_table = PenaltyLogTable(2 * B, cap)
+            self.token_log = torch.zeros(2 * B, cap, dtype=torch.int32, device=self.dev)
+            none = torch.from_numpy(pack_penalty_records([None] * B))
+            self.penalty_records = none.to(self.dev)
+            self.resident_penalties: List[Optional[tuple]] = [None] * B
+            self.penalty_staging = [none.clone().pin_memory() for _ in range(2)]
+            self.penalty_stage = [t.numpy() for t in self.penalty_staging]
+            # the seeds of a fill, back to back (at worst every row of a launch, each with a full log row)
+            self.seed_staging = [torch.zeros(B * cap, dtype=torch.int32).pin_memory() for _ in range(2)]
+            self.seed_stage = [t.numpy() for t in self.seed_staging]
         if self.keep_draws:
             self.draws = torch.zeros(B, dtype=torch.float32, device=self.dev)
             self.host_draws = [torch.zeros(B, dtype=torch.float32).pin_memory() for _ in range(2)]
@@ -289,10 +402,11 @@ class GraphedDecoder:
                                     kv_max_seq_len=kv_max, decode_rank=rank) for kc in self.kv_caches]
         return LanguageModelParameters(attention_params=attn, all_sequences_decode=True)
 
-    def _body(self, B: int, params, sampled: bool = False):
+    def _body(self, B: int, params, sampled=False):
         """One decode step as library launches only (+ the lm_head GEMM): recordable in a launch plan.  sampled: the
         step ends in hx_sample_rows_resident over the resident records instead of the argmax, and its logits come back
-        as a third result."""
+        as a third result; sampled == "penalized": in hx_sample_rows_resident_penalized, over the resident penalty
+        records and the token log as well."""
         ids, pos = self._views(B)[:2]
         src = self._views(B)[6]
         lib = _lib.lib()
@@ -313,7 +427,11 @@ class GraphedDecoder:
         self.model.sample_out = out
         logits = None
         try:
-            if sampled:
+            if sampled == "penalized":
+                logits = self.model.forward_logits(fed, pos, params)
+                res = sample_rows_resident_penalized(logits, self.records[:B], pos, self.penalty_records[:B], self.token_log,
+                                                     out=out, u_out=self.draws[:B] if self.keep_draws else None)
+            elif sampled:
                 logits = self.model.forward_logits(fed, pos, params)
                 res = sample_rows_resident(logits, self.records[:B], pos, out=out,
                                            u_out=self.draws[:B] if self.keep_draws else None)
@@ -334,7 +452,7 @@ class GraphedDecoder:
         return (out, err, logits) if sampled else (out, err)
 
     def _capture(self, B: int, bucket: int, variant: str = None):
-        sampled = variant == "sampled"
+        sampled = variant if variant in ("sampled", "penalized") else False
         params = self._params(B, bucket if bucket else 4096)
         saved = self.prev_tokens.clone()
         side = torch.cuda.Stream(device=self.dev)
@@ -359,10 +477,25 @@ class GraphedDecoder:
                 out, err, *logits = self._body(B, params, sampled)
         return (graph, out, err, *logits)
 
-    def _fill(self, rows: List[tuple], B: int, records=None) -> int:
+    def _copy_words(self, copies) -> None:
+        """(dst address, src address, words) copies, two to a launch (hx_copy_words2)."""
+        for i in range(0, len(copies), 2):
+            a, b = copies[i], copies[i + 1] if i + 1 < len(copies) else (None, None, 0)
+            _lib.check(_lib.lib().hx_copy_words2(*a, *b, _lib.current_stream()), "copy_words2")
+
+    def _fill(self, rows: List[tuple], B: int, records=None, penalties=None) -> int:
         """Stage the step (DecodeStager.stage) and enqueue the kernel that applies it to the resident buffer.  records:
         None, or the sampled step's record per live row — rows of the resident table that hold something else are
-        rewritten, through the pinned buffer of this fill, by one more launch."""
+        rewritten, through the pinned buffer of this fill, by one more launch.  penalties: None, or per live row None or
+        (frequency, presence, repetition[, the request's generated tokens]) — the rows' log slots are looked up, the
+        penalty table is rewritten where it differs, and a row the log does not hold the tokens of is seeded, through
+        the pinned buffers of this fill as well."""
+        slots = seeds = None
+        if penalties is not None:
+            slots, seeds = self.log_table.step([
+                None if p is None else (row[5] if len(row) > 5 and row[5] is not None else ("row", i),
+                                        records[i][4] + row[1], p[3] if len(p) > 3 else None)
+                for i, (row, p) in enumerate(zip(rows, penalties))])
         which = self.fills % 2
         self.fills += 1
         self.copy_done[which].synchronize()      # no-op until the buffer has been used once
@@ -379,6 +512,20 @@ class GraphedDecoder:
                                                      SAMPLE_RECORD_WORDS * B, None, None, 0, _lib.current_stream()),
                            "copy_words2")
                 self.resident[:B] = want
+        if penalties is not None:
+            copies = []
+            want = [None if p is None else (p[0], p[1], p[2], s) for p, s in zip(penalties, slots)] + [None] * (B - len(rows))
+            if want != self.resident_penalties[:B]:
+                pack_penalty_records(want, self.penalty_stage[which][:B])
+                copies.append((self.penalty_records.data_ptr(), self.penalty_staging[which].data_ptr(), PENALTY_RECORD_WORDS * B))
+                self.resident_penalties[:B] = want
+            at, cap = 0, self.penalty_log_cap
+            for slot, tokens in seeds:
+                self.seed_stage[which][at:at + len(tokens)] = tokens
+                copies.append((self.token_log.data_ptr() + 4 * slot * cap, self.seed_staging[which].data_ptr() + 4 * at,
+                               len(tokens)))
+                at += len(tokens)
+            self._copy_words(copies)
         self.copy_done[which].record()
         return kv_max
 
@@ -387,9 +534,14 @@ class GraphedDecoder:
         for n in batch_sizes:
             B = (n + self.pad_to - 1) // self.pad_to * self.pad_to
             key = (B, self._kv_bucket(B, kv_max))
-            for key in (key, key + ("sampled",)) if self.sampled else (key,):
+            variants = ((), ("sampled",), ("penalized",)) if self.penalized else ((), ("sampled",)) if self.sampled else ((),)
+            for key in [key + v for v in variants]:
                 if key not in self.graphs:
                     self._fill(rows, B)
+                    if key[2:] == ("penalized",) and any(p is not None for p in self.resident_penalties):
+                        # a warm-up behind real launches: its padding rows must not write into a live request's log
+                        self.penalty_records.copy_(torch.from_numpy(pack_penalty_records([None] * self.max_batch)))
+                        self.resident_penalties = [None] * self.max_batch
                     self.graphs[key] = self._capture(*key)
         torch.cuda.synchronize(self.dev)
 
@@ -404,13 +556,19 @@ class GraphedDecoder:
                                               self.stager.head_words, _lib.current_stream()), "stage_decode")
         self.copy_done[which].record()
         # the variant of the launch the cohort was formed behind: the same rows in the same order, so their records
-        # are in the table already, and the positions staged above move every row's offset on by one
-        return self._replay(n, B, kv_max, self.last_sampled)
+        # are in the table already, and the positions staged above move every row's offset on by one.  Penalised rows:
+        # their slots are unchanged and the log holds their newest token already — nothing to upload
+        if self.last_variant == "penalized":
+            self.log_table.step_cohort()
+        return self._replay(n, B, kv_max, self.last_variant)
 
-    def launch(self, rows: List[tuple], records=None) -> int:
+    def launch(self, rows: List[tuple], records=None, penalties=None) -> int:
         """Enqueue one decode step; returns a launch id for `fetch`.  Does not wait for the GPU.  records (a decoder
         built with sampled=True): per row None — greedy — or (temperature, top_p, top_k, seed, n_out - position); None or
-        all None is the greedy step as it ever was."""
+        all None is the greedy step as it ever was.  penalties (a decoder built with penalized=True): per row None or
+        (frequency, presence, repetition[, tokens]) — such a row needs a record (a greedy one: (0.0, 1.0, 0, 0, n_out -
+        position)), and `tokens`, a sequence holding the request's generated tokens, whenever the log does not continue
+        (PenaltyLogTable); None or all None: the launch is the one it is without the argument."""
         n = len(rows)
         B = (n + self.pad_to - 1) // self.pad_to * self.pad_to
         if records is not None and all(r is None for r in records):
@@ -418,13 +576,22 @@ class GraphedDecoder:
         if records is not None and not self.sampled:
             raise HydraHipError("sampling records for a decoder without a sampled variant (sampled=False, a vocabulary "
                                 f"above {SAMPLE_MAX_N}, or logits that are not fp16 / bf16)")
-        self.last_sampled = records is not None
-        return self._replay(n, B, self._fill(rows, B, records), self.last_sampled)
+        if penalties is not None and all(p is None for p in penalties):
+            penalties = None
+        if penalties is not None:
+            if not self.penalized:
+                raise HydraHipError("penalties for a decoder without a penalised variant (penalized=False, or no sampled variant)")
+            if records is None or any(p is not None and r is None for p, r in zip(penalties, records)):
+                raise HydraHipError("a penalised row needs a record: (0.0, 1.0, 0, 0, n_out - position) for a greedy one")
+        variant = "penalized" if penalties is not None else "sampled" if records is not None else None
+        kv_max = self._fill(rows, B, records, penalties)
+        self.last_variant, self.last_sampled = variant, variant is not None
+        return self._replay(n, B, kv_max, variant)
 
-    def sample_logits(self, B: int, bucket: int):
-        """Tests: the logits tensor the sampled graph (B, bucket) writes — the graph's own buffer, valid until the next
-        replay."""
-        return self.graphs[(B, bucket, "sampled")][3]
+    def sample_logits(self, B: int, bucket: int, variant: str = "sampled"):
+        """Tests: the logits tensor the sampled (or "penalized") graph (B, bucket) writes — the graph's own buffer, valid
+        until the next replay."""
+        return self.graphs[(B, bucket, variant)][3]
 
     def fetch_draws(self, launch_id: int):
         """Tests (keep_draws=True): the per-row u of a sampled launch, fp32 (waits for it); None for a greedy launch.
@@ -436,8 +603,9 @@ class GraphedDecoder:
         self.events[launch_id % 2].synchronize()
         return self.host_draws[launch_id % 2][:n].numpy().copy()
 
-    def _replay(self, n: int, B: int, kv_max: int, sampled: bool = False) -> int:
-        key = (B, self._kv_bucket(B, kv_max)) + (("sampled",) if sampled else ())
+    def _replay(self, n: int, B: int, kv_max: int, sampled=False) -> int:
+        """sampled: False / None (the greedy step), True or "sampled", or "penalized"."""
+        key = (B, self._kv_bucket(B, kv_max)) + (("sampled" if sampled is True else sampled,) if sampled else ())
         if key not in self.graphs:
             self.graphs[key] = self._capture(*key)
         graph, out, err = self.graphs[key][:3]
@@ -484,5 +652,5 @@ class GraphedDecoder:
                                 "with the add+RMSNorm as separate launches (fuse_norm = False)")
         return self.host_tokens[slot][:n].tolist()
 
-    def run(self, rows: List[Tuple[int, int, int, int, List[int]]], records=None) -> List[int]:
-        return self.fetch(self.launch(rows, records))
+    def run(self, rows: List[Tuple[int, int, int, int, List[int]]], records=None, penalties=None) -> List[int]:
+        return self.fetch(self.launch(rows, records, penalties))

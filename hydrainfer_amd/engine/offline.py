@@ -74,7 +74,7 @@ class OfflineInferenceEngine:
     def __init__(self, language_model, vision_model, dtype: torch.dtype, device: str = "cuda:0",
                  max_running_requests: int = 32, token_budgets: int = 2048, image_budgets: int = 8,
                  max_context: int = 4096, kv_cache_gib: Optional[float] = None, warm_up: bool = True,
-                 graph_sampling: bool = False):
+                 graph_sampling: bool = False, graph_penalties: bool = False):
         self.device = torch.device(device)
         torch.cuda.set_device(self.device)
         shape = language_model.language_model.shape
@@ -86,7 +86,8 @@ class OfflineInferenceEngine:
                                      chunked_prefill=True, token_budgets=token_budgets, image_budgets=image_budgets)
         self.node = build_node("EPD0", "EPD", language_model, vision_model, shape, dtype, self.device, n_blocks,
                                2 * max_running_requests + 2, self.n_image_tokens, sched,
-                               max_blocks_per_seq=blocks_per_seq, graph_sampling=graph_sampling)
+                               max_blocks_per_seq=blocks_per_seq, graph_sampling=graph_sampling,
+                               graph_penalties=graph_penalties)
         self.cluster = LocalCluster([self.node])
         self.creator = InstructionCreator(image_token_id=language_model.image_token_id,
                                           n_image_tokens_per_image=self.n_image_tokens, block_size=16, ignore_eos=True,

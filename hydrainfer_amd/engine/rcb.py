@@ -21,7 +21,7 @@ class SamplingParameters:
     top_logprobs: int = 0       # 0..20 most likely alternatives in each of them; needs logprobs
     # steps 1-2 of the reference's process_logits (hydrainfer/sampling/logits_processor.py:65-72) over the request's
     # GENERATED tokens (hydrainfer_amd/sampling); (0, 0, 1) is the identity: such a request is sampled as before.  A
-    # penalised request decodes eagerly and can ask for logprobs only with logprobs_mode = "processed_logprobs".
+    # penalised request decodes eagerly (from the captured step under the graph_penalties switch) and can ask for logprobs only with logprobs_mode = "processed_logprobs".
     frequency_penalty: float = 0.0      # subtracted once per earlier occurrence of a token
     presence_penalty: float = 0.0       # subtracted once from every token that occurred
     repetition_penalty: float = 1.0     # > 0: a token that occurred has its logit divided (if negative: multiplied) by it

@@ -25,11 +25,15 @@ def build_node(name: str, node_type: str, language_model, vision_model, lm_shape
                device: torch.device, kv_blocks: int, image_blocks: int, n_image_tokens: int,
                sched: BatchSchedulerConfig, rank: int = 0, graph_decode: bool = True,
                max_blocks_per_seq: int = 256, world_size: int = 1, eager_migrate: bool = True,
-               release_prefill_weights: Optional[bool] = None, graph_sampling: bool = False) -> EPDNode:
+               release_prefill_weights: Optional[bool] = None, graph_sampling: bool = False,
+               graph_penalties: bool = False, penalty_log_cap: int = 1024) -> EPDNode:
     """release_prefill_weights (default: this node never prefills, i.e. a "D" node of parallel.epd_roles): keep only
     the packed decode layouts of the decoder weights — one copy in HBM instead of two.
     graph_sampling (opt-in): requests whose only departure from greedy is temperature / top_p / top_k / seed decode
-    from the captured step as well (GraphedDecoder(sampled=True)); off, every sampled request decodes eagerly."""
+    from the captured step as well (GraphedDecoder(sampled=True)); off, every sampled request decodes eagerly.
+    graph_penalties (opt-in, implies graph_sampling): requests under frequency / presence / repetition penalties whose
+    max_tokens are at most penalty_log_cap decode from the captured step too (GraphedDecoder(penalized=True)); off, a
+    penalised request decodes eagerly and takes its batch along."""
     nt = NodeType(node_type)
     if nt.has_language_model and nt.enable_decode:
         # every weight layout a decode batch of this node can need is built NOW: before the cache pools are
@@ -57,7 +61,8 @@ def build_node(name: str, node_type: str, language_model, vision_model, lm_shape
         if graph_decode and nt.enable_decode:
             from hydrainfer_amd.engine.graph_decode import GraphedDecoder
             decoder = GraphedDecoder(language_model, kv, max_batch=sched.max_running_requests,
-                                     max_blocks_per_seq=max_blocks_per_seq, sampled=graph_sampling)
+                                     max_blocks_per_seq=max_blocks_per_seq, sampled=graph_sampling or graph_penalties,
+                                     penalized=graph_penalties, penalty_log_cap=penalty_log_cap)
         fill = BatchFillExecutor(language_model, kv, img, dtype, device, graph_decoder=decoder)
     emb = BatchImageEmbedExecutor(vision_model, img, lm_shape.num_attention_heads, lm_shape.head_dim, dtype,
                                   device, use_graphs=graph_decode) if nt.has_vision_model else None

@@ -1,4 +1,5 @@
 """python -m hydrainfer_amd.entrypoint [--model 7b|13b|tiny] [--host H] [--port P] [--max-running N] [--tokenizer DIR] [--graph-sampling]
+[--graph-penalties]
 
 One collocated EPD replica on cuda:0 behind the OpenAI-compatible endpoint (hydrainfer/entrypoint/entrypoint.py serves
 the same routes through Ray + zmq).  No checkpoints offline: LLaVA-1.5-shaped RANDOM weights (what bench.py measures) and
@@ -22,6 +23,8 @@ def main():
                     "(serve.tune_library_gemms; opt-in: the pass runs every candidate kernel of the library — read its caution)")
     ap.add_argument("--graph-sampling", action="store_true", help="decode requests that differ from greedy only in temperature / "
                     "top_p / top_k / seed from the captured step and the cohort (default: they decode eagerly)")
+    ap.add_argument("--graph-penalties", action="store_true", help="decode requests under frequency / presence / repetition "
+                    "penalties from the captured step as well (implies --graph-sampling; default: they decode eagerly)")
     a = ap.parse_args()
     from hydrainfer_amd import _lib
     from hydrainfer_amd.engine.node import LocalCluster
@@ -50,7 +53,7 @@ def main():
     per_req = (a.max_tokens + 15) // 16 + 1
     node = build_node("EPD0", "EPD", lm, vision, shape, dt, dev, kv_blocks=a.max_running * per_req + 64,
                       image_blocks=2 * a.max_running, n_image_tokens=576, sched=sched, max_blocks_per_seq=per_req,
-                      graph_sampling=a.graph_sampling)
+                      graph_sampling=a.graph_sampling, graph_penalties=a.graph_penalties)
     warm_library_gemms(lm, sched.token_budgets, a.max_running)
     if a.tune_rows:
         print("library GEMMs tuned:", tune_library_gemms(lm, rows=tuple(int(r) for r in a.tune_rows.split(","))), flush=True)

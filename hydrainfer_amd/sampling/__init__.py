@@ -36,7 +36,9 @@ distinct masks to `pack_constrained_step`'s buffer.
 
 Sampled decoding from a captured decode step: `sample_rows_resident` (hx_sample_rows_resident) is `sample_rows` without a
 history whose records stay on the device — `pack_resident_records` writes `n_out - position` where the offset stood, the
-launch adds the row's position (engine/graph_decode.py)."""
+launch adds the row's position (engine/graph_decode.py).  `sample_rows_resident_penalized`
+(hx_sample_rows_resident_penalized) penalises such a row as well, over a token log that stays on the device and that the
+launch itself appends to; `pack_penalty_records` writes the rows' penalties and log slots."""
 import math
 from array import array
 from typing import Optional, Sequence, Tuple
@@ -53,6 +55,8 @@ SAMPLE_MAX_N = 35840            # the widest row hx_sample_rows takes (HX_SAMPLE
 SAMPLE_RECORD_WORDS = 8         # a row's record: [temperature, top_p (fp32 bits), top_k, 0, seed lo, hi, offset lo, hi]
 GREEDY_RECORD = (0.0, 1.0, 0, 0, 0)     # (temperature, top_p, top_k, seed, offset): the row is penalised argmax
 MAX_SEED = (1 << 63) - 1
+SAMPLE_LOG_MAX = 4096           # the longest row of a resident token log (HX_SAMPLE_LOG_MAX)
+PENALTY_RECORD_WORDS = 4        # a row's penalty record: [frequency, presence, repetition (fp32 bits), log slot]
 
 
 def penalized_argmax_rows(logits: Tensor, hist_ids: Tensor, hist_counts: Tensor, cu_hist: Tensor, penalties: Tensor,
@@ -306,6 +310,48 @@ def sample_rows_resident(logits: Tensor, sample_params: Tensor, positions: Tenso
         out.data_ptr(), cut_out.data_ptr() if cut_out is not None else None, u_out.data_ptr() if u_out is not None else None,
         logits.data_ptr(), rows, logits.shape[1], logits.stride(0), sample_params.data_ptr(), positions.data_ptr(),
         _lib.dtype_code(logits), _lib.current_stream()), "sample_rows_resident")
+    return out
+
+
+def pack_penalty_records(rows, out: Optional[np.ndarray] = None) -> np.ndarray:
+    """rows: per launch row None — no penalties, no log slot: (0, 0, 1.0, -1) — or (frequency, presence, repetition, slot)
+    -> int32 [rows, 4], the layout hx_sample_rows_resident_penalized reads (into `out` if given): the three penalties as
+    fp32 bits, then the row's slot of the resident token log (negative: none)."""
+    n = len(rows)
+    if out is None:
+        out = np.zeros((n, PENALTY_RECORD_WORDS), dtype=np.int32)
+    recs = [NO_PENALTIES + (-1,) if r is None else r for r in rows]
+    out[:, :3] = np.asarray([r[:3] for r in recs], dtype=np.float32).reshape(n, 3).view(np.int32)
+    out[:, 3] = [r[3] for r in recs]
+    return out
+
+
+def sample_rows_resident_penalized(logits: Tensor, sample_params: Tensor, positions: Tensor, penalty_params: Tensor,
+                                   token_log: Tensor, out: Optional[Tensor] = None, cut_out: Optional[Tensor] = None,
+                                   u_out: Optional[Tensor] = None) -> Tensor:
+    """`sample_rows_resident` under penalties over a resident token log (include/hydra_hip.h:
+    hx_sample_rows_resident_penalized): penalty_params int32 [rows, 4] from `pack_penalty_records`, token_log int32
+    [log_slots, log_cap] on the device (log_cap <= SAMPLE_LOG_MAX).  A row with a slot is penalised over the slot's first
+    L words, L = its record's offset_base + its position, and writes its id as word L; a row without one is
+    `sample_rows_resident`'s.  Nothing here allocates when `out` is given."""
+    _lib.require_gpu(logits, sample_params, positions, penalty_params, token_log, out, cut_out, u_out)
+    what = "sample_rows_resident_penalized"
+    rows, _, out = _check_sample_arguments(what, logits, sample_params, None, None, None, None, out, cut_out, u_out)
+    if positions.dtype != torch.int32 or tuple(positions.shape) != (rows,) or not positions.is_contiguous():
+        raise _lib.HydraHipError(f"{what}: positions must be a contiguous int32 tensor of shape [{rows}]")
+    if penalty_params.dtype != torch.int32 or tuple(penalty_params.shape) != (rows, PENALTY_RECORD_WORDS) \
+            or not penalty_params.is_contiguous():
+        raise _lib.HydraHipError(f"{what}: penalty_params must be a contiguous int32 tensor of shape "
+                                 f"[{rows}, {PENALTY_RECORD_WORDS}]")
+    if token_log.dtype != torch.int32 or token_log.dim() != 2 or not token_log.is_contiguous() or token_log.shape[0] < 1 \
+            or not 1 <= token_log.shape[1] <= SAMPLE_LOG_MAX:
+        raise _lib.HydraHipError(f"{what}: token_log must be a contiguous int32 tensor [log_slots >= 1, 1 <= log_cap <= "
+                                 f"{SAMPLE_LOG_MAX}]")
+    _lib.check(_lib.lib().hx_sample_rows_resident_penalized(
+        out.data_ptr(), cut_out.data_ptr() if cut_out is not None else None, u_out.data_ptr() if u_out is not None else None,
+        logits.data_ptr(), rows, logits.shape[1], logits.stride(0), sample_params.data_ptr(), positions.data_ptr(),
+        penalty_params.data_ptr(), token_log.data_ptr(), token_log.shape[0], token_log.shape[1], _lib.dtype_code(logits),
+        _lib.current_stream()), what)
     return out
 
 

@@ -363,6 +363,35 @@ int hx_sample_rows(int64_t* ids, float* cut_out, float* u_out, const void* logit
  * must have gone before on this device. */
 int hx_sample_rows_resident(int64_t* ids, float* cut_out, float* u_out, const void* logits, int64_t rows, int64_t n,
                             int64_t ld, const void* sample_params, const int32_t* positions, int dtype, hx_stream stream);
+/* hx_sample_rows_resident_penalized: hx_sample_rows_resident with frequency / presence / repetition penalties over a
+ * RESIDENT token log that the kernel both reads and appends to, so that a captured decode step penalises without the host
+ * (extension; added WITHOUT raising HX_ABI_VERSION: nothing that existed changed).  token_log: int32 [log_slots,
+ * log_cap], on the device.  penalty_params: int32 [rows, 4] = frequency, presence, repetition (fp32 bits) and the row's
+ * log slot s.  With rec the row's record, L = offset_base(rec) + (int64)positions[r] — the 64-bit sum that is the Philox
+ * offset, a request's generated-token count:
+ *   Row without a slot (s < 0 or s >= log_slots): ids, cut_out and u_out are hx_sample_rows_resident's bit for bit; the
+ *   log is neither read nor written.
+ *   Row with a slot: its history is the multiset token_log[s][0 .. L'), L' = min(max(L, 0), log_cap).  ids, cut_out and
+ *   u_out are bit for bit what hx_sample_rows gives for the same logits, the CSR of that multiset's (distinct ids,
+ *   counts), the same three penalties and a record that carries offset L — greedy rows (hx_penalized_argmax_rows' id) and
+ *   degenerate rows included.  A log entry outside [0, n) is ignored.  Then, if 0 <= L < log_cap, token_log[s][L] =
+ *   (int32)ids[r]; otherwise nothing is written.
+ * Nothing outside token_log[s][0 .. log_cap) is read or written.  The launch is IDEMPOTENT: it reads words [0, L) and
+ * writes word [L] alone, so a step that is replayed, or whose sample is later dropped, desynchronises nothing — the next
+ * step of the row overwrites word [L] or reads what a replay wrote again.  Two rows of one launch that name the same slot
+ * break the contract (one of them wins word [L]); nothing goes out of bounds.
+ * HX_SAMPLE_LOG_MAX: the log takes NO LDS beside the row (a 140 KiB row at n = HX_SAMPLE_MAX_N leaves under 19 KiB of the
+ * 160 KiB, too little for a (token, count) table of 2048 entries at a sane load): the count of token t is built in the
+ * row's own word t, whose value the log entries naming t hold in registers meanwhile.  The bound is those registers —
+ * 4 entries for each of the 1024 threads.
+ * Errors: hx_sample_rows_resident's rules; penalty_params or token_log NULL: HX_ERR_NULL; log_slots < 1, log_cap < 1 or
+ * log_cap > HX_SAMPLE_LOG_MAX: HX_ERR_SHAPE — nothing is launched.  The dynamic-LDS rule of hx_sample_rows_resident holds
+ * unchanged (for this kernel: one call outside a capture must have gone before). */
+#define HX_SAMPLE_LOG_MAX 4096
+int hx_sample_rows_resident_penalized(int64_t* ids, float* cut_out, float* u_out, const void* logits, int64_t rows, int64_t n,
+                                      int64_t ld, const void* sample_params, const int32_t* positions,
+                                      const void* penalty_params, int32_t* token_log, int64_t log_slots, int64_t log_cap,
+                                      int dtype, hx_stream stream);
 /* hx_sample_rows_constrained: hx_sample_rows with a per-row logit bias table and a min_p cut, still one launch and one
  * read of the logits (extension; added WITHOUT raising HX_ABI_VERSION: nothing that existed changed).  Everything
  * hx_sample_rows documents holds word for word, with two additions.
