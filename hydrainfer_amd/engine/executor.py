@@ -7,7 +7,7 @@ image cache.  Both run on the current stream; `InstructionExecutor` can put the 
 its own stream (executor.py:247-249)."""
 import os
 import time
-from typing import List, Optional
+from typing import List, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -96,6 +96,22 @@ class PendingToken:
         return f"<pending {self.launch}:{self.row}>"
 
 
+class DecodeStep(NamedTuple):
+    """What BatchFillExecutor._decode_rows hands GraphedDecoder.launch."""
+    rows: list
+    records: Optional[list]
+    penalties: Optional[list]
+
+
+def decoder_abilities(dec):
+    """-> (sampled, log_cap, has_cohort) of a graph decoder: it has a sampled variant; the token log's row when it has
+    the penalised one as well, else 0; it has launch_cohort.  Read with defaults — a stand-in for the decoder need
+    not carry the attributes — and at every use: tests replace the decoder of a built executor."""
+    sampled = bool(getattr(dec, "sampled", False))
+    return (sampled, dec.penalty_log_cap if sampled and getattr(dec, "penalized", False) else 0,
+            hasattr(dec, "launch_cohort"))
+
+
 class DecodeCohort:
     """The steady state of a decode batch — the SAME sequences step after step, each one token further — kept as arrays
     instead of being rediscovered from every request's instruction chain every step (the
@@ -141,59 +157,34 @@ class BatchFillExecutor:
         self.n_cohort_steps = 0
         self.ended_rows: Optional[List] = None   # the rows of a cohort that ended inside its own step (an end-of-sequence id came back)
 
-    def _decode_rows(self, batch: BatchRequest):
-        """(token, position, slot, kv_len, block_table) per request if the whole batch is decode.
-        A token still on the device is encoded as -(row + 1) of the pending launch."""
-        if getattr(self.graph_decoder, "sampled", False):
-            return self._decode_rows_sampled(batch)
-        rows, max_blocks = [], 0
-        bs = self.kv_manager.block_size
-        pending_launch = self.pending[0] if self.pending is not None else None
-        for rcb, inst in batch:
-            if (len(inst.token_ids) != 1 or not inst.sample or rcb.sampling_params.logprobs
-                    or rcb.penalty_history is not None or rcb.sampling_params.temperature > 0
-                    or inst.score_targets is not None or rcb.token_constraints is not None
-                    or getattr(rcb, "token_mask", None) is not None):
-                return None                    # (a request that wants log-probabilities, one under sampling penalties,
-                                               # a sampled, a constrained or a masked one decodes eagerly: execute(); so does a one-token piece
-                                               # of a prompt that is being scored — decode Fills carry no score list)
-            token = inst.token_ids[0]
-            if isinstance(token, PendingToken):
-                if token.launch != pending_launch:
-                    return None
-                token = -(token.row + 1)
-            bt = rcb.virtual_kv_cache.block_table
-            c = inst.cache_ids[0]
-            rows.append((token, inst.position_ids[0], bt[c // bs] * bs + c % bs, c + 1, bt, rcb.sid))      # (v2p inline)
-            if len(bt) > max_blocks:
-                max_blocks = len(bt)
-        return rows if self.graph_decoder.fits(len(rows), max_blocks) else None
-
-    def _decode_rows_sampled(self, batch: BatchRequest):
-        """_decode_rows for a decoder with a sampled variant (GraphedDecoder(sampled=True)): a request with
-        temperature > 0 stays eligible when every other condition holds, and the rows come with their records — None for
-        a greedy request, else (temperature, top_p, top_k, seed, n_out - position): the decoder's launch adds the row's
-        position, so the draw's offset is n_out, what the eager step computes (placeholders of tokens still on the
-        device count in output_token_ids).  -> (rows, records) or None.
-
-        A decoder that has the penalised variant as well (GraphedDecoder(penalized=True)): a request under penalties stays
-        eligible when its max_tokens fit a row of the token log — decided once for its whole life — and the result is
-        (rows, records, penalties) when some row is penalised: per row None or (frequency, presence, repetition,
-        output_token_ids), the row's record carrying n_out - position for a greedy one too.  A penalised row the log
-        does not continue for is seeded from output_token_ids by the decoder: while a token of it is still on the device
-        the step runs eagerly (which reads the pending launch back first)."""
+    def _decode_rows(self, batch: BatchRequest) -> Optional[DecodeStep]:
+        """The step the captured decoder runs for this batch, or None: the batch runs eagerly (execute()).
+        rows: (token, position, slot, kv_len, block_table, sid) per request; a token still on the device is encoded as
+        -(row + 1) of the pending launch.  records (a decoder with a sampled variant, else None): per row None — greedy —
+        or (temperature, top_p, top_k, seed, n_out - position): the decoder's launch adds the row's position, so the
+        draw's offset is n_out, what the eager step computes (placeholders of tokens still on the device count in
+        output_token_ids).  penalties (None unless some row is penalised): per row None or (frequency, presence,
+        repetition, output_token_ids), the row's record carrying n_out - position for a greedy one too."""
         rows, records, penalties, max_blocks = [], [], [], 0
         bs = self.kv_manager.block_size
         pending_launch = self.pending[0] if self.pending is not None else None
         dec = self.graph_decoder
-        log_cap = dec.penalty_log_cap if getattr(dec, "penalized", False) else 0
+        sampled, log_cap, _ = decoder_abilities(dec)
         for rcb, inst in batch:
             sp = rcb.sampling_params
             penalised = rcb.penalty_history is not None
-            if (len(inst.token_ids) != 1 or not inst.sample or sp.logprobs or (penalised and not (log_cap and sp.max_tokens <= log_cap))
-                    or inst.score_targets is not None or rcb.token_constraints is not None
-                    or getattr(rcb, "token_mask", None) is not None):
+            # Who decodes from the captured step: a request that samples from ONE new token; without log-probabilities,
+            # token constraints or a token mask (the eager sampling step's business), and not a one-token piece of a
+            # prompt that is being scored (decode Fills carry no score list); a drawn one only with the sampled variant;
+            # a penalised one only with the penalised variant and a max_tokens that fits a row of the token log —
+            # decided once for its whole life
+            if (len(inst.token_ids) != 1 or not inst.sample or sp.logprobs or inst.score_targets is not None
+                    or rcb.token_constraints is not None or getattr(rcb, "token_mask", None) is not None
+                    or (sp.temperature > 0 and not sampled)
+                    or (penalised and not (log_cap and sp.max_tokens <= log_cap))):
                 return None
+            # a penalised row the log does not continue for is seeded from output_token_ids by the decoder: while a token
+            # of it is still on the device the step runs eagerly (which reads the pending launch back first)
             if penalised and not dec.log_table.continues(rcb.sid, len(rcb.output_token_ids)) \
                     and any(isinstance(t, PendingToken) for t in rcb.output_token_ids):
                 return None
@@ -205,25 +196,25 @@ class BatchFillExecutor:
             bt = rcb.virtual_kv_cache.block_table
             c = inst.cache_ids[0]
             position = inst.position_ids[0]
-            rows.append((token, position, bt[c // bs] * bs + c % bs, c + 1, bt, rcb.sid))
-            records.append((sp.temperature, sp.top_p, sp.top_k, sp.seed, len(rcb.output_token_ids) - position)
-                           if sp.temperature > 0 else
-                           (0.0, 1.0, 0, 0, len(rcb.output_token_ids) - position) if penalised else None)
-            penalties.append((sp.frequency_penalty, sp.presence_penalty, sp.repetition_penalty, rcb.output_token_ids)
-                             if penalised else None)
+            rows.append((token, position, bt[c // bs] * bs + c % bs, c + 1, bt, rcb.sid))      # (v2p inline)
+            if sampled:
+                records.append((sp.temperature, sp.top_p, sp.top_k, sp.seed, len(rcb.output_token_ids) - position)
+                               if sp.temperature > 0 else
+                               (0.0, 1.0, 0, 0, len(rcb.output_token_ids) - position) if penalised else None)
+                penalties.append((sp.frequency_penalty, sp.presence_penalty, sp.repetition_penalty, rcb.output_token_ids)
+                                 if penalised else None)
             if len(bt) > max_blocks:
                 max_blocks = len(bt)
-        if not self.graph_decoder.fits(len(rows), max_blocks):
+        if not dec.fits(len(rows), max_blocks):
             return None
-        return (rows, records, penalties) if any(p is not None for p in penalties) else (rows, records)
+        return DecodeStep(rows, records if sampled else None, penalties if any(p is not None for p in penalties) else None)
 
-    def _launch_decode(self, batch: BatchRequest, rows) -> None:
+    def _launch_decode(self, batch: BatchRequest, step: DecodeStep) -> None:
         """Enqueue the step, hand every request a placeholder for its new token, THEN read the
         previous step's tokens: the GPU already has the next step queued while the host catches up."""
-        if isinstance(rows, tuple):            # (rows, records) of _decode_rows_sampled
-            launch = self.graph_decoder.launch(*rows)
-        else:
-            launch = self.graph_decoder.launch(rows)
+        # a decoder without a sampled variant is called as it ever was, with the rows alone: a stand-in for one need
+        # not take the other two arguments, as it need not carry the attributes (decoder_abilities)
+        launch = self.graph_decoder.launch(*(step if step.records is not None else step[:1]))
         entries = []
         for row, (rcb, inst) in enumerate(batch):
             placeholder = PendingToken(launch, row)
@@ -264,7 +255,7 @@ class BatchFillExecutor:
         """Called by EPDNode.step() in front of the scheduler.  Launches the next decode step of the cohort and returns
         its row count — or ends / declines the cohort and returns 0: the general path then runs the step."""
         dec = self.graph_decoder
-        if not self.cohort_enabled or dec is None or not hasattr(dec, "launch_cohort"):
+        if not self.cohort_enabled or dec is None or not decoder_abilities(dec)[2]:
             return 0
         co = self.cohort
         if co is None:
@@ -668,9 +659,9 @@ class BatchFillExecutor:
             return
         self._publish_prefix_blocks(batch)
         if self.graph_decoder is not None:
-            rows = self._decode_rows(batch)
-            if rows is not None:
-                self._launch_decode(batch, rows)
+            step = self._decode_rows(batch)
+            if step is not None:
+                self._launch_decode(batch, step)
                 return
             self.resolve_pending()             # the eager path needs every token on the host
         sh = self.shape

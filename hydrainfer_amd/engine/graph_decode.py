@@ -24,6 +24,8 @@ static buffer the graph itself updates at its end), so the host can build and en
 while launch N is still running and read N's tokens afterwards (`launch` / `fetch`).  The host work
 of a step (scheduler, tables, staging) no longer leaves the GPU idle.
 
+A captured step is keyed (B, bucket, variant), variant one of VARIANTS; the plain step is (B, bucket, "greedy").
+
 Sampled decoding from the graph (`sampled=True`, opt-in): a second variant of the step, keyed (B, bucket, "sampled"), ends
 in hx_sample_rows_resident instead of the argmax.  Its records live in a RESIDENT table indexed by launch row; a
 record's offset word is `n_out - position`, which decode never changes, and the kernel adds the row's position — the
@@ -36,7 +38,7 @@ request (PenaltyLogTable), which the kernel itself appends to — so the look-ah
 needs it, and the host uploads tokens only to seed a request the log does not hold ("Penalties from the
 captured step")."""
 import os
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -50,6 +52,50 @@ from hydrainfer_amd.model.llama import LanguageModelParameters
 from hydrainfer_amd.sampling import (PENALTY_RECORD_WORDS, SAMPLE_LOG_MAX, SAMPLE_MAX_N, SAMPLE_RECORD_WORDS,
                                      pack_penalty_records, pack_resident_records, sample_rows_resident,
                                      sample_rows_resident_penalized)
+
+# The variants of a captured step, each with what the one before it has: the argmax; hx_sample_rows_resident over the
+# resident records; hx_sample_rows_resident_penalized over the penalty records and the token log as well.  A decoder
+# has a prefix of them (GraphedDecoder.variants).
+VARIANTS = ("greedy", "sampled", "penalized")
+
+
+class CapturedStep(NamedTuple):
+    graph: object                  # a hipGraph or a launch plan: .replay()
+    out: torch.Tensor              # the step's tokens (a view of prev_tokens)
+    err: Optional[torch.Tensor]    # the give-up word of its in-kernel hand-overs, None without any
+    logits: Optional[torch.Tensor] # None for the greedy variant
+
+
+def step_variant(records, penalties, variants=VARIANTS):
+    """What launch() was given -> (variant, records, penalties) for a decoder that has `variants`: all None counts as
+    None, and what the decoder or the rows cannot serve is refused."""
+    if records is not None and all(r is None for r in records):
+        records = None
+    if records is not None and "sampled" not in variants:
+        raise HydraHipError("sampling records for a decoder without a sampled variant (sampled=False, a vocabulary "
+                            f"above {SAMPLE_MAX_N}, or logits that are not fp16 / bf16)")
+    if penalties is not None and all(p is None for p in penalties):
+        penalties = None
+    if penalties is not None:
+        if "penalized" not in variants:
+            raise HydraHipError("penalties for a decoder without a penalised variant (penalized=False, or no sampled variant)")
+        if records is None or any(p is not None and r is None for p, r in zip(penalties, records)):
+            raise HydraHipError("a penalised row needs a record: (0.0, 1.0, 0, 0, n_out - position) for a greedy one")
+    return VARIANTS[(records is not None) + (penalties is not None)], records, penalties
+
+
+NAMED, ANONYMOUS, PADDING = "named", "anonymous", "padding"
+
+
+def row_identity(row: tuple, i: int):
+    """Launch row i -> (sid, kind).  A row that names its sequence (a sixth element) is NAMED and keyed by it; one that
+    does not is ANONYMOUS, keyed ("row", i), and the stager writes its table in full every step; a sixth element of None
+    is a PADDING / warm-up row — no table of its own for the stager, ("row", i) for the penalty log."""
+    if len(row) <= 5:
+        return ("row", i), ANONYMOUS
+    if row[5] is None:
+        return ("row", i), PADDING
+    return row[5], NAMED
 
 
 class DecodeStager:
@@ -115,13 +161,10 @@ class DecodeStager:
         starts = []
         for i, r in enumerate(rows):
             tbl = r[4]
-            if len(r) > 5:
-                sid, anonymous = r[5], False
-                if sid is None:
-                    starts.append(0)
-                    continue
-            else:                              # a caller that does not name its sequences: row i's table is written in full
-                sid, anonymous = ("row", i), True
+            sid, kind = row_identity(r, i)
+            if kind is PADDING:
+                starts.append(0)
+                continue
             nb = len(tbl)
             if nb > cap:
                 raise HydraHipError(f"a sequence of {nb} blocks in a decoder built for {cap}")
@@ -129,7 +172,7 @@ class DecodeStager:
             if e is None:
                 e = self.slot_of[sid] = [self._alloc(), 0, -1, self.step_no]
             e[3] = self.step_no
-            if anonymous or nb < e[1] or (e[1] and tbl[e[1] - 1] != e[2]):
+            if kind is ANONYMOUS or nb < e[1] or (e[1] and tbl[e[1] - 1] != e[2]):
                 e[1] = 0                       # not the table this slot holds a prefix of: written again in full
             if nb > e[1]:
                 new = tbl[e[1]:]
@@ -178,7 +221,7 @@ class DecodeStager:
             st[o["rank"] + 1:o["rank"] + B + 1] = np.argsort(-kv, kind="stable")
         else:
             st[o["rank"]] = 0
-            st[o["rank"] + 1:o["rank"] + B + 1] = self._arange_b(B)
+            st[o["rank"] + 1:o["rank"] + B + 1] = self._arange[:B]
         st[o["kv_cu"]] = 0
         np.cumsum(kv, out=kv)
         at = self.head_words + 1
@@ -189,9 +232,6 @@ class DecodeStager:
             e[1], e[2] = before + 1, block
         st[self.head_words] = len(grown)
         return kv_max
-
-    def _arange_b(self, B: int):
-        return np.arange(B, dtype=np.int32)
 
     def touch(self, sids) -> None:
         """The sequences of a cohort episode were seen until now (least-recently-seen bookkeeping)."""
@@ -287,6 +327,37 @@ class PenaltyLogTable:
             e[2] = self.step_no
 
 
+class ResidentTable:
+    """A table that stays on the device, one packed row per launch row: `tensor`, the host's copy of what it holds, by
+    row (`mirror`), and the pinned double buffer new rows go through — used alternately with the decoder's staging
+    buffers and guarded by the same events.  `packer(rows, out=None)` packs a list of rows (None: the row that does
+    nothing) into int32 [len(rows), words].  On a CPU device (tests/test_decode_step_cpu.py) nothing is pinned."""
+
+    def __init__(self, packer, words: int, n_rows: int, device):
+        self.packer, self.words = packer, words
+        empty = torch.from_numpy(packer([None] * n_rows))
+        self.tensor = empty.to(device)
+        self.mirror: List[Optional[tuple]] = [None] * n_rows
+        pinned = torch.device(device).type != "cpu"
+        self.staging = [empty.clone().pin_memory() if pinned else empty.clone() for _ in range(2)]
+        self.stage = [t.numpy() for t in self.staging]
+
+    def update(self, which: int, want: list) -> Optional[Tuple[int, int, int]]:
+        """The first len(want) rows are to hold `want`: None when they do, else the rows are packed into pinned buffer
+        `which` and the (dst address, src address, words) copy to enqueue comes back."""
+        B = len(want)
+        if want == self.mirror[:B]:
+            return None
+        self.packer(want, self.stage[which][:B])
+        self.mirror[:B] = want
+        return self.tensor.data_ptr(), self.staging[which].data_ptr(), self.words * B
+
+    def reset(self) -> None:
+        """Every row back to None, by a copy in stream order."""
+        self.tensor.copy_(torch.from_numpy(self.packer([None] * len(self.mirror))))
+        self.mirror = [None] * len(self.mirror)
+
+
 class GraphedDecoder:
     def __init__(self, language_model, kv_cache_block_manager, max_batch: int = 64,
                  max_blocks_per_seq: int = 256, pad_to: int = 4, executor: str = None, sampled: bool = False,
@@ -303,7 +374,7 @@ class GraphedDecoder:
         self.kv = kv_cache_block_manager
         self.dev = self.kv.device
         self.pad_to = pad_to
-        self.max_batch = (max_batch + pad_to - 1) // pad_to * pad_to
+        self.max_batch = self._padded(max_batch)
         self.cap = max_blocks_per_seq
         B = self.max_batch
         # scratch block for padding rows
@@ -335,38 +406,30 @@ class GraphedDecoder:
         self.launch_rows = {}              # launch id -> number of live rows
         n_layers = self.model.shape.num_hidden_layers
         self.kv_caches = [KVCache.from_token_cache(self.kv.get_layer_cache(l)) for l in range(n_layers)]
-        self.graphs: Dict[Tuple[int, int], tuple] = {}
+        self.graphs: Dict[Tuple[int, int, str], CapturedStep] = {}
         # sampled decoding from the graph: the records of the launch rows, resident; a padding row keeps the greedy record.
         # A vocabulary wider than the sampling kernel's row, or logits it does not read: no sampled variant — `sampled`
         # stays False and the executor keeps such batches eager
         self.sampled = bool(sampled) and self.model.shape.vocab_size <= SAMPLE_MAX_N \
             and self.model.dtype in (torch.float16, torch.bfloat16)
         self.keep_draws = keep_draws and self.sampled      # tests: the sampled graphs also write each row's u
-        self.last_sampled = False                          # the variant of the most recent launch (launch_cohort repeats it)
         if self.sampled:
-            greedy = torch.from_numpy(pack_resident_records([None] * B))
-            self.records = greedy.to(self.dev)
-            # what the table holds, by row (the host's copy), and the pinned double buffer new records go through —
-            # used alternately with `staging` and guarded by the same events
-            self.resident: List[Optional[tuple]] = [None] * B
-            self.record_staging = [greedy.clone().pin_memory() for _ in range(2)]
-            self.record_stage = [t.numpy() for t in self.record_staging]
+            self.record_table = ResidentTable(pack_resident_records, SAMPLE_RECORD_WORDS, B, self.dev)
+            self.records = self.record_table.tensor
         # penalties from the graph: a third variant of the step ends in hx_sample_rows_resident_penalized over a token log
         # that stays on the device — a slot per REQUEST (PenaltyLogTable), twice as many as launch rows — and a table of
         # the launch rows' penalties and slots beside `records`.  Without a sampled variant: off, as `sampled` is
         self.penalized = bool(penalized) and self.sampled
-        self.last_variant = None                           # None (greedy), "sampled" or "penalized"
+        self.variants = VARIANTS[:1 + self.sampled + self.penalized]
+        self.last_variant = "greedy"                       # the variant of the most recent launch (launch_cohort repeats it)
         if self.penalized:
             if not 1 <= penalty_log_cap <= SAMPLE_LOG_MAX:
                 raise HydraHipError(f"penalty_log_cap {penalty_log_cap} outside 1 .. {SAMPLE_LOG_MAX}")
             self.penalty_log_cap = cap = int(penalty_log_cap)
             self.log_table = PenaltyLogTable(2 * B, cap)
             self.token_log = torch.zeros(2 * B, cap, dtype=torch.int32, device=self.dev)
-            none = torch.from_numpy(pack_penalty_records([None] * B))
-            self.penalty_records = none.to(self.dev)
-            self.resident_penalties: List[Optional[tuple]] = [None] * B
-            self.penalty_staging = [none.clone().pin_memory() for _ in range(2)]
-            self.penalty_stage = [t.numpy() for t in self.penalty_staging]
+            self.penalty_table = ResidentTable(pack_penalty_records, PENALTY_RECORD_WORDS, B, self.dev)
+            self.penalty_records = self.penalty_table.tensor
             # the seeds of a fill, back to back (at worst every row of a launch, each with a full log row)
             self.seed_staging = [torch.zeros(B * cap, dtype=torch.int32).pin_memory() for _ in range(2)]
             self.seed_stage = [t.numpy() for t in self.seed_staging]
@@ -375,10 +438,18 @@ class GraphedDecoder:
             self.host_draws = [torch.zeros(B, dtype=torch.float32).pin_memory() for _ in range(2)]
             self.draw_rows = {}            # launch id -> number of live rows (sampled launches only)
 
+    @property
+    def resident_penalties(self) -> List[Optional[tuple]]:
+        """What the penalty table holds, by launch row (the host's copy)."""
+        return self.penalty_table.mirror
+
+    def _padded(self, n: int) -> int:
+        """The row count of the captured step that serves n live rows."""
+        return (n + self.pad_to - 1) // self.pad_to * self.pad_to
+
     def fits(self, n_seqs: int, max_blocks: int) -> bool:
         """n_seqs rows whose longest block table has max_blocks entries."""
-        padded = (n_seqs + self.pad_to - 1) // self.pad_to * self.pad_to
-        return padded <= self.max_batch and max_blocks <= self.cap
+        return self._padded(n_seqs) <= self.max_batch and max_blocks <= self.cap
 
     def _views(self, B: int):
         o, s = self.off, self.static
@@ -402,11 +473,11 @@ class GraphedDecoder:
                                     kv_max_seq_len=kv_max, decode_rank=rank) for kc in self.kv_caches]
         return LanguageModelParameters(attention_params=attn, all_sequences_decode=True)
 
-    def _body(self, B: int, params, sampled=False):
-        """One decode step as library launches only (+ the lm_head GEMM): recordable in a launch plan.  sampled: the
-        step ends in hx_sample_rows_resident over the resident records instead of the argmax, and its logits come back
-        as a third result; sampled == "penalized": in hx_sample_rows_resident_penalized, over the resident penalty
-        records and the token log as well."""
+    def _body(self, B: int, params, variant: str):
+        """One decode step as library launches only (+ the lm_head GEMM): recordable in a launch plan.  -> (out, err,
+        logits).  "sampled": the step ends in hx_sample_rows_resident over the resident records instead of the argmax;
+        "penalized": in hx_sample_rows_resident_penalized, over the resident penalty records and the token log as well.
+        Both give their logits back, "greedy" gives None."""
         ids, pos = self._views(B)[:2]
         src = self._views(B)[6]
         lib = _lib.lib()
@@ -427,11 +498,11 @@ class GraphedDecoder:
         self.model.sample_out = out
         logits = None
         try:
-            if sampled == "penalized":
+            if variant == "penalized":
                 logits = self.model.forward_logits(fed, pos, params)
                 res = sample_rows_resident_penalized(logits, self.records[:B], pos, self.penalty_records[:B], self.token_log,
                                                      out=out, u_out=self.draws[:B] if self.keep_draws else None)
-            elif sampled:
+            elif variant == "sampled":
                 logits = self.model.forward_logits(fed, pos, params)
                 res = sample_rows_resident(logits, self.records[:B], pos, out=out,
                                            u_out=self.draws[:B] if self.keep_draws else None)
@@ -449,10 +520,9 @@ class GraphedDecoder:
             err = torch.empty(1, dtype=torch.int32, device=self.dev)
             _lib.check(lib.hx_collect_errors(err.data_ptr(), sync.data_ptr(), sync.numel() // sync.shape[-1],
                                              sync.shape[-1], 1, None, _lib.current_stream()), "collect_errors")
-        return (out, err, logits) if sampled else (out, err)
+        return out, err, logits
 
-    def _capture(self, B: int, bucket: int, variant: str = None):
-        sampled = variant if variant in ("sampled", "penalized") else False
+    def _capture(self, B: int, bucket: int, variant: str) -> CapturedStep:
         params = self._params(B, bucket if bucket else 4096)
         saved = self.prev_tokens.clone()
         side = torch.cuda.Stream(device=self.dev)
@@ -460,22 +530,22 @@ class GraphedDecoder:
         with torch.cuda.stream(side):
             for _ in range(2):             # warm-up outside capture: workspace growth, lazy init
                 self.prev_tokens.copy_(saved)
-                self._body(B, params, sampled)
+                self._body(B, params, variant)
             self.prev_tokens.copy_(saved)
         torch.cuda.current_stream(self.dev).wait_stream(side)
         graph = None
         if self.executor == "plan":
             graph = launch_plan.LaunchPlan(self.dev)
             try:
-                out, err, *logits = graph.capture(lambda: self._body(B, params, sampled))
+                step = graph.capture(lambda: self._body(B, params, variant))
             except launch_plan.PlanNotRecordable:
                 graph = None       # a step with torch ops in it (library GEMMs, a shape off the hx fast path): hipGraph
                 self.executor = "graph"
         if graph is None:
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                out, err, *logits = self._body(B, params, sampled)
-        return (graph, out, err, *logits)
+                step = self._body(B, params, variant)
+        return CapturedStep(graph, *step)
 
     def _copy_words(self, copies) -> None:
         """(dst address, src address, words) copies, two to a launch (hx_copy_words2)."""
@@ -483,78 +553,72 @@ class GraphedDecoder:
             a, b = copies[i], copies[i + 1] if i + 1 < len(copies) else (None, None, 0)
             _lib.check(_lib.lib().hx_copy_words2(*a, *b, _lib.current_stream()), "copy_words2")
 
-    def _fill(self, rows: List[tuple], B: int, records=None, penalties=None) -> int:
-        """Stage the step (DecodeStager.stage) and enqueue the kernel that applies it to the resident buffer.  records:
-        None, or the sampled step's record per live row — rows of the resident table that hold something else are
-        rewritten, through the pinned buffer of this fill, by one more launch.  penalties: None, or per live row None or
-        (frequency, presence, repetition[, the request's generated tokens]) — the rows' log slots are looked up, the
-        penalty table is rewritten where it differs, and a row the log does not hold the tokens of is seeded, through
-        the pinned buffers of this fill as well."""
-        slots = seeds = None
-        if penalties is not None:
-            slots, seeds = self.log_table.step([
-                None if p is None else (row[5] if len(row) > 5 and row[5] is not None else ("row", i),
-                                        records[i][4] + row[1], p[3] if len(p) > 3 else None)
-                for i, (row, p) in enumerate(zip(rows, penalties))])
+    def _staged(self, fill) -> int:
+        """One turn of the pinned double buffers: take the next one, wait for the launch that last read it, let
+        fill(which) -> (kv_max, copies) write the staging buffer (and the other pinned buffers of the turn the copies
+        read), enqueue the kernel that applies it to the resident buffer, then the copies, and record the turn's event
+        behind the last of them.  -> kv_max."""
         which = self.fills % 2
         self.fills += 1
         self.copy_done[which].synchronize()      # no-op until the buffer has been used once
-        kv_max = self.stager.stage(self.stage[which], rows, B)
+        kv_max, copies = fill(which)
         # (a kernel reading the pinned buffer, not a memcpy: a memcpy between two graph launches left the stream idle
         # for ~0.1 ms per step)
         _lib.check(_lib.lib().hx_stage_decode(self.static.data_ptr(), self.static.numel(), self.staging[which].data_ptr(),
                                               self.stager.head_words, _lib.current_stream()), "stage_decode")
-        if records is not None:
-            want = list(records) + [None] * (B - len(records))          # a padding row is greedy
-            if want != self.resident[:B]:
-                pack_resident_records(want, self.record_stage[which][:B])
-                _lib.check(_lib.lib().hx_copy_words2(self.records.data_ptr(), self.record_staging[which].data_ptr(),
-                                                     SAMPLE_RECORD_WORDS * B, None, None, 0, _lib.current_stream()),
-                           "copy_words2")
-                self.resident[:B] = want
-        if penalties is not None:
-            copies = []
-            want = [None if p is None else (p[0], p[1], p[2], s) for p, s in zip(penalties, slots)] + [None] * (B - len(rows))
-            if want != self.resident_penalties[:B]:
-                pack_penalty_records(want, self.penalty_stage[which][:B])
-                copies.append((self.penalty_records.data_ptr(), self.penalty_staging[which].data_ptr(), PENALTY_RECORD_WORDS * B))
-                self.resident_penalties[:B] = want
-            at, cap = 0, self.penalty_log_cap
-            for slot, tokens in seeds:
-                self.seed_stage[which][at:at + len(tokens)] = tokens
-                copies.append((self.token_log.data_ptr() + 4 * slot * cap, self.seed_staging[which].data_ptr() + 4 * at,
-                               len(tokens)))
-                at += len(tokens)
-            self._copy_words(copies)
+        self._copy_words(copies)
         self.copy_done[which].record()
         return kv_max
+
+    def _fill(self, rows: List[tuple], B: int, records=None, penalties=None) -> int:
+        """Stage the step (DecodeStager.stage) and enqueue the kernel that applies it to the resident buffer.  records:
+        None, or the sampled step's record per live row — rows of the resident table that hold something else are
+        rewritten, through the pinned buffer of this fill.  penalties: None, or per live row None or
+        (frequency, presence, repetition[, the request's generated tokens]) — the rows' log slots are looked up, the
+        penalty table is rewritten where it differs, and a row the log does not hold the tokens of is seeded, through
+        the pinned buffers of this fill as well.  The copies go record table, penalty table, seeds, two to a launch."""
+        slots = seeds = None
+        if penalties is not None:
+            slots, seeds = self.log_table.step([
+                None if p is None else (row_identity(row, i)[0], records[i][4] + row[1], p[3] if len(p) > 3 else None)
+                for i, (row, p) in enumerate(zip(rows, penalties))])
+        pad = [None] * (B - len(rows))            # a padding row is greedy and unpenalised
+
+        def fill(which):
+            kv_max = self.stager.stage(self.stage[which], rows, B)
+            copies = []
+            if records is not None:
+                copies.append(self.record_table.update(which, list(records) + pad))
+            if penalties is not None:
+                copies.append(self.penalty_table.update(
+                    which, [None if p is None else (p[0], p[1], p[2], s) for p, s in zip(penalties, slots)] + pad))
+                at, cap = 0, self.penalty_log_cap
+                for slot, tokens in seeds:
+                    self.seed_stage[which][at:at + len(tokens)] = tokens
+                    copies.append((self.token_log.data_ptr() + 4 * slot * cap, self.seed_staging[which].data_ptr() + 4 * at,
+                                   len(tokens)))
+                    at += len(tokens)
+            return kv_max, [c for c in copies if c is not None]
+        return self._staged(fill)
 
     def warmup(self, batch_sizes: List[int], kv_max: int = 1024) -> None:
         rows = [(1, 0, self.pad_block * self.kv.block_size, 1, [self.pad_block], None)]
         for n in batch_sizes:
-            B = (n + self.pad_to - 1) // self.pad_to * self.pad_to
-            key = (B, self._kv_bucket(B, kv_max))
-            variants = ((), ("sampled",), ("penalized",)) if self.penalized else ((), ("sampled",)) if self.sampled else ((),)
-            for key in [key + v for v in variants]:
+            B = self._padded(n)
+            for variant in self.variants:
+                key = (B, self._kv_bucket(B, kv_max), variant)
                 if key not in self.graphs:
                     self._fill(rows, B)
-                    if key[2:] == ("penalized",) and any(p is not None for p in self.resident_penalties):
+                    if variant == "penalized" and any(p is not None for p in self.resident_penalties):
                         # a warm-up behind real launches: its padding rows must not write into a live request's log
-                        self.penalty_records.copy_(torch.from_numpy(pack_penalty_records([None] * self.max_batch)))
-                        self.resident_penalties = [None] * self.max_batch
+                        self.penalty_table.reset()
                     self.graphs[key] = self._capture(*key)
         torch.cuda.synchronize(self.dev)
 
     def launch_cohort(self, n: int, pos, slots, starts, grown) -> int:
         """launch() for the same n sequences as the previous launch, one token further (DecodeStager.stage_cohort)."""
-        B = (n + self.pad_to - 1) // self.pad_to * self.pad_to
-        which = self.fills % 2
-        self.fills += 1
-        self.copy_done[which].synchronize()
-        kv_max = self.stager.stage_cohort(self.stage[which], n, B, pos, slots, starts, grown)
-        _lib.check(_lib.lib().hx_stage_decode(self.static.data_ptr(), self.static.numel(), self.staging[which].data_ptr(),
-                                              self.stager.head_words, _lib.current_stream()), "stage_decode")
-        self.copy_done[which].record()
+        B = self._padded(n)
+        kv_max = self._staged(lambda which: (self.stager.stage_cohort(self.stage[which], n, B, pos, slots, starts, grown), ()))
         # the variant of the launch the cohort was formed behind: the same rows in the same order, so their records
         # are in the table already, and the positions staged above move every row's offset on by one.  Penalised rows:
         # their slots are unchanged and the log holds their newest token already — nothing to upload
@@ -568,30 +632,18 @@ class GraphedDecoder:
         all None is the greedy step as it ever was.  penalties (a decoder built with penalized=True): per row None or
         (frequency, presence, repetition[, tokens]) — such a row needs a record (a greedy one: (0.0, 1.0, 0, 0, n_out -
         position)), and `tokens`, a sequence holding the request's generated tokens, whenever the log does not continue
-        (PenaltyLogTable); None or all None: the launch is the one it is without the argument."""
+        (PenaltyLogTable); None or all None: the launch is the one it is without the argument (step_variant)."""
         n = len(rows)
-        B = (n + self.pad_to - 1) // self.pad_to * self.pad_to
-        if records is not None and all(r is None for r in records):
-            records = None
-        if records is not None and not self.sampled:
-            raise HydraHipError("sampling records for a decoder without a sampled variant (sampled=False, a vocabulary "
-                                f"above {SAMPLE_MAX_N}, or logits that are not fp16 / bf16)")
-        if penalties is not None and all(p is None for p in penalties):
-            penalties = None
-        if penalties is not None:
-            if not self.penalized:
-                raise HydraHipError("penalties for a decoder without a penalised variant (penalized=False, or no sampled variant)")
-            if records is None or any(p is not None and r is None for p, r in zip(penalties, records)):
-                raise HydraHipError("a penalised row needs a record: (0.0, 1.0, 0, 0, n_out - position) for a greedy one")
-        variant = "penalized" if penalties is not None else "sampled" if records is not None else None
+        B = self._padded(n)
+        variant, records, penalties = step_variant(records, penalties, self.variants)
         kv_max = self._fill(rows, B, records, penalties)
-        self.last_variant, self.last_sampled = variant, variant is not None
+        self.last_variant = variant
         return self._replay(n, B, kv_max, variant)
 
     def sample_logits(self, B: int, bucket: int, variant: str = "sampled"):
         """Tests: the logits tensor the sampled (or "penalized") graph (B, bucket) writes — the graph's own buffer, valid
         until the next replay."""
-        return self.graphs[(B, bucket, variant)][3]
+        return self.graphs[(B, bucket, variant)].logits
 
     def fetch_draws(self, launch_id: int):
         """Tests (keep_draws=True): the per-row u of a sampled launch, fp32 (waits for it); None for a greedy launch.
@@ -603,12 +655,11 @@ class GraphedDecoder:
         self.events[launch_id % 2].synchronize()
         return self.host_draws[launch_id % 2][:n].numpy().copy()
 
-    def _replay(self, n: int, B: int, kv_max: int, sampled=False) -> int:
-        """sampled: False / None (the greedy step), True or "sampled", or "penalized"."""
-        key = (B, self._kv_bucket(B, kv_max)) + (("sampled" if sampled is True else sampled,) if sampled else ())
+    def _replay(self, n: int, B: int, kv_max: int, variant: str) -> int:
+        key = (B, self._kv_bucket(B, kv_max), variant)
         if key not in self.graphs:
             self.graphs[key] = self._capture(*key)
-        graph, out, err = self.graphs[key][:3]
+        graph, out, err, _ = self.graphs[key]
         graph.replay()
         self.launches += 1
         slot = self.launches % 2
@@ -620,7 +671,7 @@ class GraphedDecoder:
         self.launch_has_err[self.launches] = err is not None
         if self.keep_draws:
             self.draw_rows.pop(self.launches - 2, None)
-            if sampled:
+            if variant != "greedy":
                 _lib.check(_lib.lib().hx_copy_words2(self.host_draws[slot].data_ptr(), self.draws.data_ptr(), n, None, None,
                                                      0, _lib.current_stream()), "copy_words2")
                 self.draw_rows[self.launches] = n

@@ -60,7 +60,7 @@ class ResidentDecoder:
         self.tokens[self.launches] = out
         return self.launches
 
-    def launch(self, rows):
+    def launch(self, rows, records=None, penalties=None):
         B = (len(rows) + 3) // 4 * 4
         st = self.st[self.launches % 2]
         self.stager.stage(st, rows, B)

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from hydrainfer_amd._lib import HydraHipError
-from hydrainfer_amd.engine.graph_decode import DecodeStager
+from hydrainfer_amd.engine.graph_decode import ANONYMOUS, NAMED, PADDING, DecodeStager, row_identity
 from hydrainfer_amd.layer.causal_attention import decode_rank_descriptor
 
 
@@ -98,6 +98,25 @@ def test_stager_refuses_what_the_kernels_cannot_take():
         stg.stage(st, [(100, 3, 0, 4, [0], 1)], 4)              # token outside the vocabulary
     with pytest.raises(HydraHipError):
         stg.stage(st, [(5, 3, 0, 4, [0, 1, 2, 3, 4], 1)], 4)    # more blocks than the decoder was built for
+
+
+def test_row_identity_and_what_the_stager_writes_for_it():
+    rows = [(5, 20, 40 * 16 + 4, 21, [40, 41]), (-2, 17, 3 * 16 + 1, 18, [3, 4], 7), (1, 0, 9 * 16, 1, [9], None)]
+    assert [row_identity(r, i) for i, r in enumerate(rows)] == [(("row", 0), ANONYMOUS), (7, NAMED), (("row", 2), PADDING)]
+    stg = DecodeStager(4, 4, 16, 9, max_pos=128, vocab=100)
+    st = np.zeros(stg.staging_words, dtype=np.int32)
+    assert stg.stage(st, rows, 4) == 21
+    # head: ids, pos, slots, src, kv_cu, cu_blocks (the padding row and the pad: table slot 0), rank; then 3 runs — the
+    # padding table once, the anonymous row's table in full, the named row's
+    assert st.tolist() == [5, 0, 1, 0, 20, 17, 0, 0, 644, 49, 144, 144, -1, 1, -1, -1, 0, 21, 39, 40, 41, 4, 8, 0, 0, 0, 0, 0, 1,
+                           2, 3, 3, 31, 1, 9, 35, 2, 40, 41, 39, 2, 3, 4] + [0] * 19
+    # one step on: the anonymous row is written in full again, the named one appends its new block, the padding row nothing
+    rows = [(6, 21, 40 * 16 + 5, 22, [40, 41]), (-1, 32, 5 * 16, 33, [3, 4, 5], 7), (1, 0, 9 * 16, 1, [9], None)]
+    st = np.zeros(stg.staging_words, dtype=np.int32)
+    assert stg.stage(st, rows, 4) == 33
+    assert st.tolist() == [6, 0, 1, 0, 21, 32, 0, 0, 645, 80, 144, 144, -1, 0, -1, -1, 0, 22, 55, 56, 57, 4, 8, 0, 0, 0, 1, 1, 0,
+                           2, 3, 2, 35, 2, 40, 41, 41, 1, 5] + [0] * 23
+    assert stg.slot_of == {("row", 0): [1, 2, 41, 2], 7: [2, 3, 5, 2]}
 
 
 @pytest.mark.gpu

@@ -167,7 +167,7 @@ class FakeGraphDecoder:
     def fits(self, n_seqs, n_blocks):
         return True
 
-    def launch(self, rows):
+    def launch(self, rows, records=None, penalties=None):
         prev = self.tokens.get(self.launches, [])
         out = []
         for token, pos, slot, kv_len, table, _sid in rows:

@@ -35,9 +35,9 @@ def run(reqs, monkeypatch, switch=True):
         assert dec.sampled and dec.penalized
         real_replay = dec._replay
 
-        def replay(n, B, kv_max, sampled=False):
-            launch = real_replay(n, B, kv_max, sampled)
-            variants[launch] = (sampled, made[0].step)
+        def replay(n, B, kv_max, variant):
+            launch = real_replay(n, B, kv_max, variant)
+            variants[launch] = (variant, made[0].step)
             return launch
         dec._replay = replay
     watch = Watch(old.lm, fill, monkeypatch)
@@ -65,7 +65,7 @@ def test_penalised_requests_decode_from_the_graph(monkeypatch):
     assert all(r.penalty_history is not None for r in (rcbs[0], rcbs[1])) and rcbs[2].penalty_history is None
     # after the prefill steps: no eager sampling launch; the penalised variant ran, the cohort formed and ran it
     assert watch.last_prefill > 0 and watch.eager and max(watch.eager) <= watch.last_prefill, (watch.eager, watch.last_prefill)
-    assert any(len(key) == 3 and key[2] == "penalized" for key in dec.graphs), "the penalised variant was never replayed"
+    assert any(key[2] == "penalized" for key in dec.graphs), "the penalised variant was never replayed"
     assert fill.n_cohort_steps > 0
     cohort_launches = [launch for launch in watch.fetched if launch not in watch.by_launch_decode]
     assert cohort_launches and all(variants[launch][0] == "penalized" for launch in cohort_launches), \
@@ -114,6 +114,6 @@ def test_switch_off_a_penalised_request_still_sends_the_steps_to_eager(monkeypat
     assert dec.sampled and not dec.penalized and not hasattr(dec, "token_log")
     assert all(len(r.output_token_ids) == m for r, m in zip(rcbs, MAX_TOKENS))
     assert max(watch.eager) > watch.last_prefill
-    assert not any(len(key) == 3 and key[2] == "penalized" for key in dec.graphs)
+    assert not any(key[2] == "penalized" for key in dec.graphs)
     for i in PENALTIES:
         assert Counter(rcbs[i].output_token_ids) == dict(zip(rcbs[i].penalty_history.ids, rcbs[i].penalty_history.counts))

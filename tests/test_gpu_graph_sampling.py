@@ -66,7 +66,7 @@ def test_sampled_steps_reproduce_from_their_logits(executor):
     first = dec.run(step_rows(caches, 0, None), [None] * 3)
     assert first == plain.run(step_rows(plain_caches, 0, None))
     assert dec.run(step_rows(caches, 0, None)) == first
-    assert list(dec.graphs) == [(B, 256)] and list(plain.graphs) == [(B, 256)]
+    assert list(dec.graphs) == [(B, 256, "greedy")] and list(plain.graphs) == [(B, 256, "greedy")]
     with pytest.raises(HydraHipError):
         plain.launch(step_rows(plain_caches, 0, None), RECORDS)
 
@@ -92,7 +92,7 @@ def test_sampled_steps_reproduce_from_their_logits(executor):
                                  f"step {step} row {r}")
             assert kind == "sampled"
         assert previous[1] == int(argmax_rows(logits)[1]) == greedy_previous[1]
-    assert (B, 256, "sampled") in dec.graphs and len(dec.graphs) == 2 and list(plain.graphs) == [(B, 256)]
+    assert (B, 256, "sampled") in dec.graphs and len(dec.graphs) == 2 and list(plain.graphs) == [(B, 256, "greedy")]
     assert [t[1] for t in tokens] == [t[1] for t in greedy_tokens]
     assert any(t[r] != g[r] for t, g in zip(tokens, greedy_tokens) for r in (0, 2)), "no draw left the greedy path"
     # the padding row stayed greedy: its record in the resident table is the greedy one
@@ -102,7 +102,7 @@ def test_sampled_steps_reproduce_from_their_logits(executor):
 def test_warmup_captures_both_variants_and_cohort_repeats_the_variant():
     dec, caches = decoder(sampled=True, keep_draws=True)
     dec.warmup([3], kv_max=64)
-    assert sorted(dec.graphs, key=len) == [(B, 256), (B, 256, "sampled")]
+    assert list(dec.graphs) == [(B, 256, "greedy"), (B, 256, "sampled")]
     # a sampled launch, then the cohort form of the next two steps: the records stay resident, the offset moves with
     # the position — the draws are those of base + position
     lid = dec.launch(step_rows(caches, 0, None), RECORDS)

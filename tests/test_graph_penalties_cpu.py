@@ -177,4 +177,5 @@ def test_the_other_conditions_are_still_refused(odd):
 def test_without_a_penalised_row_the_return_value_is_todays():
     batch = [request(0, 3, 20, temperature=0.8, top_p=0.9, top_k=20, seed=77), request(1, 1, 17)]
     assert with_variant()._decode_rows(batch) == executor(True)._decode_rows(batch)
-    assert len(with_variant()._decode_rows(batch)) == 2
+    rows, records, penalties = with_variant()._decode_rows(batch)
+    assert penalties is None and len(records) == len(rows) == 2

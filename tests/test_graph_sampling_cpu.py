@@ -62,18 +62,20 @@ def test_decode_rows_gives_records_under_the_switch():
     batch = [request(0, 3, 20, temperature=0.8, top_p=0.9, top_k=20, seed=77),
              request(1, 1, 17),
              request(2, 6, 9, temperature=1.3, seed=(1 << 40) + 1)]
-    rows, records = fill._decode_rows(batch)
+    rows, records, penalties = fill._decode_rows(batch)
+    assert penalties is None
     assert records == [(0.8, 0.9, 20, 77, 3 - 20), None, (1.3, 1.0, 0, (1 << 40) + 1, 6 - 9)]
     assert [r[:4] for r in rows] == [(5, 20, 40 * BS + 4, 21), (5, 17, 41 * BS + 1, 18), (5, 9, 5 * BS + 9, 10)]
     assert [r[5] for r in rows] == [0, 1, 2]
     # the rows are what the decoder gets with the switch off, for a batch the old test lets through
     greedy = [request(1, 1, 17), request(2, 6, 9)]
-    assert fill._decode_rows(greedy)[0] == executor(False)._decode_rows(greedy)
-    assert fill._decode_rows(greedy)[1] == [None, None]
+    assert (fill._decode_rows(greedy)[0], None, None) == executor(False)._decode_rows(greedy)
+    assert fill._decode_rows(greedy)[1] == [None, None] and fill._decode_rows(greedy)[2] is None
     # look-ahead: the input still on the device, and the placeholder counts as a generated token
     fill.pending = (4, [])
     rcb, inst = request(0, 4, 21, temperature=0.8, seed=77, token=PendingToken(4, 2))
-    rows, records = fill._decode_rows([(rcb, inst)])
+    rows, records, penalties = fill._decode_rows([(rcb, inst)])
+    assert penalties is None
     assert rows[0][0] == -3 and records == [(0.8, 1.0, 0, 77, 4 - 21)]          # the same base one step later
     assert fill._decode_rows([request(0, 4, 21, temperature=0.8, seed=77, token=PendingToken(3, 2))]) is None
 
@@ -90,9 +92,11 @@ def test_decode_rows_keeps_the_other_conditions(odd):
 def test_decode_rows_with_the_switch_off():
     fill = executor(False)
     assert fill._decode_rows([request(0, 1, 17), request(1, 3, 20, temperature=0.8, seed=7)]) is None
-    rows = fill._decode_rows([request(0, 1, 17), request(1, 3, 20)])
+    rows, records, penalties = fill._decode_rows([request(0, 1, 17), request(1, 3, 20)])
+    assert records is None and penalties is None
     assert isinstance(rows, list) and len(rows) == 2 and len(rows[0]) == 6
     # a decoder that has no such attribute at all (a stand-in from before the switch): as off
     fill.graph_decoder = NS(fits=lambda n, b: True)
     assert fill._decode_rows([request(1, 3, 20, temperature=0.8, seed=7)]) is None
-    assert len(fill._decode_rows([request(1, 3, 20)])) == 1
+    rows, records, penalties = fill._decode_rows([request(1, 3, 20)])
+    assert len(rows) == 1 and records is None and penalties is None
