@@ -103,6 +103,16 @@ __device__ __forceinline__ float smp_block_sum(float s, float* part) {
   constexpr bool LOGGED = false;                                                                       \
   const int32_t* const penalty_params = nullptr; int32_t* const token_log = nullptr;                   \
   const int32_t log_slots = 0, log_cap = 0;
+// and for its bias table, in the kernels that take none (bias_total the constant 0: step 1b finds no row with entries)
+#define SMP_NO_BIAS                                                                                    \
+  const int32_t* const bias_ids = nullptr; const float* const bias_values = nullptr; const int32_t* const cu_bias = nullptr; \
+  const int32_t bias_total = 0;
+// and for bias table and history together, in the resident kernels (total the constant 0: step 2 is not compiled)
+#define SMP_NO_TABLES                                                                                  \
+  SMP_NO_BIAS                                                                                          \
+  const int32_t* const hist_ids = nullptr; const int32_t* const hist_counts = nullptr; const int32_t* const cu_hist = nullptr; \
+  const float* const penalties = nullptr;                                                              \
+  constexpr int32_t total = 0;
 // log entries a thread holds in step 2L: 1024 threads x 4 = HX_SAMPLE_LOG_MAX
 #define SMP_LOG_PER_THREAD 4
 static_assert(HX_SAMPLE_LOG_MAX == SMP_THREADS * SMP_LOG_PER_THREAD, "the longest log prefix is what 1024 threads hold");
@@ -122,8 +132,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_rows_kernel(
   SMP_NO_SCORES
   SMP_NO_MASK
   SMP_NO_LOG
-  const int32_t* const bias_ids = nullptr; const float* const bias_values = nullptr; const int32_t* const cu_bias = nullptr;
-  const int32_t bias_total = 0;
+  SMP_NO_BIAS
 #include "sampling_body.inc"
 }
 
@@ -204,11 +213,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_rows_resident_kernel(
   SMP_NO_SCORES
   SMP_NO_MASK
   SMP_NO_LOG
-  const int32_t* const bias_ids = nullptr; const float* const bias_values = nullptr; const int32_t* const cu_bias = nullptr;
-  const int32_t bias_total = 0;
-  const int32_t* const hist_ids = nullptr; const int32_t* const hist_counts = nullptr; const int32_t* const cu_hist = nullptr;
-  const float* const penalties = nullptr;
-  constexpr int32_t total = 0;
+  SMP_NO_TABLES
 #include "sampling_body.inc"
 }
 
@@ -224,11 +229,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_rows_resident_penalized_ke
   constexpr bool LOGGED = true;
   SMP_NO_SCORES
   SMP_NO_MASK
-  const int32_t* const bias_ids = nullptr; const float* const bias_values = nullptr; const int32_t* const cu_bias = nullptr;
-  const int32_t bias_total = 0;
-  const int32_t* const hist_ids = nullptr; const int32_t* const hist_counts = nullptr; const int32_t* const cu_hist = nullptr;
-  const float* const penalties = nullptr;
-  constexpr int32_t total = 0;
+  SMP_NO_TABLES
 #include "sampling_body.inc"
 }
 #undef SMP_OFFSET_LO
@@ -308,19 +309,20 @@ static int sample_rows(SampleKernel which, const SampleArgs& a) {
 // the kernel's dynamic-LDS limit raised, which is no stream operation and may not happen while `stream` is being
 // captured: it is raised — to the widest row, so one call serves every n — on every launch outside a capture, and a
 // capture relies on such a launch having gone before (GraphedDecoder._capture runs the step twice first).
+static int raise_lds_limit(const void* kernel, size_t lds, hipStream_t stream) {
+  if (lds <= 48 * 1024) return HX_OK;
+  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+  hipError_t e = hipStreamIsCapturing(stream, &capturing);
+  if (e != hipSuccess) return hip_rc(e);
+  if (capturing != hipStreamCaptureStatusNone) return HX_OK;
+  return hip_rc(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(SAMPLE_MAX_N * sizeof(float))));
+}
+
 template <typename T>
 static int launch_sample_rows_resident(const SampleArgs& a, const int32_t* positions) {
   const size_t lds = (size_t)((a.n + 7) / 8 * 8) * sizeof(float);
-  if (lds > 48 * 1024) {
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    hipError_t e = hipStreamIsCapturing(a.stream, &capturing);
-    if (e != hipSuccess) return hip_rc(e);
-    if (capturing == hipStreamCaptureStatusNone) {
-      e = hipFuncSetAttribute((const void*)sample_rows_resident_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)(SAMPLE_MAX_N * sizeof(float)));
-      if (e != hipSuccess) return hip_rc(e);
-    }
-  }
+  const int rc = raise_lds_limit((const void*)sample_rows_resident_kernel<T>, lds, a.stream);
+  if (rc != HX_OK) return rc;
   launcher(sample_rows_resident_kernel<T>, (unsigned)a.rows, SMP_THREADS, lds, a.stream)(
       a.ids, a.cut_out, a.u_out, (const u16*)a.logits, (int32_t)a.n, a.ld, (const uint32_t*)a.sample_params, positions);
   return check_launch();
@@ -343,16 +345,8 @@ template <typename T>
 static int launch_sample_rows_resident_penalized(const SampleArgs& a, const int32_t* positions, const int32_t* penalty_params,
                                                  int32_t* token_log, int64_t log_slots, int64_t log_cap) {
   const size_t lds = (size_t)((a.n + 7) / 8 * 8) * sizeof(float);
-  if (lds > 48 * 1024) {
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    hipError_t e = hipStreamIsCapturing(a.stream, &capturing);
-    if (e != hipSuccess) return hip_rc(e);
-    if (capturing == hipStreamCaptureStatusNone) {
-      e = hipFuncSetAttribute((const void*)sample_rows_resident_penalized_kernel<T>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)(SAMPLE_MAX_N * sizeof(float)));
-      if (e != hipSuccess) return hip_rc(e);
-    }
-  }
+  const int rc = raise_lds_limit((const void*)sample_rows_resident_penalized_kernel<T>, lds, a.stream);
+  if (rc != HX_OK) return rc;
   launcher(sample_rows_resident_penalized_kernel<T>, (unsigned)a.rows, SMP_THREADS, lds, a.stream)(
       a.ids, a.cut_out, a.u_out, (const u16*)a.logits, (int32_t)a.n, a.ld, (const uint32_t*)a.sample_params, positions,
       penalty_params, token_log, (int32_t)(log_slots > 0x7fffffff ? 0x7fffffff : log_slots), (int32_t)log_cap);

@@ -23,8 +23,8 @@ from hydrainfer_amd.engine.rcb import PROCESSED_LOGPROBS, BatchRequest, PromptTo
 from hydrainfer_amd.model.llama import LanguageModelParameters
 # (the packers and kernels are reached by name: SAMPLING_MODES)
 from hydrainfer_amd.sampling import (GREEDY_RECORD, NO_PENALTIES, pack_constrained_step, pack_masked_step, pack_penalty_step,
-                                     pack_sample_step, penalized_argmax_rows, sample_rows, sample_rows_constrained,
-                                     sample_rows_logprobs, sample_rows_masked)
+                                     pack_sample_step, pack_scored_step, penalized_argmax_rows, sample_rows,
+                                     sample_rows_constrained, sample_rows_logprobs, sample_rows_masked)
 
 
 # What the table-driven modes of the eager sampling step (BatchFillExecutor._sample) differ in: how many elements of a
@@ -79,7 +79,7 @@ def scored_rows(rows) -> bool:
 def masked_rows(rows) -> bool:
     """rows: the sampling (rcb, inst) pairs of an eager step.  True when some request carries a token mask
     (allowed_token_ids, guided_choice) and delivers a token this step (a chunk head's sample is discarded): the step then
-    runs ONE hx_sample_rows_masked launch for the whole batch (BatchFillExecutor._sample_masked) — consulted ahead of
+    runs ONE hx_sample_rows_masked launch for the whole batch (BatchFillExecutor._sample_scored) — consulted ahead of
     scored_rows.  Read with a default: a stand-in for a request need not carry the attribute."""
     return any(getattr(rcb, "token_mask", None) is not None and not inst.is_chunked for rcb, inst in rows)
 
@@ -502,71 +502,24 @@ class BatchFillExecutor:
                                record, bias)[:take]
         return entries, at
 
-    def _sample_scored(self, batch: BatchRequest, inputs, params, logits=None):
-        """The eager step of a batch in which some request asked for PROCESSED log-probabilities (scored_rows) ->
-        (sampled, scores).  The same logits, then ONE hx_sample_rows_logprobs launch for the whole batch in place of the
-        mode's kernel: the four-element entries of the constrained mode, so constrained, drawn, penalised and plain
-        requests ride along and get the ids they would have got; want = -1 on every row but those of the processed
-        requests that deliver a token, so only those pay for their scores.  K is the largest top_logprobs among them.
-        The tables and `want` reach the device as one pinned buffer in one copy, the ids and scores come back in one.
-        RAW-mode logprobs requests in the same batch (greedy, unpenalised, unconstrained by admission) keep getting their
-        scores from hx_logprob_rows over the raw logits, exactly as in _sample: a mixed batch is two launches and two
-        packed buffers."""
+    def _sample_scored(self, batch: BatchRequest, inputs, params, logits=None, masked: bool = False):
+        """The eager step of a batch in which some request asked for PROCESSED log-probabilities (scored_rows) or, with
+        `masked`, carries a token mask (masked_rows) -> (sampled, scores).  The same logits, then ONE launch for the whole
+        batch in place of the mode's kernel — hx_sample_rows_logprobs, or hx_sample_rows_masked — over the four-element
+        entries of the constrained mode, so constrained, drawn, penalised and plain requests ride along and get the ids
+        they would have got.  want = -1 on every row but those of the processed requests that deliver a token, so only
+        those pay for their scores; K is the largest top_logprobs among them.  masked: mask_row = -1 on every row without
+        a mask (a chunk head's discarded sample included), rows on the same trie node share one mask of the step, and with
+        no processed request in the batch the launch is unscored and only the ids come back.  The step's tables, `want`
+        and the masks reach the device as one pinned buffer in one copy (pack_scored_step / pack_masked_step), the ids
+        and scores come back in one.  RAW-mode logprobs requests in the same batch (greedy, unpenalised, unconstrained by
+        admission) keep getting their scores from hx_logprob_rows over the raw logits, exactly as in _sample: a mixed
+        batch is two launches and two packed buffers."""
         rows = sampling_rows(batch)
         geometry = sel, decode, n_rows = self._step_rows(inputs, logits)
         entries, at = self._step_entries(batch, sel, decode, n_rows, 4)
-        step = pack_constrained_step(entries)
-        size = step.buffer.size
-        host = np.empty(size + n_rows, dtype=np.int32)
-        host[:size] = step.buffer
-        host[size:] = -1
-        top_k, raw = 0, []                      # the processed requests' K; the raw-mode requests' top_logprobs
-        for row, (rcb, inst) in zip(at, rows):
-            sp = rcb.sampling_params
-            if inst.is_chunked or not sp.logprobs:
-                continue
-            if asks_processed(rcb):
-                host[size + row] = 0
-                top_k = max(top_k, sp.top_logprobs)
-            else:
-                raw.append(sp.top_logprobs)
-        host = torch.from_numpy(host)
-        if torch.device(self.device).type == "cuda":
-            host = host.pin_memory()
-        dev = host.to(self.device, non_blocking=True)
-        tables, want = step.views(dev[:size]), dev[size:]
-        lm = self.language_model
-        if not raw and logits is None:
-            ids = lm.forward_scored(inputs.input_ids, inputs.image_features, inputs.position_ids, params, *tables,
-                                    top_k=top_k, want=want)[0]
-        else:
-            if logits is None:
-                logits = lm.forward_logits(inputs.input_ids, inputs.image_features, inputs.position_ids, params)
-            if raw:
-                raw_packed = self._raw_scores(logits, max(raw))
-            ids = sample_rows_logprobs(logits, *tables, top_k=top_k, want=want)[0]
-        sampled, *scores = self._to_host(logprob_rows_packed(ids, top_k), n_rows, top_k)
-        if raw:
-            raw_scores = self._to_host(raw_packed, n_rows, max(raw))[1:]
-            for row, (rcb, _) in zip(at, rows):
-                if rcb.sampling_params.logprobs and not asks_processed(rcb):
-                    for col, raw_col in zip(scores, raw_scores):
-                        col[row] = raw_col[row]
-        return self._pick(geometry, sampled, scores)
-
-    def _sample_masked(self, batch: BatchRequest, inputs, params, logits=None):
-        """The eager step of a batch in which some request carries a token mask (masked_rows) -> (sampled, scores).  The
-        same logits, then ONE hx_sample_rows_masked launch for the whole batch, modelled on _sample_scored: the
-        four-element entries of the constrained mode, want = -1 on every row but those of the processed-logprobs requests
-        that deliver a token, mask_row = -1 on every row without a mask (a chunk head's discarded sample included); rows on
-        the same trie node share one mask of the step.  The tables, `want`, `mask_row` and the step's distinct masks reach
-        the device as one pinned buffer in one copy.  With no processed request in the batch the launch is unscored and
-        only the ids come back.  RAW-mode logprobs requests beside them keep hx_logprob_rows over the raw logits."""
-        rows = sampling_rows(batch)
-        geometry = sel, decode, n_rows = self._step_rows(inputs, logits)
-        entries, at = self._step_entries(batch, sel, decode, n_rows, 4)
-        entries = [e + (-1, None) for e in entries]
-        top_k, raw = None, []                   # the processed requests' K (None: nobody asks); the raw-mode requests' top_logprobs
+        extra = [(-1, None)] * n_rows           # (want, mask) per logits row
+        top_k, raw = None if masked else 0, []  # the processed requests' K (None: nobody asks); the raw-mode requests' top_logprobs
         for row, (rcb, inst) in zip(at, rows):
             if inst.is_chunked:
                 continue
@@ -576,18 +529,28 @@ class BatchFillExecutor:
                 want, top_k = 0, max(top_k or 0, sp.top_logprobs)
             elif sp.logprobs:
                 raw.append(sp.top_logprobs)
-            entries[row] = entries[row][:4] + (want, mask.current() if mask is not None else None)
-        *tables, want = pack_masked_step(entries).to_device(self.device)
-        if logits is None:
-            logits = self.language_model.forward_logits(inputs.input_ids, inputs.image_features, inputs.position_ids, params)
-        if raw:
-            raw_packed = self._raw_scores(logits, max(raw))
-        if top_k is None:
-            sampled, scores = sample_rows_masked(logits, *tables).tolist(), None
+            extra[row] = (want, mask.current() if mask is not None else None)
+        if masked:
+            kernel, step = sample_rows_masked, pack_masked_step([e + x for e, x in zip(entries, extra)])
+        else:
+            kernel, step = sample_rows_logprobs, pack_scored_step([e + x[:1] for e, x in zip(entries, extra)])
+        *tables, want = step.to_device(self.device)
+        lm, ids = self.language_model, None
+        if not masked and not raw and logits is None:
+            ids = lm.forward_scored(inputs.input_ids, inputs.image_features, inputs.position_ids, params, *tables,
+                                    top_k=top_k, want=want)[0]
+        else:
+            if logits is None:
+                logits = lm.forward_logits(inputs.input_ids, inputs.image_features, inputs.position_ids, params)
+            if raw:
+                raw_packed = self._raw_scores(logits, max(raw))
+            if top_k is not None:
+                ids = kernel(logits, *tables, top_k=top_k, want=want)[0]
+        if ids is None:                         # a masked step whose requests ask for no processed scores: ids only
+            sampled, scores = kernel(logits, *tables).tolist(), None
             if raw:
                 scores = [[float("nan")] * n_rows, [[]] * n_rows, [[]] * n_rows]
         else:
-            ids = sample_rows_masked(logits, *tables, top_k=top_k, want=want)[0]
             sampled, *scores = self._to_host(logprob_rows_packed(ids, top_k), n_rows, top_k)
         if raw:
             raw_scores = self._to_host(raw_packed, n_rows, max(raw))[1:]
@@ -603,7 +566,7 @@ class BatchFillExecutor:
         argmax — the language model's own when it runs the forward, the step's only device sync."""
         rows = sampling_rows(batch)
         if masked_rows(rows):
-            return self._sample_masked(batch, inputs, params, logits)
+            return self._sample_scored(batch, inputs, params, logits, masked=True)
         if scored_rows(rows):
             return self._sample_scored(batch, inputs, params, logits)
         mode, top_k = step_mode(rows)

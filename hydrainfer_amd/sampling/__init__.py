@@ -18,21 +18,29 @@ frequency / presence penalties are defined over the sampled text as well.  The f
 empty history.  `PenaltyHistory` is that table on the host, `pack_penalty_step` turns a step's tables into the kernel's
 CSR, `pack_sample_step` does the same with the rows' sampling records in front — one buffer, one host-to-device copy.
 
+The step layouts are ONE chain, each the one before it with sections added: PenaltyStep [cu_hist | penalties | hist_ids |
+hist_counts], SampleStep [records] in front of that, ConstrainedStep + [cu_bias | bias_ids | bias_values], ScoredStep +
+[want], MaskedStep + [mask_row | masks].  A class states its own sections once (`sections()`), `views` is one cursor walk
+over them, and a packer allocates its step's buffer once and has every level write its sections in place — a step's
+buffer starts with the inner step's buffer, word for word.  The kernel wrappers share one launch path the same way:
+`_sample_arguments` checks and marshals what the hx_sample_rows* entries have in common, `_scored_output` the packed
+scores, `_check_tensor` every table; a wrapper is its own checks and one `_launch`.
+
 Token constraints (`logit_bias`, `min_tokens`, `min_p`): `sample_rows_constrained` (hx_sample_rows_constrained) is
 `sample_rows` with a per-row (token, bias) table added ahead of the penalties and a min_p cut; `TokenConstraints` is a
 request's table on the host (min_tokens: its end-of-sequence ids banned while too few tokens stand), and
-`pack_constrained_step` appends the step's bias CSR to `pack_sample_step`'s buffer.
+`pack_constrained_step` puts the step's bias CSR behind `pack_sample_step`'s layout.
 
 Scores of the processed distribution (`logprobs_mode = "processed_logprobs"`): `sample_rows_logprobs`
 (hx_sample_rows_logprobs) is `sample_rows_constrained` that also writes, for the rows that want it, the log-probability
 of the chosen token under the distribution it was chosen from and the K most likely alternatives of that distribution,
-in `logprob_rows`' packed layout.
+in `logprob_rows`' packed layout; `pack_scored_step` puts `want`, the rows' wish to be scored, behind the constrained layout.
 
 Token masks (`allowed_token_ids`, `guided_choice`): `sample_rows_masked` (hx_sample_rows_masked) is the scored launch with
 a per-row bitmask of the tokens a row may choose — 32 tokens per int32 word, 1 = allowed, the format grammar engines
 exchange — applied as -inf ahead of everything else; `TokenMask` holds a request's masks (one node, or a trie over its
-choices' token sequences) and where it stands, and `pack_masked_step` appends `want`, the rows' mask indices and the step's
-distinct masks to `pack_constrained_step`'s buffer.
+choices' token sequences) and where it stands, and `pack_masked_step` puts the rows' mask indices and the step's distinct
+masks behind `pack_scored_step`'s layout.
 
 Sampled decoding from a captured decode step: `sample_rows_resident` (hx_sample_rows_resident) is `sample_rows` without a
 history whose records stay on the device — `pack_resident_records` writes `n_out - position` where the offset stood, the
@@ -59,6 +67,100 @@ SAMPLE_LOG_MAX = 4096           # the longest row of a resident token log (HX_SA
 PENALTY_RECORD_WORDS = 4        # a row's penalty record: [frequency, presence, repetition (fp32 bits), log slot]
 
 
+# ---- the one launch path: what the seven wrappers check and marshal alike ----
+def _check_tensor(what: str, name: str, t: Tensor, dtype, shape, device=None) -> None:
+    """A table argument: a contiguous tensor of this dtype and shape (on `device`, where one is given)."""
+    if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or (device is not None and t.device != device):
+        kind = "fp32" if dtype == torch.float32 and device is None else str(dtype)[6:]     # (the messages as they always read)
+        raise _lib.HydraHipError(f"{what}: {name} must be a contiguous {kind} tensor of shape {list(shape)}"
+                                 + (" on the logits' device" if device is not None else ""))
+
+
+def _check_logits(what: str, logits: Tensor, max_n: int) -> int:
+    """fp16 / bf16 [rows, n] with contiguous rows, n at most what the kernel's LDS holds -> rows."""
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.dtype not in (torch.float16, torch.bfloat16) \
+            or logits.shape[0] < 1 or not 1 <= logits.shape[1] <= max_n or logits.stride(0) < logits.shape[1]:
+        raise _lib.HydraHipError(f"{what}: logits must be fp16 / bf16 [rows, n] (rows >= 1, 1 <= n <= {max_n}) "
+                                 "with contiguous rows")
+    return logits.shape[0]
+
+
+def _check_history(what: str, rows: int, hist_ids, hist_counts, cu_hist, penalties) -> int:
+    """The rows' (token, count) CSR and their penalties -> total."""
+    total = hist_ids.numel()
+    for name, t, n in (("hist_ids", hist_ids, total), ("hist_counts", hist_counts, total), ("cu_hist", cu_hist, rows + 1)):
+        _check_tensor(what, name, t, torch.int32, (n,))
+    _check_tensor(what, "penalties", penalties, torch.float32, (rows, 3))
+    return total
+
+
+def _ids_out(what: str, logits: Tensor, out: Optional[Tensor]) -> Tensor:
+    """`out` checked, or a new int64 [rows] on the logits' device."""
+    rows = logits.shape[0]
+    if out is None:
+        return torch.empty(rows, dtype=torch.int64, device=logits.device)
+    if out.dtype != torch.int64 or out.shape != (rows,) or not out.is_contiguous() or out.device != logits.device:
+        raise _lib.HydraHipError(f"{what}: out must be a contiguous int64 [rows] tensor on the logits' device")
+    return out
+
+
+def _ptr(t: Optional[Tensor], read=True):
+    """The address the C entry gets: None for a tensor that is not given, or for a table the launch does not read."""
+    return t.data_ptr() if t is not None and read else None
+
+
+def _launch(what: str, logits: Tensor, ids: Tensor, *args) -> Tensor:
+    """The C entry of the wrapper's own name, hx_<what>(ids, *args, dtype, stream) -> ids."""
+    _lib.check(getattr(_lib.lib(), "hx_" + what)(ids.data_ptr(), *args, _lib.dtype_code(logits), _lib.current_stream()), what)
+    return ids
+
+
+def _sample_arguments(what: str, logits, sample_params, history, bias, out, cut_out, u_out, ids_in_packed: bool = False):
+    """What the hx_sample_rows* entries share, checked and marshalled -> (rows, out, args): args are the entry's arguments
+    between the ids and its own tail — cut, u, the logits' geometry, the history CSR with `total`, the bias CSR with
+    `bias_total`, the records.  history: None (the entry takes none) or (hist_ids, hist_counts, cu_hist, penalties), all
+    given or all None; bias: None (the entry takes none) or (bias_ids, bias_values, cu_bias).  ids_in_packed: the ids go
+    into the caller's packed buffer (`_scored_output`): no `out` is checked or made."""
+    rows = _check_logits(what, logits, SAMPLE_MAX_N)
+    _check_tensor(what, "sample_params", sample_params, torch.int32, (rows, SAMPLE_RECORD_WORDS))
+    args = [_ptr(cut_out), _ptr(u_out), logits.data_ptr(), rows, logits.shape[1], logits.stride(0)]
+    if history is not None:
+        total = 0
+        if any(t is not None for t in history):
+            if any(t is None for t in history):
+                raise _lib.HydraHipError(f"{what}: hist_ids, hist_counts, cu_hist and penalties come together or not at all")
+            total = _check_history(what, rows, *history)
+        hist_ids, hist_counts, cu_hist, penalties = history
+        args += [_ptr(hist_ids, total), _ptr(hist_counts, total), _ptr(cu_hist, total), total, _ptr(penalties, total)]
+    if not ids_in_packed:
+        out = _ids_out(what, logits, out)
+    for name, t in (("cut_out", cut_out), ("u_out", u_out)):
+        if t is not None:
+            _check_tensor(what, name, t, torch.float32, (rows,))
+    if bias is not None:
+        bias_ids, bias_values, cu_bias = bias
+        bias_total = bias_ids.numel()
+        for name, t, dtype, n in (("bias_ids", bias_ids, torch.int32, bias_total), ("bias_values", bias_values, torch.float32, bias_total),
+                                  ("cu_bias", cu_bias, torch.int32, rows + 1)):
+            _check_tensor(what, name, t, dtype, (n,), logits.device)
+        args += [_ptr(bias_ids, bias_total), _ptr(bias_values, bias_total), _ptr(cu_bias, bias_total), bias_total]
+    return rows, out, args + [sample_params.data_ptr()]
+
+
+def _scored_output(what: str, logits: Tensor, rows: int, top_k, out: Optional[Tensor]):
+    """The scored launches' output block -> (views, args): top_k checked, `out` (or a new buffer) cut into logprob_rows'
+    four views, and the entry's arguments (logprobs, top_ids, top_logprobs, top_k) — the ids are views[0]."""
+    from hydrainfer_amd._C.kernel.norm import LOGPROB_MAX_TOP_K, logprob_rows_bytes, logprob_rows_views
+    if not isinstance(top_k, int) or isinstance(top_k, bool) or not 0 <= top_k <= LOGPROB_MAX_TOP_K:
+        raise _lib.HydraHipError(f"{what}: top_k {top_k!r} outside 0..{LOGPROB_MAX_TOP_K}")
+    if out is None:
+        out = torch.empty(logprob_rows_bytes(rows, top_k), dtype=torch.uint8, device=logits.device)
+    elif out.device != logits.device or out.data_ptr() % 8:
+        raise _lib.HydraHipError(f"{what}: out must be an 8-byte aligned buffer on the logits' device")
+    views = logprob_rows_views(out, rows, top_k)
+    return views, [views[1].data_ptr(), _ptr(views[2], top_k), _ptr(views[3], top_k), top_k]
+
+
 def penalized_argmax_rows(logits: Tensor, hist_ids: Tensor, hist_counts: Tensor, cu_hist: Tensor, penalties: Tensor,
                           out: Optional[Tensor] = None, scores_out: Optional[Tensor] = None) -> Tensor:
     """Greedy ids of fp16 / bf16 logits [rows, n] under per-row penalties, one launch (include/hydra_hip.h:
@@ -67,29 +169,14 @@ def penalized_argmax_rows(logits: Tensor, hist_ids: Tensor, hist_counts: Tensor,
     repetition).  Returns int64 [rows] (`out` if given); a row with an empty table gives argmax_rows' id.  scores_out:
     an fp32 [total] tensor that receives the penalised value of every table entry (NaN for an id outside the row)."""
     _lib.require_gpu(logits, hist_ids, hist_counts, cu_hist, penalties, out, scores_out)
-    if logits.dim() != 2 or logits.stride(1) != 1 or logits.dtype not in (torch.float16, torch.bfloat16) \
-            or logits.shape[0] < 1 or not 1 <= logits.shape[1] <= MAX_VOCAB or logits.stride(0) < logits.shape[1]:
-        raise _lib.HydraHipError(f"penalized_argmax_rows: logits must be fp16 / bf16 [rows, n] (rows >= 1, 1 <= n <= {MAX_VOCAB}) "
-                                 "with contiguous rows")
-    rows, total = logits.shape[0], hist_ids.numel()
-    for name, t, shape in (("hist_ids", hist_ids, (total,)), ("hist_counts", hist_counts, (total,)), ("cu_hist", cu_hist, (rows + 1,))):
-        if t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous():
-            raise _lib.HydraHipError(f"penalized_argmax_rows: {name} must be a contiguous int32 tensor of shape {list(shape)}")
-    if penalties.dtype != torch.float32 or tuple(penalties.shape) != (rows, 3) or not penalties.is_contiguous():
-        raise _lib.HydraHipError(f"penalized_argmax_rows: penalties must be a contiguous fp32 tensor of shape [{rows}, 3]")
-    if out is None:
-        out = torch.empty(rows, dtype=torch.int64, device=logits.device)
-    elif out.dtype != torch.int64 or out.shape != (rows,) or not out.is_contiguous() or out.device != logits.device:
-        raise _lib.HydraHipError("penalized_argmax_rows: out must be a contiguous int64 [rows] tensor on the logits' device")
-    if scores_out is not None and (scores_out.dtype != torch.float32 or tuple(scores_out.shape) != (total,)
-                                   or not scores_out.is_contiguous()):
-        raise _lib.HydraHipError(f"penalized_argmax_rows: scores_out must be a contiguous fp32 tensor of shape [{total}]")
-    _lib.check(_lib.lib().hx_penalized_argmax_rows(
-        out.data_ptr(), scores_out.data_ptr() if scores_out is not None and total else None, logits.data_ptr(), rows,
-        logits.shape[1], logits.stride(0), hist_ids.data_ptr() if total else None, hist_counts.data_ptr() if total else None,
-        cu_hist.data_ptr(), total, penalties.data_ptr(), _lib.dtype_code(logits), _lib.current_stream()),
-        "penalized_argmax_rows")
-    return out
+    what = "penalized_argmax_rows"
+    rows = _check_logits(what, logits, MAX_VOCAB)
+    total = _check_history(what, rows, hist_ids, hist_counts, cu_hist, penalties)
+    out = _ids_out(what, logits, out)
+    if scores_out is not None:
+        _check_tensor(what, "scores_out", scores_out, torch.float32, (total,))
+    return _launch(what, logits, out, _ptr(scores_out, total), logits.data_ptr(), rows, logits.shape[1], logits.stride(0),
+                   _ptr(hist_ids, total), _ptr(hist_counts, total), cu_hist.data_ptr(), total, penalties.data_ptr())
 
 
 def check_penalties(frequency_penalty, presence_penalty, repetition_penalty) -> Tuple[float, float, float]:
@@ -135,9 +222,32 @@ class PenaltyHistory:
         return len(self.ids)
 
 
+# ---- the step layouts: penalty < sample < constrained < scored < masked, each the one before it with sections added ----
 class _PackedStep:
-    """A step's tables as one int32 host `buffer`, which the subclass's `views` cuts into a kernel's arguments."""
+    """A step's tables as one int32 host `buffer` and the sizes that fix its layout.  `sections()` is that layout, stated
+    once: (name, dtype to view as, shape) per section in buffer order, every element one 32-bit word.  `views` walks it
+    with one cursor and hands the sections out in `ORDER`, the order of the kernel wrapper's arguments."""
     __slots__ = ()
+    ORDER = ()
+
+    def __init__(self, buffer: Optional[np.ndarray], *sizes: int):
+        for name, value in zip(self.__slots__, (buffer,) + sizes, strict=True):
+            setattr(self, name, value)
+
+    def views(self, t: Optional[Tensor] = None):
+        """The sections, in `ORDER`, inside `t`, a tensor holding the buffer on the host or on the device (default: the
+        host buffer itself).  Every one is an alias of `t`."""
+        if t is None:
+            t = torch.from_numpy(self.buffer)
+        cut, at = {}, 0
+        for name, dtype, shape in self.sections():
+            words = math.prod(shape)
+            v = t[at:at + words]
+            if dtype != torch.int32:            # (no tensor operation that changes nothing: a step pays for each)
+                v = v.view(dtype)
+            cut[name] = v if len(shape) == 1 else v.view(shape)
+            at += words
+        return tuple(cut[name] for name in self.ORDER)
 
     def to_device(self, device):
         """`views` on `device`: the buffer goes through pinned memory in ONE host-to-device copy."""
@@ -148,75 +258,161 @@ class _PackedStep:
 
 
 class PenaltyStep(_PackedStep):
-    """A step's packed tables: one int32 host buffer [cu_hist (rows + 1) | penalties (3 rows, fp32 bits) | hist_ids
-    (total) | hist_counts (total)] — `views` cuts it (on the host or on the device) into the kernel's four arguments."""
+    """[cu_hist (rows + 1) | penalties (3 rows, fp32 bits) | hist_ids (total) | hist_counts (total)]: `views` gives
+    penalized_argmax_rows' four table arguments."""
     __slots__ = ("buffer", "rows", "total")
+    ORDER = ("hist_ids", "hist_counts", "cu_hist", "penalties")
 
-    def __init__(self, buffer: np.ndarray, rows: int, total: int):
-        self.buffer, self.rows, self.total = buffer, rows, total
+    def sections(self):
+        return [("cu_hist", torch.int32, (self.rows + 1,)), ("penalties", torch.float32, (self.rows, 3)),
+                ("hist_ids", torch.int32, (self.total,)), ("hist_counts", torch.int32, (self.total,))]
 
-    def views(self, t: Optional[Tensor] = None):
-        """(hist_ids, hist_counts, cu_hist, penalties) inside `t`, a tensor holding the buffer (default: a host copy)."""
-        if t is None:
-            t = torch.from_numpy(self.buffer)
-        a, b = self.rows + 1, 4 * self.rows + 1
-        return (t[b:b + self.total], t[b + self.total:b + 2 * self.total], t[:a],
-                t[a:b].view(torch.float32).view(self.rows, 3))
+
+class SampleStep(_PackedStep):
+    """[records (8 rows)] in front of PenaltyStep's layout (8-byte aligned: the seeds are 64-bit): `views` gives
+    sample_rows' five table arguments."""
+    __slots__ = ("buffer", "rows", "total")
+    ORDER = ("sample_params",) + PenaltyStep.ORDER
+
+    def sections(self):
+        return [("sample_params", torch.int32, (self.rows, SAMPLE_RECORD_WORDS))] + PenaltyStep.sections(self)
+
+
+class ConstrainedStep(_PackedStep):
+    """SampleStep's layout, then [cu_bias (rows + 1) | bias_ids (bias_total) | bias_values (bias_total, fp32 bits)]: `views`
+    gives sample_rows_constrained's eight table arguments."""
+    __slots__ = ("buffer", "rows", "total", "bias_total")
+    ORDER = ("sample_params", "bias_ids", "bias_values", "cu_bias") + PenaltyStep.ORDER
+
+    def sections(self):
+        return SampleStep.sections(self) + [("cu_bias", torch.int32, (self.rows + 1,)), ("bias_ids", torch.int32, (self.bias_total,)),
+                                            ("bias_values", torch.float32, (self.bias_total,))]
+
+
+class ScoredStep(_PackedStep):
+    """ConstrainedStep's layout, then [want (rows)]: `views` gives sample_rows_logprobs' eight table arguments, then `want`."""
+    __slots__ = ConstrainedStep.__slots__
+    ORDER = ConstrainedStep.ORDER + ("want",)
+
+    def sections(self):
+        return ConstrainedStep.sections(self) + [("want", torch.int32, (self.rows,))]
+
+
+class MaskedStep(_PackedStep):
+    """ScoredStep's layout, then [mask_row (rows) | the step's distinct masks (n_masks * words)]: `views` gives
+    sample_rows_masked's ten table arguments, in its order, then `want`."""
+    __slots__ = ScoredStep.__slots__ + ("n_masks", "words")
+    ORDER = ("sample_params", "bias_ids", "bias_values", "cu_bias", "allow_words", "mask_row") + PenaltyStep.ORDER + ("want",)
+
+    def sections(self):
+        return ScoredStep.sections(self) + [("mask_row", torch.int32, (self.rows,)),
+                                            ("allow_words", torch.int32, (self.n_masks, self.words))]
+
+
+# The packers.  A public packer allocates its step's buffer once; the private ones take `tail`, the words the caller's
+# own sections need behind theirs, allocate (the innermost) or pass it down, write their sections in place and return
+# (buffer, where their layout ends, the sizes so far).  Entries longer than a level reads pass through it untouched.
+def _pack_penalty(entries, front: int, tail: int):
+    rows = len(entries)
+    lens = [len(e[0]) if e[0] is not None else 0 for e in entries]
+    total = sum(lens)
+    at = front + 4 * rows + 1
+    buf = np.zeros(at + 2 * total + tail, dtype=np.int32)
+    np.cumsum(lens, out=buf[front + 1:front + rows + 1])
+    buf[front + rows + 1:at] = np.asarray([e[1] for e in entries], dtype=np.float32).reshape(-1).view(np.int32)
+    for e, n in zip(entries, lens):
+        if n:
+            buf[at:at + n] = np.frombuffer(e[0].ids, dtype=np.int32)
+            buf[at + total:at + total + n] = np.frombuffer(e[0].counts, dtype=np.int32)
+            at += n
+    return buf, at + total, total
+
+
+def _pack_sample(entries, tail: int):
+    rows = len(entries)
+    r = SAMPLE_RECORD_WORDS * rows
+    buf, end, total = _pack_penalty(entries, r, tail)
+    pack_sample_records([e[2] for e in entries], buf[:r].reshape(rows, SAMPLE_RECORD_WORDS))
+    return buf, end, total
+
+
+def _pack_constrained(entries, tail: int):
+    rows = len(entries)
+    lens = [len(e[3][0]) if e[3] is not None else 0 for e in entries]
+    bias_total = sum(lens)
+    buf, c, total = _pack_sample(entries, rows + 1 + 2 * bias_total + tail)
+    np.cumsum(lens, out=buf[c + 1:c + rows + 1])
+    at = c + rows + 1
+    for e, n in zip(entries, lens):
+        if n:
+            buf[at:at + n] = np.asarray(e[3][0], dtype=np.int32)
+            buf[at + bias_total:at + bias_total + n] = np.asarray(e[3][1], dtype=np.float32).view(np.int32)
+            at += n
+    return buf, at + bias_total, total, bias_total
+
+
+def _pack_scored(entries, tail: int):
+    rows = len(entries)
+    buf, c, total, bias_total = _pack_constrained(entries, rows + tail)
+    buf[c:c + rows] = [e[4] for e in entries]
+    return buf, c + rows, total, bias_total
 
 
 def pack_penalty_step(entries) -> PenaltyStep:
     """entries: one (PenaltyHistory or None, (frequency, presence, repetition)) per logits row, in row order.  None or
     an empty history: the row is plain argmax (its penalties travel all the same)."""
+    buf, _, total = _pack_penalty(entries, 0, 0)
+    return PenaltyStep(buf, len(entries), total)
+
+
+def pack_sample_step(entries) -> SampleStep:
+    """entries: one (PenaltyHistory or None, (frequency, presence, repetition), (temperature, top_p, top_k, seed,
+    offset)) per logits row, in row order."""
+    buf, _, total = _pack_sample(entries, 0)
+    return SampleStep(buf, len(entries), total)
+
+
+def pack_constrained_step(entries) -> ConstrainedStep:
+    """entries: one (PenaltyHistory or None, (frequency, presence, repetition), record, bias) per logits row, in row
+    order — record: (temperature, top_p, top_k, seed, offset[, min_p]); bias: None or the (ids, values) arrays of
+    `TokenConstraints.step_entries`."""
+    buf, _, total, bias_total = _pack_constrained(entries, 0)
+    return ConstrainedStep(buf, len(entries), total, bias_total)
+
+
+def pack_scored_step(entries) -> ScoredStep:
+    """entries: one (PenaltyHistory or None, (frequency, presence, repetition), record, bias, want) per logits row, in row
+    order — the first four as in `pack_constrained_step`; want: < 0 for a row that is not scored."""
+    buf, _, total, bias_total = _pack_scored(entries, 0)
+    return ScoredStep(buf, len(entries), total, bias_total)
+
+
+def pack_masked_step(entries) -> MaskedStep:
+    """entries: one (PenaltyHistory or None, (frequency, presence, repetition), record, bias, want, mask) per logits row,
+    in row order — the first five as in `pack_scored_step`; mask: None or the words of `TokenMask.current()`.  Rows that
+    hand in the SAME array (two requests on one node, one request's node step after step) share one mask of the step:
+    masks are told apart by identity, not by content."""
     rows = len(entries)
-    lens = [len(h) if h is not None else 0 for h, _ in entries]
-    total = sum(lens)
-    buf = np.zeros(4 * rows + 1 + 2 * total, dtype=np.int32)
-    np.cumsum(lens, out=buf[1:rows + 1])
-    buf[rows + 1:4 * rows + 1] = np.asarray([p for _, p in entries], dtype=np.float32).reshape(-1).view(np.int32)
-    at = 4 * rows + 1
-    for (h, _), n in zip(entries, lens):
-        if n:
-            buf[at:at + n] = np.frombuffer(h.ids, dtype=np.int32)
-            buf[at + total:at + total + n] = np.frombuffer(h.counts, dtype=np.int32)
-            at += n
-    return PenaltyStep(buf, rows, total)
-
-
-def _check_sample_arguments(what: str, logits, sample_params, hist_ids, hist_counts, cu_hist, penalties, out, cut_out, u_out,
-                            ids_in_packed: bool = False):
-    """The argument checks sample_rows, sample_rows_constrained and sample_rows_logprobs share -> (rows, total, out).
-    ids_in_packed: the ids go into the caller's packed buffer (sample_rows_logprobs): no `out` is checked or made."""
-    if logits.dim() != 2 or logits.stride(1) != 1 or logits.dtype not in (torch.float16, torch.bfloat16) \
-            or logits.shape[0] < 1 or not 1 <= logits.shape[1] <= SAMPLE_MAX_N or logits.stride(0) < logits.shape[1]:
-        raise _lib.HydraHipError(f"{what}: logits must be fp16 / bf16 [rows, n] (rows >= 1, 1 <= n <= {SAMPLE_MAX_N}) "
-                                 "with contiguous rows")
-    rows = logits.shape[0]
-    if sample_params.dtype != torch.int32 or tuple(sample_params.shape) != (rows, SAMPLE_RECORD_WORDS) \
-            or not sample_params.is_contiguous():
-        raise _lib.HydraHipError(f"{what}: sample_params must be a contiguous int32 tensor of shape "
-                                 f"[{rows}, {SAMPLE_RECORD_WORDS}]")
-    tables = (hist_ids, hist_counts, cu_hist, penalties)
-    total = 0
-    if any(t is not None for t in tables):
-        if any(t is None for t in tables):
-            raise _lib.HydraHipError(f"{what}: hist_ids, hist_counts, cu_hist and penalties come together or not at all")
-        total = hist_ids.numel()
-        for name, t, shape in (("hist_ids", hist_ids, (total,)), ("hist_counts", hist_counts, (total,)),
-                               ("cu_hist", cu_hist, (rows + 1,))):
-            if t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous():
-                raise _lib.HydraHipError(f"{what}: {name} must be a contiguous int32 tensor of shape {list(shape)}")
-        if penalties.dtype != torch.float32 or tuple(penalties.shape) != (rows, 3) or not penalties.is_contiguous():
-            raise _lib.HydraHipError(f"{what}: penalties must be a contiguous fp32 tensor of shape [{rows}, 3]")
-    if ids_in_packed:
-        pass
-    elif out is None:
-        out = torch.empty(rows, dtype=torch.int64, device=logits.device)
-    elif out.dtype != torch.int64 or out.shape != (rows,) or not out.is_contiguous() or out.device != logits.device:
-        raise _lib.HydraHipError(f"{what}: out must be a contiguous int64 [rows] tensor on the logits' device")
-    for name, t in (("cut_out", cut_out), ("u_out", u_out)):
-        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (rows,) or not t.is_contiguous()):
-            raise _lib.HydraHipError(f"{what}: {name} must be a contiguous fp32 tensor of shape [{rows}]")
-    return rows, total, out
+    slot, masks = {}, []
+    mask_row = np.full(rows, -1, dtype=np.int32)
+    for r, e in enumerate(entries):
+        mask = e[5]
+        if mask is not None:
+            j = slot.get(id(mask))
+            if j is None:
+                j = slot[id(mask)] = len(masks)
+                masks.append(mask)
+            mask_row[r] = j
+    words = len(masks[0]) if masks else 0
+    if any(len(m) != words for m in masks):
+        raise ValueError("pack_masked_step: the step's masks differ in width")
+    buf, at, total, bias_total = _pack_scored(entries, rows + len(masks) * words)
+    buf[at:at + rows] = mask_row
+    at += rows
+    for m in masks:
+        buf[at:at + words] = np.asarray(m, dtype=np.uint32).view(np.int32)
+        at += words
+    return MaskedStep(buf, rows, total, bias_total, len(masks), words)
 
 
 def sample_rows(logits: Tensor, sample_params: Tensor, hist_ids: Optional[Tensor] = None,
@@ -230,14 +426,9 @@ def sample_rows(logits: Tensor, sample_params: Tensor, hist_ids: Optional[Tensor
     cut_out / u_out: fp32 [rows] tensors that receive each row's top-p cut v* (NaN for a greedy or degenerate row) and
     its uniform number u."""
     _lib.require_gpu(logits, sample_params, hist_ids, hist_counts, cu_hist, penalties, out, cut_out, u_out)
-    rows, total, out = _check_sample_arguments("sample_rows", logits, sample_params, hist_ids, hist_counts, cu_hist, penalties,
-                                               out, cut_out, u_out)
-    ptr = (lambda t: t.data_ptr()) if total else (lambda t: None)
-    _lib.check(_lib.lib().hx_sample_rows(
-        out.data_ptr(), cut_out.data_ptr() if cut_out is not None else None, u_out.data_ptr() if u_out is not None else None,
-        logits.data_ptr(), rows, logits.shape[1], logits.stride(0), ptr(hist_ids), ptr(hist_counts), ptr(cu_hist), total,
-        ptr(penalties), sample_params.data_ptr(), _lib.dtype_code(logits), _lib.current_stream()), "sample_rows")
-    return out
+    _, out, args = _sample_arguments("sample_rows", logits, sample_params, (hist_ids, hist_counts, cu_hist, penalties), None,
+                                     out, cut_out, u_out)
+    return _launch("sample_rows", logits, out, *args)
 
 
 def check_sampling(temperature, top_p, top_k, seed) -> Tuple[float, float, int, Optional[int]]:
@@ -262,18 +453,23 @@ def is_sampled(sampling_params) -> bool:
     return sampling_params.temperature > 0
 
 
-def pack_sample_records(records, out: Optional[np.ndarray] = None) -> np.ndarray:
-    """records: one (temperature, top_p, top_k, seed, offset) per logits row -> int32 [rows, 8], the layout of
-    include/hydra_hip.h (into `out` if given).  A sixth element is the row's min_p (word 3, fp32 bits: read by
-    hx_sample_rows_constrained only); a five-element record packs it as 0."""
+def _pack_records(records, out: Optional[np.ndarray], wide) -> np.ndarray:
+    """The body of pack_sample_records and pack_resident_records; wide: how words [4:8] read as two 64-bit numbers."""
     rows = len(records)
     if out is None:
         out = np.zeros((rows, SAMPLE_RECORD_WORDS), dtype=np.int32)
     out[:, :2] = np.asarray([(r[0], r[1]) for r in records], dtype=np.float32).reshape(rows, 2).view(np.int32)
     out[:, 2] = [r[2] for r in records]
     out[:, 3] = np.asarray([r[5] if len(r) > 5 else 0.0 for r in records], dtype=np.float32).view(np.int32)
-    out[:, 4:].view(np.uint64)[:] = np.asarray([(r[3], r[4]) for r in records], dtype=np.uint64).reshape(rows, 2)
+    out[:, 4:].view(wide)[:] = np.asarray([(r[3], r[4]) for r in records], dtype=wide).reshape(rows, 2)
     return out
+
+
+def pack_sample_records(records, out: Optional[np.ndarray] = None) -> np.ndarray:
+    """records: one (temperature, top_p, top_k, seed, offset) per logits row -> int32 [rows, 8], the layout of
+    include/hydra_hip.h (into `out` if given).  A sixth element is the row's min_p (word 3, fp32 bits: read by
+    hx_sample_rows_constrained only); a five-element record packs it as 0."""
+    return _pack_records(records, out, np.uint64)
 
 
 def pack_resident_records(records, out: Optional[np.ndarray] = None) -> np.ndarray:
@@ -281,17 +477,7 @@ def pack_resident_records(records, out: Optional[np.ndarray] = None) -> np.ndarr
     [rows, 8], the layout hx_sample_rows_resident reads (into `out` if given): `pack_sample_records`' with words [6] and
     [7] holding offset_base as a 64-bit two's-complement number — the row then draws with offset_base + its position,
     so a decode request's record is (.., n_out - position) for as long as it lives.  Word [3] is 0."""
-    rows = len(records)
-    if out is None:
-        out = np.zeros((rows, SAMPLE_RECORD_WORDS), dtype=np.int32)
-    recs = [GREEDY_RECORD if r is None else r for r in records]
-    out[:, :2] = np.asarray([(r[0], r[1]) for r in recs], dtype=np.float32).reshape(rows, 2).view(np.int32)
-    out[:, 2] = [r[2] for r in recs]
-    out[:, 3] = 0
-    wide = out[:, 4:].view(np.int64)
-    wide[:, 0] = [r[3] for r in recs]           # (a seed is at most 2^63 - 1)
-    wide[:, 1] = [r[4] for r in recs]
-    return out
+    return _pack_records([GREEDY_RECORD if r is None else r[:5] for r in records], out, np.int64)  # (a seed is at most 2^63 - 1)
 
 
 def sample_rows_resident(logits: Tensor, sample_params: Tensor, positions: Tensor, out: Optional[Tensor] = None,
@@ -302,15 +488,10 @@ def sample_rows_resident(logits: Tensor, sample_params: Tensor, positions: Tenso
     carries that offset, bit for bit.  Nothing here allocates when `out` is given: the launch a captured decode step
     ends in."""
     _lib.require_gpu(logits, sample_params, positions, out, cut_out, u_out)
-    rows, _, out = _check_sample_arguments("sample_rows_resident", logits, sample_params, None, None, None, None, out, cut_out,
-                                           u_out)
-    if positions.dtype != torch.int32 or tuple(positions.shape) != (rows,) or not positions.is_contiguous():
-        raise _lib.HydraHipError(f"sample_rows_resident: positions must be a contiguous int32 tensor of shape [{rows}]")
-    _lib.check(_lib.lib().hx_sample_rows_resident(
-        out.data_ptr(), cut_out.data_ptr() if cut_out is not None else None, u_out.data_ptr() if u_out is not None else None,
-        logits.data_ptr(), rows, logits.shape[1], logits.stride(0), sample_params.data_ptr(), positions.data_ptr(),
-        _lib.dtype_code(logits), _lib.current_stream()), "sample_rows_resident")
-    return out
+    what = "sample_rows_resident"
+    rows, out, args = _sample_arguments(what, logits, sample_params, None, None, out, cut_out, u_out)
+    _check_tensor(what, "positions", positions, torch.int32, (rows,))
+    return _launch(what, logits, out, *args, positions.data_ptr())
 
 
 def pack_penalty_records(rows, out: Optional[np.ndarray] = None) -> np.ndarray:
@@ -336,73 +517,20 @@ def sample_rows_resident_penalized(logits: Tensor, sample_params: Tensor, positi
     `sample_rows_resident`'s.  Nothing here allocates when `out` is given."""
     _lib.require_gpu(logits, sample_params, positions, penalty_params, token_log, out, cut_out, u_out)
     what = "sample_rows_resident_penalized"
-    rows, _, out = _check_sample_arguments(what, logits, sample_params, None, None, None, None, out, cut_out, u_out)
-    if positions.dtype != torch.int32 or tuple(positions.shape) != (rows,) or not positions.is_contiguous():
-        raise _lib.HydraHipError(f"{what}: positions must be a contiguous int32 tensor of shape [{rows}]")
-    if penalty_params.dtype != torch.int32 or tuple(penalty_params.shape) != (rows, PENALTY_RECORD_WORDS) \
-            or not penalty_params.is_contiguous():
-        raise _lib.HydraHipError(f"{what}: penalty_params must be a contiguous int32 tensor of shape "
-                                 f"[{rows}, {PENALTY_RECORD_WORDS}]")
+    rows, out, args = _sample_arguments(what, logits, sample_params, None, None, out, cut_out, u_out)
+    _check_tensor(what, "positions", positions, torch.int32, (rows,))
+    _check_tensor(what, "penalty_params", penalty_params, torch.int32, (rows, PENALTY_RECORD_WORDS))
     if token_log.dtype != torch.int32 or token_log.dim() != 2 or not token_log.is_contiguous() or token_log.shape[0] < 1 \
             or not 1 <= token_log.shape[1] <= SAMPLE_LOG_MAX:
         raise _lib.HydraHipError(f"{what}: token_log must be a contiguous int32 tensor [log_slots >= 1, 1 <= log_cap <= "
                                  f"{SAMPLE_LOG_MAX}]")
-    _lib.check(_lib.lib().hx_sample_rows_resident_penalized(
-        out.data_ptr(), cut_out.data_ptr() if cut_out is not None else None, u_out.data_ptr() if u_out is not None else None,
-        logits.data_ptr(), rows, logits.shape[1], logits.stride(0), sample_params.data_ptr(), positions.data_ptr(),
-        penalty_params.data_ptr(), token_log.data_ptr(), token_log.shape[0], token_log.shape[1], _lib.dtype_code(logits),
-        _lib.current_stream()), what)
-    return out
-
-
-class SampleStep(_PackedStep):
-    """A sampled step's packed tables: one int32 host buffer [records (8 rows) | cu_hist (rows + 1) | penalties (3 rows,
-    fp32 bits) | hist_ids (total) | hist_counts (total)] — `views` cuts it (on the host or on the device) into
-    sample_rows' five table arguments."""
-    __slots__ = ("buffer", "rows", "total")
-
-    def __init__(self, buffer: np.ndarray, rows: int, total: int):
-        self.buffer, self.rows, self.total = buffer, rows, total
-
-    def views(self, t: Optional[Tensor] = None):
-        """(sample_params, hist_ids, hist_counts, cu_hist, penalties) inside `t`, a tensor holding the buffer (default: a
-        host copy)."""
-        if t is None:
-            t = torch.from_numpy(self.buffer)
-        r = SAMPLE_RECORD_WORDS * self.rows
-        a, b = r + self.rows + 1, r + 4 * self.rows + 1
-        return (t[:r].view(self.rows, SAMPLE_RECORD_WORDS), t[b:b + self.total], t[b + self.total:b + 2 * self.total],
-                t[r:a], t[a:b].view(torch.float32).view(self.rows, 3))
-
-
-def pack_sample_step(entries) -> SampleStep:
-    """entries: one (PenaltyHistory or None, (frequency, presence, repetition), (temperature, top_p, top_k, seed,
-    offset)) per logits row, in row order.  The rows' records come first (8-byte aligned: the seeds are 64-bit), the
-    layout of `pack_penalty_step` follows."""
-    rows = len(entries)
-    tables = pack_penalty_step([(h, p) for h, p, _ in entries])
-    r = SAMPLE_RECORD_WORDS * rows
-    buf = np.empty(r + tables.buffer.size, dtype=np.int32)
-    pack_sample_records([rec for _, _, rec in entries], buf[:r].reshape(rows, SAMPLE_RECORD_WORDS))
-    buf[r:] = tables.buffer
-    return SampleStep(buf, rows, tables.total)
+    return _launch(what, logits, out, *args, positions.data_ptr(), penalty_params.data_ptr(), token_log.data_ptr(),
+                   token_log.shape[0], token_log.shape[1])
 
 
 # ---- token constraints: logit_bias, min_tokens, min_p (hx_sample_rows_constrained, include/hydra_hip.h) ----
 MAX_LOGIT_BIAS = 300            # entries of one request's logit_bias (OpenAI's limit)
 LOGIT_BIAS_RANGE = 100.0        # |bias| at most this (OpenAI's range)
-
-
-def _check_bias_arguments(what: str, logits, rows, bias_ids, bias_values, cu_bias) -> int:
-    """The checks of the bias CSR that sample_rows_constrained and sample_rows_logprobs share -> bias_total."""
-    bias_total = bias_ids.numel()
-    for name, t, dtype, shape in (("bias_ids", bias_ids, torch.int32, (bias_total,)),
-                                  ("bias_values", bias_values, torch.float32, (bias_total,)),
-                                  ("cu_bias", cu_bias, torch.int32, (rows + 1,))):
-        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != logits.device:
-            raise _lib.HydraHipError(f"{what}: {name} must be a contiguous {str(dtype)[6:]} tensor of shape "
-                                     f"{list(shape)} on the logits' device")
-    return bias_total
 
 
 def sample_rows_constrained(logits: Tensor, sample_params: Tensor, bias_ids: Tensor, bias_values: Tensor, cu_bias: Tensor,
@@ -417,17 +545,9 @@ def sample_rows_constrained(logits: Tensor, sample_params: Tensor, bias_ids: Ten
     `sample_rows`': a row with an empty table and min_p 0 gets its id, cut and u bit for bit."""
     _lib.require_gpu(logits, sample_params, bias_ids, bias_values, cu_bias, hist_ids, hist_counts, cu_hist, penalties, out,
                      cut_out, u_out)
-    rows, total, out = _check_sample_arguments("sample_rows_constrained", logits, sample_params, hist_ids, hist_counts, cu_hist,
-                                               penalties, out, cut_out, u_out)
-    bias_total = _check_bias_arguments("sample_rows_constrained", logits, rows, bias_ids, bias_values, cu_bias)
-    ptr = (lambda t: t.data_ptr()) if total else (lambda t: None)
-    bptr = (lambda t: t.data_ptr()) if bias_total else (lambda t: None)
-    _lib.check(_lib.lib().hx_sample_rows_constrained(
-        out.data_ptr(), cut_out.data_ptr() if cut_out is not None else None, u_out.data_ptr() if u_out is not None else None,
-        logits.data_ptr(), rows, logits.shape[1], logits.stride(0), ptr(hist_ids), ptr(hist_counts), ptr(cu_hist), total,
-        ptr(penalties), bptr(bias_ids), bptr(bias_values), bptr(cu_bias), bias_total, sample_params.data_ptr(),
-        _lib.dtype_code(logits), _lib.current_stream()), "sample_rows_constrained")
-    return out
+    _, out, args = _sample_arguments("sample_rows_constrained", logits, sample_params, (hist_ids, hist_counts, cu_hist, penalties),
+                                     (bias_ids, bias_values, cu_bias), out, cut_out, u_out)
+    return _launch("sample_rows_constrained", logits, out, *args)
 
 
 def sample_rows_logprobs(logits: Tensor, sample_params: Tensor, bias_ids: Tensor, bias_values: Tensor, cu_bias: Tensor,
@@ -444,32 +564,16 @@ def sample_rows_logprobs(logits: Tensor, sample_params: Tensor, bias_ids: Tensor
     want < 0 is not scored (NaN, -1, NaN) and costs what it costs in sample_rows_constrained.  The four results are views
     of one uint8 buffer with logprob_rows' layout (`out`, or a new one: logprob_rows_bytes / logprob_rows_views), which
     goes to the host in one copy (logprob_rows_packed)."""
-    from hydrainfer_amd._C.kernel.norm import LOGPROB_MAX_TOP_K, logprob_rows_bytes, logprob_rows_views
     _lib.require_gpu(logits, sample_params, bias_ids, bias_values, cu_bias, hist_ids, hist_counts, cu_hist, penalties, want,
                      out, cut_out, u_out)
     what = "sample_rows_logprobs"
-    if not isinstance(top_k, int) or isinstance(top_k, bool) or not 0 <= top_k <= LOGPROB_MAX_TOP_K:
-        raise _lib.HydraHipError(f"{what}: top_k {top_k!r} outside 0..{LOGPROB_MAX_TOP_K}")
-    rows, total, _ = _check_sample_arguments(what, logits, sample_params, hist_ids, hist_counts, cu_hist, penalties, None,
-                                             cut_out, u_out, ids_in_packed=True)
-    bias_total = _check_bias_arguments(what, logits, rows, bias_ids, bias_values, cu_bias)
-    if want is not None and (want.dtype != torch.int32 or tuple(want.shape) != (rows,) or not want.is_contiguous()
-                             or want.device != logits.device):
-        raise _lib.HydraHipError(f"{what}: want must be a contiguous int32 tensor of shape [{rows}] on the logits' device")
-    if out is None:
-        out = torch.empty(logprob_rows_bytes(rows, top_k), dtype=torch.uint8, device=logits.device)
-    elif out.device != logits.device or out.data_ptr() % 8:
-        raise _lib.HydraHipError(f"{what}: out must be an 8-byte aligned buffer on the logits' device")
-    ids, lp, top_ids, top_lp = logprob_rows_views(out, rows, top_k)
-    ptr = (lambda t: t.data_ptr()) if total else (lambda t: None)
-    bptr = (lambda t: t.data_ptr()) if bias_total else (lambda t: None)
-    _lib.check(_lib.lib().hx_sample_rows_logprobs(
-        ids.data_ptr(), cut_out.data_ptr() if cut_out is not None else None, u_out.data_ptr() if u_out is not None else None,
-        logits.data_ptr(), rows, logits.shape[1], logits.stride(0), ptr(hist_ids), ptr(hist_counts), ptr(cu_hist), total,
-        ptr(penalties), bptr(bias_ids), bptr(bias_values), bptr(cu_bias), bias_total, sample_params.data_ptr(),
-        lp.data_ptr(), top_ids.data_ptr() if top_k else None, top_lp.data_ptr() if top_k else None, top_k,
-        want.data_ptr() if want is not None else None, _lib.dtype_code(logits), _lib.current_stream()), what)
-    return ids, lp, top_ids, top_lp
+    rows, _, args = _sample_arguments(what, logits, sample_params, (hist_ids, hist_counts, cu_hist, penalties),
+                                      (bias_ids, bias_values, cu_bias), None, cut_out, u_out, ids_in_packed=True)
+    if want is not None:
+        _check_tensor(what, "want", want, torch.int32, (rows,), logits.device)
+    views, scored = _scored_output(what, logits, rows, top_k, out)
+    _launch(what, logits, views[0], *args, *scored, _ptr(want))
+    return views
 
 
 def check_constraints(logit_bias, min_tokens, min_p):
@@ -533,49 +637,6 @@ class TokenConstraints:
             self._held = (np.asarray([t for t, _ in items], dtype=np.int32),
                           np.asarray([b for _, b in items], dtype=np.float32))
         return self._held
-
-
-class ConstrainedStep(_PackedStep):
-    """A constrained step's packed tables: SampleStep's buffer with [cu_bias (rows + 1) | bias_ids (bias_total) |
-    bias_values (bias_total, fp32 bits)] appended — `views` cuts it (on the host or on the device) into
-    sample_rows_constrained's eight table arguments."""
-    __slots__ = ("buffer", "rows", "total", "bias_total")
-
-    def __init__(self, buffer: np.ndarray, rows: int, total: int, bias_total: int):
-        self.buffer, self.rows, self.total, self.bias_total = buffer, rows, total, bias_total
-
-    def views(self, t: Optional[Tensor] = None):
-        """(sample_params, bias_ids, bias_values, cu_bias, hist_ids, hist_counts, cu_hist, penalties) inside `t`, a tensor
-        holding the buffer (default: a host copy)."""
-        if t is None:
-            t = torch.from_numpy(self.buffer)
-        c = (SAMPLE_RECORD_WORDS + 4) * self.rows + 1 + 2 * self.total           # where SampleStep's layout ends
-        d = c + self.rows + 1
-        records, hist_ids, hist_counts, cu_hist, penalties = SampleStep(None, self.rows, self.total).views(t[:c])
-        return (records, t[d:d + self.bias_total], t[d + self.bias_total:d + 2 * self.bias_total].view(torch.float32),
-                t[c:d], hist_ids, hist_counts, cu_hist, penalties)
-
-
-def pack_constrained_step(entries) -> ConstrainedStep:
-    """entries: one (PenaltyHistory or None, (frequency, presence, repetition), record, bias) per logits row, in row
-    order — record: (temperature, top_p, top_k, seed, offset[, min_p]); bias: None or the (ids, values) arrays of
-    `TokenConstraints.step_entries`."""
-    rows = len(entries)
-    step = pack_sample_step([(h, p, rec) for h, p, rec, _ in entries])
-    lens = [len(b[0]) if b is not None else 0 for _, _, _, b in entries]
-    bias_total = sum(lens)
-    c = step.buffer.size
-    buf = np.empty(c + rows + 1 + 2 * bias_total, dtype=np.int32)
-    buf[:c] = step.buffer
-    buf[c] = 0
-    np.cumsum(lens, out=buf[c + 1:c + rows + 1])
-    at = c + rows + 1
-    for (_, _, _, b), n in zip(entries, lens):
-        if n:
-            buf[at:at + n] = np.asarray(b[0], dtype=np.int32)
-            buf[at + bias_total:at + bias_total + n] = np.asarray(b[1], dtype=np.float32).view(np.int32)
-            at += n
-    return ConstrainedStep(buf, rows, step.total, bias_total)
 
 
 # ---- token masks: allowed_token_ids, guided_choice (hx_sample_rows_masked, include/hydra_hip.h) ----
@@ -700,99 +761,25 @@ def sample_rows_masked(logits: Tensor, sample_params: Tensor, bias_ids: Tensor, 
     same row with -inf written into the logits at the tokens its mask leaves out; an unmasked row what it gives there.
     top_k None: unscored, returns ids int64 [rows] (`out` if given) as sample_rows_constrained does.  Otherwise
     sample_rows_logprobs' four views over the packed layout, `want` as there."""
-    from hydrainfer_amd._C.kernel.norm import LOGPROB_MAX_TOP_K, logprob_rows_bytes, logprob_rows_views
     _lib.require_gpu(logits, sample_params, bias_ids, bias_values, cu_bias, allow_words, mask_row, hist_ids, hist_counts,
                      cu_hist, penalties, want, out, cut_out, u_out)
     what = "sample_rows_masked"
     scored = top_k is not None
-    if scored and (not isinstance(top_k, int) or isinstance(top_k, bool) or not 0 <= top_k <= LOGPROB_MAX_TOP_K):
-        raise _lib.HydraHipError(f"{what}: top_k {top_k!r} outside 0..{LOGPROB_MAX_TOP_K}")
     if not scored and want is not None:
         raise _lib.HydraHipError(f"{what}: want comes with top_k (an unscored launch scores no row)")
-    rows, total, ids = _check_sample_arguments(what, logits, sample_params, hist_ids, hist_counts, cu_hist, penalties,
-                                               None if scored else out, cut_out, u_out, ids_in_packed=scored)
-    bias_total = _check_bias_arguments(what, logits, rows, bias_ids, bias_values, cu_bias)
+    rows, ids, args = _sample_arguments(what, logits, sample_params, (hist_ids, hist_counts, cu_hist, penalties),
+                                        (bias_ids, bias_values, cu_bias), None if scored else out, cut_out, u_out,
+                                        ids_in_packed=scored)
     words = mask_words(logits.shape[1])
     if allow_words.dtype not in (torch.int32, torch.uint32) or allow_words.dim() != 2 or not allow_words.is_contiguous() \
             or (allow_words.shape[0] > 0 and allow_words.shape[1] != words) or allow_words.device != logits.device:
         raise _lib.HydraHipError(f"{what}: allow_words must be a contiguous int32 / uint32 tensor of shape [n_masks, {words}] "
                                  "on the logits' device")
     n_masks = allow_words.shape[0]
-    for name, t in (("mask_row", mask_row), ("want", want)):
-        if (t is not None or name == "mask_row") and (t.dtype != torch.int32 or tuple(t.shape) != (rows,)
-                                                      or not t.is_contiguous() or t.device != logits.device):
-            raise _lib.HydraHipError(f"{what}: {name} must be a contiguous int32 tensor of shape [{rows}] on the logits' "
-                                     "device")
-    lp = top_ids = top_lp = None
-    if scored:
-        if out is None:
-            out = torch.empty(logprob_rows_bytes(rows, top_k), dtype=torch.uint8, device=logits.device)
-        elif out.device != logits.device or out.data_ptr() % 8:
-            raise _lib.HydraHipError(f"{what}: out must be an 8-byte aligned buffer on the logits' device")
-        ids, lp, top_ids, top_lp = logprob_rows_views(out, rows, top_k)
-    ptr = (lambda t: t.data_ptr()) if total else (lambda t: None)
-    bptr = (lambda t: t.data_ptr()) if bias_total else (lambda t: None)
-    _lib.check(_lib.lib().hx_sample_rows_masked(
-        ids.data_ptr(), cut_out.data_ptr() if cut_out is not None else None, u_out.data_ptr() if u_out is not None else None,
-        logits.data_ptr(), rows, logits.shape[1], logits.stride(0), ptr(hist_ids), ptr(hist_counts), ptr(cu_hist), total,
-        ptr(penalties), bptr(bias_ids), bptr(bias_values), bptr(cu_bias), bias_total, sample_params.data_ptr(),
-        lp.data_ptr() if scored else None, top_ids.data_ptr() if scored and top_k else None,
-        top_lp.data_ptr() if scored and top_k else None, top_k if scored else 0,
-        want.data_ptr() if want is not None else None, allow_words.data_ptr() if n_masks else None, n_masks,
-        mask_row.data_ptr(), _lib.dtype_code(logits), _lib.current_stream()), what)
-    return (ids, lp, top_ids, top_lp) if scored else ids
-
-
-class MaskedStep(_PackedStep):
-    """A masked step's packed tables: ConstrainedStep's buffer with [want (rows) | mask_row (rows) | the step's distinct
-    masks (n_masks * words)] appended — `views` cuts it (on the host or on the device) into sample_rows_masked's table
-    arguments, in its order, with `want` last."""
-    __slots__ = ("buffer", "rows", "total", "bias_total", "n_masks", "words")
-
-    def __init__(self, buffer: np.ndarray, rows: int, total: int, bias_total: int, n_masks: int, words: int):
-        self.buffer, self.rows, self.total, self.bias_total = buffer, rows, total, bias_total
-        self.n_masks, self.words = n_masks, words
-
-    def views(self, t: Optional[Tensor] = None):
-        """(sample_params, bias_ids, bias_values, cu_bias, allow_words, mask_row, hist_ids, hist_counts, cu_hist,
-        penalties, want) inside `t`, a tensor holding the buffer (default: a host copy)."""
-        if t is None:
-            t = torch.from_numpy(self.buffer)
-        e = t.numel() - 2 * self.rows - self.n_masks * self.words                # where ConstrainedStep's layout ends
-        records, bias_ids, bias_values, cu_bias, hist_ids, hist_counts, cu_hist, penalties = \
-            ConstrainedStep(None, self.rows, self.total, self.bias_total).views(t[:e])
-        m = e + 2 * self.rows
-        return (records, bias_ids, bias_values, cu_bias, t[m:].view(self.n_masks, self.words), t[e + self.rows:m],
-                hist_ids, hist_counts, cu_hist, penalties, t[e:e + self.rows])
-
-
-def pack_masked_step(entries) -> MaskedStep:
-    """entries: one (PenaltyHistory or None, (frequency, presence, repetition), record, bias, want, mask) per logits row,
-    in row order — the first four as in `pack_constrained_step`; want: < 0 for a row that is not scored; mask: None or
-    the words of `TokenMask.current()`.  Rows that hand in the SAME array (two requests on one node, one request's node
-    step after step) share one mask of the step: masks are told apart by identity, not by content."""
-    rows = len(entries)
-    step = pack_constrained_step([e[:4] for e in entries])
-    slot, masks = {}, []
-    mask_row = np.full(rows, -1, dtype=np.int32)
-    for r, e in enumerate(entries):
-        mask = e[5]
-        if mask is not None:
-            j = slot.get(id(mask))
-            if j is None:
-                j = slot[id(mask)] = len(masks)
-                masks.append(mask)
-            mask_row[r] = j
-    words = len(masks[0]) if masks else 0
-    if any(len(m) != words for m in masks):
-        raise ValueError("pack_masked_step: the step's masks differ in width")
-    c = step.buffer.size
-    buf = np.empty(c + 2 * rows + len(masks) * words, dtype=np.int32)
-    buf[:c] = step.buffer
-    buf[c:c + rows] = [e[4] for e in entries]
-    buf[c + rows:c + 2 * rows] = mask_row
-    at = c + 2 * rows
-    for m in masks:
-        buf[at:at + words] = np.asarray(m, dtype=np.uint32).view(np.int32)
-        at += words
-    return MaskedStep(buf, rows, step.total, step.bias_total, len(masks), words)
+    _check_tensor(what, "mask_row", mask_row, torch.int32, (rows,), logits.device)
+    if want is not None:
+        _check_tensor(what, "want", want, torch.int32, (rows,), logits.device)
+    views, tail = _scored_output(what, logits, rows, top_k, out) if scored else (None, [None, None, None, 0])
+    _launch(what, logits, views[0] if scored else ids, *args, *tail, _ptr(want), _ptr(allow_words, n_masks), n_masks,
+            mask_row.data_ptr())
+    return views if scored else ids

@@ -1,5 +1,5 @@
 """GPU: token masks through the engine (SamplingParameters.allowed_token_ids / guided_choice -> rcb.token_mask -> the eager
-step's _sample_masked -> hx_sample_rows_masked) on the tiny model of tests/engine_util.py: a masked request emits only
+step's _sample_scored -> hx_sample_rows_masked) on the tiny model of tests/engine_util.py: a masked request emits only
 what its mask allows, a guided_choice request exactly one of its choices and ends there, the requests beside them keep the
 tokens of a run without masks, and a seeded masked request replays."""
 import pytest

@@ -1,6 +1,6 @@
 """CPU: the host side of token masks (allowed_token_ids, guided_choice) — the bit layout of pack_mask_words against a
 plain Python loop (tests/mask_ref.py), TokenMask's trie, every refusal of check_token_mask and of admission, the step
-packer against pack_constrained_step, the executor's masked_rows / _choose / _sample_masked with the kernels patched by
+packer against pack_constrained_step, the executor's masked_rows / _choose / _sample_scored with the kernels patched by
 name, the API parser, and the C ABI binding."""
 import os
 from types import SimpleNamespace as NS
