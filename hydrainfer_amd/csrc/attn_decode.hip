@@ -154,16 +154,6 @@ __device__ __forceinline__ void load_tile_b(KVTile<D>& buf, const AttnParams& p,
   }
 }
 
-// T-arithmetic rotation of one (x, y) pair, identical to norm_rope_act.hip::rotate_pair
-template <typename T>
-__device__ __forceinline__ void rope_pair(float x, float y, float c, float s, float& xo, float& yo) {
-#pragma clang fp contract(off)
-  const float xc = round_to<T>(x * c), ys = round_to<T>(y * s);
-  const float xs = round_to<T>(x * s), yc = round_to<T>(y * c);
-  xo = round_to<T>(xc - ys);
-  yo = round_to<T>(xs + yc);
-}
-
 // NeoX rotation of the fragment set f[s] (lane holds dims 32s+8g+j): the partner of dim d is
 // d +- D/2, i.e. fragment s +- NS/2 of the SAME lane.  cs points at cos_sin[pos] ([2][D/2]).
 template <typename T, int D>
@@ -177,7 +167,7 @@ __device__ __forceinline__ void rope_frags(u16x8 (&f)[D / 32], const u16x8 (&rc)
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       float xo, yo;
-      rope_pair<T>(T::to_float(x[j]), T::to_float(y[j]), T::to_float(c[j]), T::to_float(sn[j]), xo, yo);
+      rotate_pair<T>(T::to_float(x[j]), T::to_float(y[j]), T::to_float(c[j]), T::to_float(sn[j]), xo, yo);
       x[j] = T::from_float(xo);
       y[j] = T::from_float(yo);
     }

@@ -98,16 +98,6 @@ __device__ __forceinline__ void load_tile4(Tile4& t, const AttnParams& p, const 
   for (int r = 0; r < TR; ++r) t.v[r] = ld16<true>(vp + (int64_t)min(r, valid - 1) * p.v_row_stride);
 }
 
-// identical rounding to norm_rope_act.hip::rotate_pair / attn_decode.hip::rope_pair
-template <typename T>
-__device__ __forceinline__ void rope_pair4(float x, float y, float c, float s, float& xo, float& yo) {
-#pragma clang fp contract(off)
-  const float xc = round_to<T>(x * c), ys = round_to<T>(y * s);
-  const float xs = round_to<T>(x * s), yc = round_to<T>(y * c);
-  xo = round_to<T>(xc - ys);
-  yo = round_to<T>(xs + yc);
-}
-
 // NeoX rotation of this lane's 8 dims (8c .. 8c+7 of one head): the partner dims d +- 64 are lane c ^ 8's
 template <typename T>
 __device__ __forceinline__ u16x8 rope8(u16x8 own, const u16* cs, int c) {
@@ -124,7 +114,7 @@ __device__ __forceinline__ u16x8 rope8(u16x8 own, const u16* cs, int c) {
   for (int j = 0; j < 8; ++j) {
     const float x = T::to_float(low ? own[j] : par[j]), y = T::to_float(low ? par[j] : own[j]);
     float xo, yo;
-    rope_pair4<T>(x, y, T::to_float(cv[j]), T::to_float(sv[j]), xo, yo);
+    rotate_pair<T>(x, y, T::to_float(cv[j]), T::to_float(sv[j]), xo, yo);
     r[j] = T::from_float(low ? xo : yo);
   }
   return r;

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <memory>
 #include <tuple>
+#include <type_traits>
 #include <utility>
 #include "../../include/hydra_hip.h"
 #include "../../include/hydra_hip_experimental.h"   // declarations only; defined in EXPERIMENTS=1 builds
@@ -166,6 +167,23 @@ __device__ __forceinline__ float round_to(float f) {
 template <>
 __device__ __forceinline__ float round_to<F32>(float f) { return f; }
 
+// The host's dtype switch, stated once: f(T{}) with T the element traits of `dtype`, HX_ERR_DTYPE for a dtype the
+// entry does not do.  f is a generic callable that returns a status:
+//   return dispatch_dtype(dtype, [&](auto t) { return launch_op<decltype(t)>(...); });
+template <bool kWithF32 = true, typename F>
+inline int dispatch_dtype(int dtype, F&& f) {                 // fp32, fp16, bf16
+  switch (dtype) {
+    case HX_F32:
+      if constexpr (kWithF32) return f(F32{});
+      return HX_ERR_DTYPE;
+    case HX_F16: return f(F16{});
+    case HX_BF16: return f(BF16{});
+    default: return HX_ERR_DTYPE;
+  }
+}
+template <typename F>
+inline int dispatch_dtype16(int dtype, F&& f) { return dispatch_dtype<false>(dtype, f); }     // the 16-bit pair only
+
 // wave-level reductions (64 lanes)
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -176,6 +194,20 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
   return v;
+}
+
+// RoPE of one (x, y) pair: x' = x*c - y*s ; y' = x*s + y*c with every operation rounded to T (the reference's
+// rope.cu:22-27).  fp contraction is off so the fp32 path also matches an unfused CPU evaluation bit for bit.  The
+// rotary op and the decode attention kernels that rotate q and k themselves all round here.
+template <typename T>
+__device__ __forceinline__ void rotate_pair(float x, float y, float c, float s, float& xo, float& yo) {
+#pragma clang fp contract(off)
+  const float xc = round_to<T>(x * c);
+  const float ys = round_to<T>(y * s);
+  const float xs = round_to<T>(x * s);
+  const float yc = round_to<T>(y * c);
+  xo = round_to<T>(xc - ys);
+  yo = round_to<T>(xs + yc);
 }
 
 // The order every row-wise pick follows (argmax, penalised argmax, a greedy sampling row, the logprob ids and top-K):

@@ -3,6 +3,12 @@
 // registers, wave64 shuffle reductions.  Rounding points follow the reference CUDA
 // kernels (csrc/kernel/norm/rms_norm.cu:14-41, csrc/kernel/position_embedding/
 // rope.cu:12-79, csrc/kernel/activation/activation.cu:13-33).
+// Text that several kernels share is included, not restated: rms_norm_tail.inc (the scaling pass of every RMSNorm
+// that holds its row in registers), residual_add_vec.inc (h = (T)(v + r), residual <- h), rope_neox_vec_rotate.inc (one
+// step of the vector NeoX rotation), argmax_finish.inc; the pair rotation is hx::rotate_pair (hx_common.h).  On the
+// host the dtype switch is hx::dispatch_dtype / dispatch_dtype16, MAXV is chosen by dispatch_maxv, the activations'
+// grids and row chunks by row_grid_x / launch_row_chunks.  profiles/rowwise_one_text.md has the comparison with the
+// separate copies: the same device code, byte for byte.
 #include "hx_common.h"
 
 namespace {
@@ -17,12 +23,15 @@ template <> struct VecOf<F32> { static constexpr int N = 4; typedef f32x4 type; 
 template <> struct VecOf<F16> { static constexpr int N = 8; typedef u16x8 type; };
 template <> struct VecOf<BF16> { static constexpr int N = 8; typedef u16x8 type; };
 
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
+// sum over the workgroup's NT threads, in every thread; red: NT / 64 floats of LDS
+template <int NT>
+__device__ __forceinline__ float block_sum(float v, float* red) {
   v = wave_sum(v);
-  const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) red[wid] = v;
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
-  float t = red[0] + red[1] + red[2] + red[3];
+  float t = red[0];
+#pragma unroll
+  for (int k = 1; k < NT / 64; ++k) t += red[k];
   return t;
 }
 
@@ -53,14 +62,7 @@ __global__ __launch_bounds__(256) void rms_norm_vec_kernel(
       V v = in_v[i];
       if (ADD) {
         V r = res_v[i];
-        V h;
-#pragma unroll
-        for (int e = 0; e < N; ++e) {
-          float s = round_to<T>(T::to_float(v[e]) + T::to_float(r[e]));
-          x[j][e] = s;
-          h[e] = T::from_float(s);
-        }
-        res_v[i] = h;
+#include "residual_add_vec.inc"
       } else {
 #pragma unroll
         for (int e = 0; e < N; ++e) x[j][e] = T::to_float(v[e]);
@@ -69,23 +71,10 @@ __global__ __launch_bounds__(256) void rms_norm_vec_kernel(
       for (int e = 0; e < N; ++e) ss += x[j][e] * x[j][e];
     }
   }
-  const float total = block_sum_256(ss, red);
-  const float inv = rsqrtf(total / (float)hidden + eps);
-#pragma unroll
-  for (int j = 0; j < MAXV; ++j) {
-    const int i = threadIdx.x + j * 256;
-    if (i < nvec) {
-      V w = w_v[i];
-      V o;
-#pragma unroll
-      for (int e = 0; e < N; ++e) {
-        // (T)(x * s_variance) * weight  — two T roundings (rms_norm.cu:39)
-        float n = round_to<T>(x[j][e] * inv);
-        o[e] = T::from_float(n * T::to_float(w[e]));
-      }
-      out_v[i] = o;
-    }
-  }
+  const float total = block_sum<256>(ss, red);
+  constexpr int kNT = 256, frag_mb = 0;
+  const auto w_at = [=](int, int i) { return w_v[i]; };
+#include "rms_norm_tail.inc"
 }
 
 // generic (any hidden, any alignment): re-reads the row
@@ -107,13 +96,23 @@ __global__ __launch_bounds__(256) void rms_norm_generic_kernel(
     }
     ss += x * x;
   }
-  const float total = block_sum_256(ss, red);
+  const float total = block_sum<256>(ss, red);
   const float inv = rsqrtf(total / (float)hidden + eps);
   for (int64_t i = threadIdx.x; i < hidden; i += 256) {
     const float x = ADD ? T::to_float(res[i]) : T::to_float(in[i]);
     float n = round_to<T>(x * inv);
     out[row * hidden + i] = T::from_float(n * T::to_float(weight[i]));
   }
+}
+
+// MAXV of a row kernel that holds its row in registers — 16-byte vectors per thread, built for 1, 2 and 4 — as a
+// constant: f(std::integral_constant<int, MAXV>) for a row of nvec vectors on nt threads (nvec <= 4 * nt)
+template <typename F>
+void dispatch_maxv(int64_t nvec, int nt, F&& f) {
+  const int64_t mv = (nvec + nt - 1) / nt;
+  if (mv <= 1) f(std::integral_constant<int, 1>{});
+  else if (mv <= 2) f(std::integral_constant<int, 2>{});
+  else f(std::integral_constant<int, 4>{});
 }
 
 template <typename T, bool ADD>
@@ -125,18 +124,11 @@ int launch_rms(void* out, void* residual, const void* input, const void* weight,
   const bool vec = (hidden % N == 0) && aligned16(out) && aligned16(input) && aligned16(weight) &&
                    (!ADD || aligned16(residual));
   dim3 grid((unsigned)rows);
-  if (vec && hidden / N <= 256 * 1) {
-    hx::launcher(rms_norm_vec_kernel<T, 1, ADD>, grid, 256, 0, stream)((S*)out, (S*)residual,
-                                                            (const S*)input, (const S*)weight,
-                                                            eps, (int)hidden);
-  } else if (vec && hidden / N <= 256 * 2) {
-    hx::launcher(rms_norm_vec_kernel<T, 2, ADD>, grid, 256, 0, stream)((S*)out, (S*)residual,
-                                                            (const S*)input, (const S*)weight,
-                                                            eps, (int)hidden);
-  } else if (vec && hidden / N <= 256 * 4) {
-    hx::launcher(rms_norm_vec_kernel<T, 4, ADD>, grid, 256, 0, stream)((S*)out, (S*)residual,
-                                                            (const S*)input, (const S*)weight,
-                                                            eps, (int)hidden);
+  if (vec && hidden / N <= 256 * 4) {
+    dispatch_maxv(hidden / N, 256, [&](auto mv) {
+      hx::launcher(rms_norm_vec_kernel<T, mv.value, ADD>, grid, 256, 0, stream)((S*)out, (S*)residual, (const S*)input,
+                                                                                (const S*)weight, eps, (int)hidden);
+    });
   } else {
     hx::launcher(rms_norm_generic_kernel<T, ADD>, grid, 256, 0, stream)((S*)out, (S*)residual,
                                                              (const S*)input, (const S*)weight,
@@ -175,13 +167,7 @@ __global__ __launch_bounds__(256) void layer_norm_vec_kernel(
       const V r = res_v[i];
       if (ADD) {
         const V v = in_v[i];
-        V h;
-#pragma unroll
-        for (int e = 0; e < N; ++e) {
-          x[j][e] = round_to<T>(T::to_float(v[e]) + T::to_float(r[e]));
-          h[e] = T::from_float(x[j][e]);
-        }
-        res_v[i] = h;
+#include "residual_add_vec.inc"
       } else {
 #pragma unroll
         for (int e = 0; e < N; ++e) x[j][e] = T::to_float(r[e]);
@@ -190,7 +176,7 @@ __global__ __launch_bounds__(256) void layer_norm_vec_kernel(
       for (int e = 0; e < N; ++e) sum += x[j][e];
     }
   }
-  const float mean = block_sum_256(sum, red[0]) / (float)hidden;
+  const float mean = block_sum<256>(sum, red[0]) / (float)hidden;
   float sq = 0.f;
 #pragma unroll
   for (int j = 0; j < MAXV; ++j) {
@@ -200,7 +186,7 @@ __global__ __launch_bounds__(256) void layer_norm_vec_kernel(
       for (int e = 0; e < N; ++e) { const float d = x[j][e] - mean; sq += d * d; }
     }
   }
-  const float rstd = rsqrtf(block_sum_256(sq, red[1]) / (float)hidden + eps);
+  const float rstd = rsqrtf(block_sum<256>(sq, red[1]) / (float)hidden + eps);
   const V* w_v = reinterpret_cast<const V*>(weight);
   const V* b_v = reinterpret_cast<const V*>(bias);
 #pragma unroll
@@ -225,13 +211,10 @@ int launch_layer_norm(void* out, void* residual, const void* input, const void* 
   if (!aligned16(out) || !aligned16(residual) || (ADD && !aligned16(input)) || !aligned16(weight) || !aligned16(bias))
     return HX_ERR_STRIDE;
   const dim3 grid((unsigned)rows);
-  const int nv = (int)(hidden / N);
-#define HX_LN(MV) hx::launcher(layer_norm_vec_kernel<T, MV, ADD>, grid, 256, 0, stream)((S*)out, (S*)residual, (const S*)input, \
-                                                                                     (const S*)weight, (const S*)bias, eps, (int)hidden)
-  if (nv <= 256) HX_LN(1);
-  else if (nv <= 512) HX_LN(2);
-  else HX_LN(4);
-#undef HX_LN
+  dispatch_maxv(hidden / N, 256, [&](auto mv) {
+    hx::launcher(layer_norm_vec_kernel<T, mv.value, ADD>, grid, 256, 0, stream)((S*)out, (S*)residual, (const S*)input,
+                                                                                (const S*)weight, (const S*)bias, eps, (int)hidden);
+  });
   return check_launch();
 }
 
@@ -267,6 +250,24 @@ __global__ __launch_bounds__(256) void quick_gelu_vec_kernel(typename T::storage
   }
 }
 
+// The grid of the activations: x = workgroups of 256 threads that stride over a row's `items`, 64 at the most; y = rows.
+inline unsigned row_grid_x(int64_t items) {
+  const int64_t gx = (items + 255) / 256;
+  return (unsigned)(gx > 64 ? 64 : gx);
+}
+
+// ... and their launches, a grid's y being 65535 at the most: launch(r0, grid) for rows [r0, r0 + grid.y)
+template <typename F>
+int launch_row_chunks(int64_t rows, int64_t items, F&& launch) {
+  for (int64_t r0 = 0; r0 < rows; r0 += 65535) {
+    const int64_t nr = rows - r0 < 65535 ? rows - r0 : 65535;
+    launch(r0, dim3(row_grid_x(items), (unsigned)nr));
+    const int rc = check_launch();
+    if (rc) return rc;
+  }
+  return HX_OK;
+}
+
 template <typename T>
 int launch_quick_gelu(void* out, const void* in, int64_t rows, int64_t n, int64_t in_stride, hipStream_t stream) {
   typedef typename T::storage S;
@@ -274,16 +275,10 @@ int launch_quick_gelu(void* out, const void* in, int64_t rows, int64_t n, int64_
   if (n % N || in_stride % N) return HX_ERR_SHAPE;
   if (!aligned16(out) || !aligned16(in)) return HX_ERR_STRIDE;
   const int nvec = (int)(n / N);
-  int gx = (nvec + 255) / 256;
-  if (gx > 64) gx = 64;
-  for (int64_t r0 = 0; r0 < rows; r0 += 65535) {
-    const int64_t nr = rows - r0 < 65535 ? rows - r0 : 65535;
-    hx::launcher(quick_gelu_vec_kernel<T>, dim3((unsigned)gx, (unsigned)nr), 256, 0, stream)(
-        (S*)out + r0 * n, (const S*)in + r0 * in_stride, nvec, in_stride, n);
-    const int rc = check_launch();
-    if (rc) return rc;
-  }
-  return HX_OK;
+  return launch_row_chunks(rows, nvec, [&](int64_t r0, dim3 grid) {
+    hx::launcher(quick_gelu_vec_kernel<T>, grid, 256, 0, stream)((S*)out + r0 * n, (const S*)in + r0 * in_stride, nvec,
+                                                                 in_stride, n);
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -321,18 +316,10 @@ __device__ __forceinline__ void embed_rms_norm_row(typename T::storage* __restri
       }
     }
   }
-  const float total = block_sum_256(ss, red);
-  const float inv = rsqrtf(total / (float)hidden + eps);
-#pragma unroll
-  for (int j = 0; j < MAXV; ++j) {
-    const int i = threadIdx.x + j * 256;
-    if (i < nvec) {
-      V o;
-#pragma unroll
-      for (int e = 0; e < N; ++e) o[e] = T::from_float(round_to<T>(x[j][e] * inv) * T::to_float(wv[j][e]));
-      out_v[i] = o;
-    }
-  }
+  const float total = block_sum<256>(ss, red);
+  constexpr int kNT = 256, frag_mb = 0;
+  const auto w_at = [=](int j, int) { return wv[j]; };
+#include "rms_norm_tail.inc"
 }
 
 template <typename T, int MAXV>
@@ -440,22 +427,8 @@ __global__ __launch_bounds__(1024) void argmax_rows_kernel(int64_t* __restrict__
 
 // ---------------------------------------------------------------------------
 // RoPE.  Work item = (token, head (q heads then kv heads), pair index).
-// One thread rotates PV pairs: x' = x*c - y*s ; y' = x*s + y*c with every
-// operation rounded to T (rope.cu:22-27).  fp contraction is disabled so the
-// fp32 path also matches an unfused CPU evaluation bit for bit.
+// One thread rotates a pair at a time with hx::rotate_pair (hx_common.h): every operation rounded to T.
 // ---------------------------------------------------------------------------
-template <typename T>
-__device__ __forceinline__ void rotate_pair(float x, float y, float c, float s, float& xo,
-                                            float& yo) {
-#pragma clang fp contract(off)
-  const float xc = round_to<T>(x * c);
-  const float ys = round_to<T>(y * s);
-  const float xs = round_to<T>(x * s);
-  const float yc = round_to<T>(y * c);
-  xo = round_to<T>(xc - ys);
-  yo = round_to<T>(xs + yc);
-}
-
 template <typename T>
 __global__ __launch_bounds__(256) void rope_kernel(
     typename T::storage* __restrict__ q, typename T::storage* __restrict__ k,
@@ -499,29 +472,9 @@ __global__ __launch_bounds__(256) void rope_neox_vec_kernel(
   const int total = (n_heads + n_kv_heads) * vph;
   const typename T::storage* cs = cos_sin + (int64_t)positions[token] * rotary_dim;
   for (int i = threadIdx.x; i < total; i += 256) {
-    const int h = i / vph;
-    const int rv = i - h * vph;
-    typename T::storage* base = (h < n_heads) ? (q + token * q_stride + (int64_t)h * head_dim)
-                                              : (k + token * k_stride +
-                                                 (int64_t)(h - n_heads) * head_dim);
-    V* xp = reinterpret_cast<V*>(base + rv * N);
-    V* yp = reinterpret_cast<V*>(base + half + rv * N);
-    const V cv = *reinterpret_cast<const V*>(cs + rv * N);
-    const V sv = *reinterpret_cast<const V*>(cs + half + rv * N);
-    V xv = *xp, yv = *yp, xo, yo;
-#pragma unroll
-    for (int e = 0; e < N; ++e) {
-      float a, b;
-      rotate_pair<T>(T::to_float(xv[e]), T::to_float(yv[e]), T::to_float(cv[e]),
-                     T::to_float(sv[e]), a, b);
-      xo[e] = T::from_float(a);
-      yo[e] = T::from_float(b);
-    }
-    *xp = xo;
-    *yp = yo;
+#include "rope_neox_vec_rotate.inc"
   }
 }
-
 
 // Fused RoPE + set_kv_cache: rotates q and k in place exactly like
 // rope_neox_vec_kernel, and in the same pass writes the rotated k row and the v row of the
@@ -548,26 +501,7 @@ __global__ __launch_bounds__(256) void rope_cache_neox_vec_kernel(
   typename T::storage* kc_row = key_cache + blk * kc_block_stride + off * row_elems;
   typename T::storage* vc_row = value_cache + blk * vc_block_stride + off * row_elems;
   for (int i = threadIdx.x; i < total; i += 256) {
-    const int h = i / vph;
-    const int rv = i - h * vph;
-    const bool is_k = h >= n_heads;
-    typename T::storage* base = !is_k ? (q + token * q_stride + (int64_t)h * head_dim)
-                                      : (k + token * k_stride + (int64_t)(h - n_heads) * head_dim);
-    V* xp = reinterpret_cast<V*>(base + rv * N);
-    V* yp = reinterpret_cast<V*>(base + half + rv * N);
-    const V cv = *reinterpret_cast<const V*>(cs + rv * N);
-    const V sv = *reinterpret_cast<const V*>(cs + half + rv * N);
-    V xv = *xp, yv = *yp, xo, yo;
-#pragma unroll
-    for (int e = 0; e < N; ++e) {
-      float a, b;
-      rotate_pair<T>(T::to_float(xv[e]), T::to_float(yv[e]), T::to_float(cv[e]),
-                     T::to_float(sv[e]), a, b);
-      xo[e] = T::from_float(a);
-      yo[e] = T::from_float(b);
-    }
-    *xp = xo;
-    *yp = yo;
+#include "rope_neox_vec_rotate.inc"
     if (is_k && slot >= 0) {
       typename T::storage* crow = kc_row + (int64_t)(h - n_heads) * head_dim;
       *reinterpret_cast<V*>(crow + rv * N) = xo;
@@ -740,26 +674,17 @@ __global__ __launch_bounds__(NT) void add_rms_norm_slab_kernel(
       res_v[i] = h;
     }
   }
-  // block reduction over NT threads
+  // not block_sum<NT>: this sum starts from 0.f, block_sum from red[0] — one v_add_f32 apart, so another code object
   float tsum = wave_sum(ss);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = tsum;
   __syncthreads();
   float total = 0.f;
 #pragma unroll
   for (int k = 0; k < NT / 64; ++k) total += red[k];
-  const float inv = rsqrtf(total / (float)hidden + eps);
-#pragma unroll
-  for (int j = 0; j < MAXV; ++j) {
-    const int i = threadIdx.x + j * NT;
-    if (i < nvec) {
-      const u16x8 w = ww[j];
-      u16x8 o;
-#pragma unroll
-      for (int e = 0; e < 8; ++e)
-        o[e] = T::from_float(round_to<T>(x[j][e] * inv) * T::to_float(w[e]));
-      out_v[frag_mb ? (i >> 2) * frag_mb * 64 + (i & 3) * 16 : i] = o;
-    }
-  }
+  typedef u16x8 V;
+  constexpr int N = 8, kNT = NT;
+  const auto w_at = [=](int j, int) { return ww[j]; };
+#include "rms_norm_tail.inc"
 }
 
 // out[row][i] = (T)silu(gate) * up, gate = col i, up = col inter + i of the [rows, 2*inter] slabs
@@ -792,26 +717,33 @@ int launch_silu(void* out, const void* gate, const void* up, int64_t rows, int64
   const int64_t es = sizeof(S);
   const bool vec = (n % N == 0) && (gate_stride * es % 16 == 0) && aligned16(out) &&
                    aligned16(gate) && (!MUL || ((up_stride * es % 16 == 0) && aligned16(up)));
-  for (int64_t r0 = 0; r0 < rows; r0 += 65535) {
-    const int64_t nr = rows - r0 < 65535 ? rows - r0 : 65535;
+  const int nvec = (int)(n / N);
+  return launch_row_chunks(rows, vec ? nvec : n, [&](int64_t r0, dim3 grid) {
     S* o = (S*)out + r0 * n;
     const S* g = (const S*)gate + r0 * gate_stride;
     const S* u = MUL ? (const S*)up + r0 * up_stride : nullptr;
-    if (vec) {
-      const int nvec = (int)(n / N);
-      int gx = (nvec + 255) / 256;
-      if (gx > 64) gx = 64;
-      hx::launcher(silu_vec_kernel<T, MUL>, dim3(gx, (unsigned)nr), 256, 0, stream)(o, g, u, nvec,
-                                                                         gate_stride, up_stride, n);
-    } else {
-      int64_t gx = (n + 255) / 256;
-      if (gx > 64) gx = 64;
-      hx::launcher(silu_elem_kernel<T, MUL>, dim3((unsigned)gx, (unsigned)nr), 256, 0, stream)(
-          o, g, u, n, gate_stride, up_stride, n);
-    }
-    int rc = check_launch();
-    if (rc) return rc;
-  }
+    if (vec) hx::launcher(silu_vec_kernel<T, MUL>, grid, 256, 0, stream)(o, g, u, nvec, gate_stride, up_stride, n);
+    else hx::launcher(silu_elem_kernel<T, MUL>, grid, 256, 0, stream)(o, g, u, n, gate_stride, up_stride, n);
+  });
+}
+
+// hx_silu / hx_quick_gelu: the checks of a one-input activation, then launch(T{}) for the dtype
+template <typename F>
+int unary_activation(const void* out, const void* input, int64_t rows, int64_t n, int64_t in_stride, int dtype, F&& launch) {
+  if (rows < 0 || n < 0) return HX_ERR_SHAPE;
+  if (rows == 0 || n == 0) return HX_OK;
+  if (!out || !input) return HX_ERR_NULL;
+  if (in_stride < n) return HX_ERR_STRIDE;
+  return dispatch_dtype(dtype, launch);
+}
+
+// hx_embed_rms_norm / hx_decode_step_head: what both ask of the embedding row and its norm
+int check_embed_row_args(const void* h_out, const void* x_out, const void* ids, const void* table, const void* weight,
+                         int dtype, int64_t hidden) {
+  if (!h_out || !x_out || !ids || !table || !weight) return HX_ERR_NULL;
+  if (dtype != HX_F16 && dtype != HX_BF16) return HX_ERR_DTYPE;
+  if (hidden % 8 || hidden / 8 > 1024) return HX_ERR_SHAPE;
+  if (!aligned16(h_out) || !aligned16(x_out) || !aligned16(table) || !aligned16(weight)) return HX_ERR_STRIDE;
   return HX_OK;
 }
 
@@ -823,12 +755,9 @@ extern "C" int hx_rms_norm(void* out, const void* input, const void* weight, flo
   if (rows == 0) return HX_OK;
   if (!out || !input || !weight) return HX_ERR_NULL;
   hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case HX_F32: return launch_rms<F32, false>(out, nullptr, input, weight, epsilon, rows, hidden, s);
-    case HX_F16: return launch_rms<F16, false>(out, nullptr, input, weight, epsilon, rows, hidden, s);
-    case HX_BF16: return launch_rms<BF16, false>(out, nullptr, input, weight, epsilon, rows, hidden, s);
-    default: return HX_ERR_DTYPE;
-  }
+  return dispatch_dtype(dtype, [&](auto t) {
+    return launch_rms<decltype(t), false>(out, nullptr, input, weight, epsilon, rows, hidden, s);
+  });
 }
 
 extern "C" int hx_add_rms_norm(void* out, void* residual, const void* x, const void* weight,
@@ -838,12 +767,9 @@ extern "C" int hx_add_rms_norm(void* out, void* residual, const void* x, const v
   if (rows == 0) return HX_OK;
   if (!out || !residual || !x || !weight) return HX_ERR_NULL;
   hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case HX_F32: return launch_rms<F32, true>(out, residual, x, weight, epsilon, rows, hidden, s);
-    case HX_F16: return launch_rms<F16, true>(out, residual, x, weight, epsilon, rows, hidden, s);
-    case HX_BF16: return launch_rms<BF16, true>(out, residual, x, weight, epsilon, rows, hidden, s);
-    default: return HX_ERR_DTYPE;
-  }
+  return dispatch_dtype(dtype, [&](auto t) {
+    return launch_rms<decltype(t), true>(out, residual, x, weight, epsilon, rows, hidden, s);
+  });
 }
 
 extern "C" int hx_add_layer_norm(void* out, void* residual, const void* x, const void* weight, const void* bias,
@@ -853,30 +779,18 @@ extern "C" int hx_add_layer_norm(void* out, void* residual, const void* x, const
   if (!out || !residual || !weight || !bias) return HX_ERR_NULL;
   hipStream_t s = (hipStream_t)stream;
   // x == NULL: plain layer norm of `residual` (which is left untouched)
-#define HX_LN_T(T) (x ? launch_layer_norm<T, true>(out, residual, x, weight, bias, epsilon, rows, hidden, s) \
-                      : launch_layer_norm<T, false>(out, residual, nullptr, weight, bias, epsilon, rows, hidden, s))
-  switch (dtype) {
-    case HX_F32: return HX_LN_T(F32);
-    case HX_F16: return HX_LN_T(F16);
-    case HX_BF16: return HX_LN_T(BF16);
-    default: return HX_ERR_DTYPE;
-  }
-#undef HX_LN_T
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return x ? launch_layer_norm<T, true>(out, residual, x, weight, bias, epsilon, rows, hidden, s)
+             : launch_layer_norm<T, false>(out, residual, nullptr, weight, bias, epsilon, rows, hidden, s);
+  });
 }
 
 extern "C" int hx_quick_gelu(void* out, const void* input, int64_t rows, int64_t n, int64_t in_stride, int dtype,
                              hx_stream stream) {
-  if (rows < 0 || n < 0) return HX_ERR_SHAPE;
-  if (rows == 0 || n == 0) return HX_OK;
-  if (!out || !input) return HX_ERR_NULL;
-  if (in_stride < n) return HX_ERR_STRIDE;
-  hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case HX_F32: return launch_quick_gelu<F32>(out, input, rows, n, in_stride, s);
-    case HX_F16: return launch_quick_gelu<F16>(out, input, rows, n, in_stride, s);
-    case HX_BF16: return launch_quick_gelu<BF16>(out, input, rows, n, in_stride, s);
-    default: return HX_ERR_DTYPE;
-  }
+  return unary_activation(out, input, rows, n, in_stride, dtype, [&](auto t) {
+    return launch_quick_gelu<decltype(t)>(out, input, rows, n, in_stride, (hipStream_t)stream);
+  });
 }
 
 extern "C" int hx_apply_rotary_pos_emb(void* query, void* key, const int32_t* positions,
@@ -890,33 +804,17 @@ extern "C" int hx_apply_rotary_pos_emb(void* query, void* key, const int32_t* po
   if (!query || !key || !positions || !cos_sin) return HX_ERR_NULL;
   if (q_stride < n_heads * head_dim || k_stride < n_kv_heads * head_dim) return HX_ERR_STRIDE;
   hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case HX_F32:
-      return launch_rope<F32>(query, key, positions, cos_sin, n_tokens, n_heads, n_kv_heads,
-                              head_dim, rotary_dim, q_stride, k_stride, interleaved, s);
-    case HX_F16:
-      return launch_rope<F16>(query, key, positions, cos_sin, n_tokens, n_heads, n_kv_heads,
-                              head_dim, rotary_dim, q_stride, k_stride, interleaved, s);
-    case HX_BF16:
-      return launch_rope<BF16>(query, key, positions, cos_sin, n_tokens, n_heads, n_kv_heads,
-                               head_dim, rotary_dim, q_stride, k_stride, interleaved, s);
-    default: return HX_ERR_DTYPE;
-  }
+  return dispatch_dtype(dtype, [&](auto t) {
+    return launch_rope<decltype(t)>(query, key, positions, cos_sin, n_tokens, n_heads, n_kv_heads, head_dim, rotary_dim,
+                                    q_stride, k_stride, interleaved, s);
+  });
 }
 
 extern "C" int hx_silu(void* out, const void* input, int64_t rows, int64_t n, int64_t in_stride,
                        int dtype, hx_stream stream) {
-  if (rows < 0 || n < 0) return HX_ERR_SHAPE;
-  if (rows == 0 || n == 0) return HX_OK;
-  if (!out || !input) return HX_ERR_NULL;
-  if (in_stride < n) return HX_ERR_STRIDE;
-  hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case HX_F32: return launch_silu<F32, false>(out, input, nullptr, rows, n, in_stride, 0, s);
-    case HX_F16: return launch_silu<F16, false>(out, input, nullptr, rows, n, in_stride, 0, s);
-    case HX_BF16: return launch_silu<BF16, false>(out, input, nullptr, rows, n, in_stride, 0, s);
-    default: return HX_ERR_DTYPE;
-  }
+  return unary_activation(out, input, rows, n, in_stride, dtype, [&](auto t) {
+    return launch_silu<decltype(t), false>(out, input, nullptr, rows, n, in_stride, 0, (hipStream_t)stream);
+  });
 }
 
 extern "C" int hx_silu_and_mul(void* out, const void* gate, const void* up, int64_t rows,
@@ -927,12 +825,9 @@ extern "C" int hx_silu_and_mul(void* out, const void* gate, const void* up, int6
   if (!out || !gate || !up) return HX_ERR_NULL;
   if (gate_stride < n || up_stride < n) return HX_ERR_STRIDE;
   hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case HX_F32: return launch_silu<F32, true>(out, gate, up, rows, n, gate_stride, up_stride, s);
-    case HX_F16: return launch_silu<F16, true>(out, gate, up, rows, n, gate_stride, up_stride, s);
-    case HX_BF16: return launch_silu<BF16, true>(out, gate, up, rows, n, gate_stride, up_stride, s);
-    default: return HX_ERR_DTYPE;
-  }
+  return dispatch_dtype(dtype, [&](auto t) {
+    return launch_silu<decltype(t), true>(out, gate, up, rows, n, gate_stride, up_stride, s);
+  });
 }
 
 extern "C" int hx_rope_set_kv_cache(void* query, void* key, const void* value,
@@ -965,20 +860,14 @@ extern "C" int hx_rope_set_kv_cache(void* query, void* key, const void* value,
     return HX_ERR_STRIDE;
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((unsigned)n_tokens);
-#define HX_RC(TT)                                                                              \
-  hx::launcher(rope_cache_neox_vec_kernel<TT>, grid, 256, 0, s)(                                         \
-      (TT::storage*)query, (TT::storage*)key, (const TT::storage*)value, positions,            \
-      (const TT::storage*)cos_sin, slot_ids, (TT::storage*)key_cache,                          \
-      (TT::storage*)value_cache, (int)n_heads, (int)n_kv_heads, (int)head_dim, (int)rotary_dim, \
-      q_stride, k_stride, v_stride, kcache_block_stride, vcache_block_stride, (int)block_size)
-  switch (dtype) {
-    case HX_F32: HX_RC(F32); break;
-    case HX_F16: HX_RC(F16); break;
-    case HX_BF16: HX_RC(BF16); break;
-    default: return HX_ERR_DTYPE;
-  }
-#undef HX_RC
-  return check_launch();
+  return dispatch_dtype(dtype, [&](auto t) {
+    typedef typename decltype(t)::storage S;
+    hx::launcher(rope_cache_neox_vec_kernel<decltype(t)>, grid, 256, 0, s)(
+        (S*)query, (S*)key, (const S*)value, positions, (const S*)cos_sin, slot_ids, (S*)key_cache, (S*)value_cache,
+        (int)n_heads, (int)n_kv_heads, (int)head_dim, (int)rotary_dim, q_stride, k_stride, v_stride, kcache_block_stride,
+        vcache_block_stride, (int)block_size);
+    return check_launch();
+  });
 }
 
 extern "C" int hx_add_rms_norm_slabs(void* out, void* residual, const float* partial,
@@ -1004,20 +893,13 @@ extern "C" int hx_add_rms_norm_slabs_ex(void* out, void* residual, const float* 
   dim3 grid((unsigned)rows);
   // 512 threads: one 8-element vector (and its n_splits fp32 slab pieces) per thread up to
   // hidden = 4096 — the kernel is latency-bound on 32 rows, so more loads in flight per row win
-#define HX_L(TT, MV)                                                                             \
-  hx::launcher(add_rms_norm_slab_kernel<TT, MV, 512>, grid, 512, 0, s)((u16*)out, (u16*)residual, partial, \
-                                                            n_splits, stride, (const u16*)weight, \
-                                                            epsilon, (int)hidden, frag_mb)
-  const int mv = (int)((hidden / 8 + 511) / 512);
-  if (dtype == HX_F16) {
-    if (mv <= 1) HX_L(F16, 1); else if (mv <= 2) HX_L(F16, 2); else HX_L(F16, 4);
-  } else if (dtype == HX_BF16) {
-    if (mv <= 1) HX_L(BF16, 1); else if (mv <= 2) HX_L(BF16, 2); else HX_L(BF16, 4);
-  } else {
-    return HX_ERR_DTYPE;
-  }
-#undef HX_L
-  return check_launch();
+  return dispatch_dtype16(dtype, [&](auto t) {
+    dispatch_maxv(hidden / 8, 512, [&](auto mv) {
+      hx::launcher(add_rms_norm_slab_kernel<decltype(t), mv.value, 512>, grid, 512, 0, s)(
+          (u16*)out, (u16*)residual, partial, n_splits, stride, (const u16*)weight, epsilon, (int)hidden, frag_mb);
+    });
+    return check_launch();
+  });
 }
 
 extern "C" int hx_silu_and_mul_slabs(void* out, const float* partial, int32_t n_splits,
@@ -1036,17 +918,12 @@ extern "C" int hx_silu_and_mul_slabs_ex(void* out, const float* partial, int32_t
   if (inter % 8 || rows > 65535) return HX_ERR_SHAPE;
   if (!aligned16(out) || !aligned16(partial)) return HX_ERR_STRIDE;
   hipStream_t s = (hipStream_t)stream;
-  int gx = (int)((inter / 8 + 255) / 256);
-  if (gx > 64) gx = 64;
-  dim3 grid(gx, (unsigned)rows);
+  dim3 grid(row_grid_x(inter / 8), (unsigned)rows);
   const int64_t stride = rows * 2 * inter;
-  if (dtype == HX_F16)
-    hx::launcher(silu_mul_slab_kernel<F16>, grid, 256, 0, s)((u16*)out, partial, n_splits, stride, (int)inter, frag_mb);
-  else if (dtype == HX_BF16)
-    hx::launcher(silu_mul_slab_kernel<BF16>, grid, 256, 0, s)((u16*)out, partial, n_splits, stride, (int)inter, frag_mb);
-  else
-    return HX_ERR_DTYPE;
-  return check_launch();
+  return dispatch_dtype16(dtype, [&](auto t) {
+    hx::launcher(silu_mul_slab_kernel<decltype(t)>, grid, 256, 0, s)((u16*)out, partial, n_splits, stride, (int)inter, frag_mb);
+    return check_launch();
+  });
 }
 
 extern "C" int hx_embed_rms_norm(void* h_out, void* x_out, const void* ids, int ids_are_int64, const void* table,
@@ -1054,32 +931,21 @@ extern "C" int hx_embed_rms_norm(void* h_out, void* x_out, const void* ids, int 
                                  int dtype, hx_stream stream) {
   if (rows < 0 || hidden <= 0 || vocab <= 0) return HX_ERR_SHAPE;
   if (rows == 0) return HX_OK;
-  if (!h_out || !x_out || !ids || !table || !weight) return HX_ERR_NULL;
-  if (dtype != HX_F16 && dtype != HX_BF16) return HX_ERR_DTYPE;
-  if (hidden % 8 || hidden / 8 > 1024) return HX_ERR_SHAPE;
-  if (!aligned16(h_out) || !aligned16(x_out) || !aligned16(table) || !aligned16(weight)) return HX_ERR_STRIDE;
+  if (const int rc = check_embed_row_args(h_out, x_out, ids, table, weight, dtype, hidden)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  const int mv = (int)((hidden / 8 + 255) / 256);
-#define HX_L(TT, MV)                                                                                      \
-  hx::launcher(embed_rms_norm_kernel<TT, MV>, (unsigned)rows, 256, 0, s)((u16*)h_out, (u16*)x_out, ids, ids_are_int64, \
-                                                               (const u16*)table, (const u16*)weight, epsilon,  \
-                                                               (int)hidden, vocab)
-  if (dtype == HX_F16) {
-    if (mv <= 1) HX_L(F16, 1); else if (mv <= 2) HX_L(F16, 2); else HX_L(F16, 4);
-  } else {
-    if (mv <= 1) HX_L(BF16, 1); else if (mv <= 2) HX_L(BF16, 2); else HX_L(BF16, 4);
-  }
-#undef HX_L
-  return check_launch();
+  return dispatch_dtype16(dtype, [&](auto t) {
+    dispatch_maxv(hidden / 8, 256, [&](auto mv) {
+      hx::launcher(embed_rms_norm_kernel<decltype(t), mv.value>, (unsigned)rows, 256, 0, s)(
+          (u16*)h_out, (u16*)x_out, ids, ids_are_int64, (const u16*)table, (const u16*)weight, epsilon, (int)hidden, vocab);
+    });
+    return check_launch();
+  });
 }
 
 extern "C" int hx_decode_step_head(const hx_step_head_args* a, hx_stream stream) {
   if (!a) return HX_ERR_NULL;
   if (a->rows <= 0 || a->hidden <= 0 || a->vocab <= 0 || a->zero_bytes < 0 || a->batch < 0) return HX_ERR_SHAPE;
-  if (!a->h_out || !a->x_out || !a->ids || !a->table || !a->weight) return HX_ERR_NULL;
-  if (a->dtype != HX_F16 && a->dtype != HX_BF16) return HX_ERR_DTYPE;
-  if (a->hidden % 8 || a->hidden / 8 > 1024) return HX_ERR_SHAPE;
-  if (!aligned16(a->h_out) || !aligned16(a->x_out) || !aligned16(a->table) || !aligned16(a->weight)) return HX_ERR_STRIDE;
+  if (const int rc = check_embed_row_args(a->h_out, a->x_out, a->ids, a->table, a->weight, a->dtype, a->hidden)) return rc;
   if ((a->feed_src == nullptr) != (a->feed_prev == nullptr)) return HX_ERR_NULL;
   if (a->zero_bytes > 0 && (!a->zero_ptr || (a->zero_bytes & 3) || !aligned16(a->zero_ptr))) return a->zero_ptr ? HX_ERR_STRIDE : HX_ERR_NULL;
   if (a->batch > 0) {
@@ -1097,15 +963,12 @@ extern "C" int hx_decode_step_head(const hx_step_head_args* a, hx_stream stream)
   p.batch = a->batch; p.block_size = a->block_size; p.stride = a->stride;
   const unsigned grid = (unsigned)(p.rows + p.n_zero + (p.batch > 0 ? 1 : 0));
   hipStream_t s = (hipStream_t)stream;
-  const int mv = (int)((a->hidden / 8 + 255) / 256);
-#define HX_L(TT, MV) hx::launcher(decode_step_head_kernel<TT, MV>, grid, 256, 0, s)(p)
-  if (a->dtype == HX_F16) {
-    if (mv <= 1) HX_L(F16, 1); else if (mv <= 2) HX_L(F16, 2); else HX_L(F16, 4);
-  } else {
-    if (mv <= 1) HX_L(BF16, 1); else if (mv <= 2) HX_L(BF16, 2); else HX_L(BF16, 4);
-  }
-#undef HX_L
-  return check_launch();
+  return dispatch_dtype16(a->dtype, [&](auto t) {
+    dispatch_maxv(a->hidden / 8, 256, [&](auto mv) {
+      hx::launcher(decode_step_head_kernel<decltype(t), mv.value>, grid, 256, 0, s)(p);
+    });
+    return check_launch();
+  });
 }
 
 extern "C" int hx_argmax_rows(int64_t* out, const void* logits, int64_t rows, int64_t n, int64_t ld, int dtype,
@@ -1114,8 +977,8 @@ extern "C" int hx_argmax_rows(int64_t* out, const void* logits, int64_t rows, in
   if (rows == 0) return HX_OK;
   if (!out || !logits) return HX_ERR_NULL;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == HX_F16) hx::launcher(argmax_rows_kernel<F16>, (unsigned)rows, 1024, 0, s)(out, (const u16*)logits, (int)n, ld);
-  else if (dtype == HX_BF16) hx::launcher(argmax_rows_kernel<BF16>, (unsigned)rows, 1024, 0, s)(out, (const u16*)logits, (int)n, ld);
-  else return HX_ERR_DTYPE;
-  return check_launch();
+  return dispatch_dtype16(dtype, [&](auto t) {
+    hx::launcher(argmax_rows_kernel<decltype(t)>, (unsigned)rows, 1024, 0, s)(out, (const u16*)logits, (int)n, ld);
+    return check_launch();
+  });
 }

@@ -231,3 +231,192 @@ def test_moe_gemm_entries_keep_their_order_of_refusals():
             assert call((3, _P + 2)) == -3 and call((3, _P + 2), f32) == -1 and call((3, None)) == -4, name
         # NULL and shape come first in both families
         assert call((0, None), f32, (1, _P + 8)) == -4 and call((dtype - 2, 192), f32, (1, _P + 8)) == -2, name
+
+
+# The row-wise entries (csrc/norm_rope_act.hip): which refusal each reports for one bad argument, and which of two it
+# reports first.  The statuses are what the library gave before the entries shared their dtype dispatch, launch
+# helpers and argument checks; they are written out, not derived.  Per entry: an argument list that would launch (it
+# is never passed as it stands) and [(changes, status)] with changes = [(position, value)].  Every call is refused on
+# the host or returns for an empty problem: HX_OK 0, HX_ERR_DTYPE -1, HX_ERR_SHAPE -2, HX_ERR_STRIDE -3, HX_ERR_NULL -4.
+_ODD = _P + 8                  # a pointer that is not 16-byte aligned
+_F32, _BAD = 0, 7              # HX_F32 (refused by the 16-bit-only entries) and no dtype at all
+
+
+def _nulls(*positions):
+    return [(p, None) for p in positions]
+
+
+_ROWWISE_ENTRIES = {
+    #              out input weight eps rows hidden dtype stream
+    "hx_rms_norm": ([_P, _P, _P, 1e-5, 2, 64, 1, None], [
+        ([(4, -1)], -2), ([(5, 0)], -2), ([(5, -8)], -2),
+        ([(4, -1), (0, None)], -2), ([(4, -1), (6, _BAD)], -2), ([(5, 0), (4, 0)], -2),      # shape first
+        ([(4, 0)] + _nulls(0, 1, 2) + [(6, _BAD)], 0),                                       # no rows: nothing is looked at
+        ([(0, None)], -4), ([(1, None)], -4), ([(2, None)], -4),
+        ([(1, None), (6, _BAD)], -4),                                                        # NULL before dtype
+        ([(6, _BAD)], -1), ([(6, 3)], -1), ([(6, -1)], -1),
+        ([(0, _ODD), (5, 63), (6, _BAD)], -1),                # no alignment or width refusal: the generic kernel takes those
+    ]),
+    #                  out residual x weight eps rows hidden dtype stream
+    "hx_add_rms_norm": ([_P, _P, _P, _P, 1e-5, 2, 64, 1, None], [
+        ([(5, -1)], -2), ([(6, 0)], -2),
+        ([(5, -1), (1, None)], -2), ([(5, -1), (7, _BAD)], -2), ([(6, 0), (5, 0)], -2),
+        ([(5, 0)] + _nulls(0, 1, 2, 3) + [(7, _BAD)], 0),
+        ([(0, None)], -4), ([(1, None)], -4), ([(2, None)], -4), ([(3, None)], -4),
+        ([(1, None), (7, _BAD)], -4),
+        ([(7, _BAD)], -1), ([(7, 3)], -1),
+        ([(1, _ODD), (6, 63), (7, _BAD)], -1),
+    ]),
+    #                    out residual x weight bias eps rows hidden dtype stream
+    "hx_add_layer_norm": ([_P, _P, _P, _P, _P, 1e-5, 2, 64, 1, None], [
+        ([(6, -1)], -2), ([(7, 0)], -2),
+        ([(6, -1), (0, None)], -2), ([(6, -1), (8, _BAD)], -2), ([(7, 0), (6, 0)], -2),
+        ([(6, 0)] + _nulls(0, 1, 2, 3, 4) + [(8, _BAD)], 0),
+        ([(0, None)], -4), ([(1, None)], -4), ([(3, None)], -4), ([(4, None)], -4),
+        ([(3, None), (8, _BAD)], -4), ([(4, None), (7, 63)], -4),
+        ([(8, _BAD)], -1), ([(2, None), (8, _BAD)], -1),                                     # x may be NULL: plain layer norm
+        ([(8, _BAD), (7, 63)], -1), ([(8, _BAD), (0, _ODD)], -1),                            # dtype before width
+        ([(7, 63)], -2), ([(7, 8200)], -2), ([(7, 62), (8, _F32)], -2), ([(7, 4100), (8, _F32)], -2), ([(7, 4)], -2),
+        ([(7, 63), (0, _ODD)], -2),                                                          # width before alignment
+        ([(0, _ODD)], -3), ([(1, _ODD)], -3), ([(2, _ODD)], -3), ([(3, _ODD)], -3), ([(4, _ODD)], -3),
+        ([(2, None), (0, _ODD)], -3), ([(7, 4), (8, _F32), (4, _ODD)], -3),                  # 4 floats are one vector
+    ]),
+    #                out input rows n in_stride dtype stream
+    "hx_quick_gelu": ([_P, _P, 2, 64, 64, 1, None], [
+        ([(2, -1)], -2), ([(3, -1)], -2), ([(2, -1), (3, 0)], -2), ([(2, -1), (0, None)], -2),
+        ([(2, 0)] + _nulls(0, 1) + [(5, _BAD)], 0), ([(3, 0)] + _nulls(0, 1) + [(5, _BAD)], 0),
+        ([(0, None)], -4), ([(1, None)], -4), ([(1, None), (4, 8)], -4), ([(0, None), (5, _BAD)], -4),
+        ([(4, 63)], -3), ([(4, 8), (5, _BAD)], -3),                                          # a short stride before dtype
+        ([(5, _BAD)], -1), ([(5, _BAD), (3, 63)], -1), ([(5, _BAD), (0, _ODD)], -1),         # dtype before width
+        ([(3, 63)], -2), ([(4, 65)], -2), ([(3, 60), (4, 62), (5, _F32)], -2),
+        ([(3, 63), (0, _ODD)], -2),                                                          # width before alignment
+        ([(0, _ODD)], -3), ([(1, _ODD)], -3),
+    ]),
+    #                          q k positions cos_sin n_tokens n_heads n_kv_heads head_dim rotary_dim q_stride k_stride
+    #                          interleaved dtype stream
+    "hx_apply_rotary_pos_emb": ([_P, _P, _P, _P, 2, 4, 2, 64, 64, 256, 128, 0, 1, None], [
+        ([(4, -1)], -2), ([(5, -1)], -2), ([(6, -1)], -2), ([(7, 0)], -2),
+        ([(8, 0)], -2), ([(8, 66)], -2), ([(8, 63)], -2),
+        ([(8, 63), (4, 0)], -2), ([(4, -1), (0, None)], -2), ([(8, 63), (12, _BAD)], -2),
+        ([(4, 0)] + _nulls(0, 1, 2, 3) + [(9, 1), (12, _BAD)], 0),
+        ([(0, None)], -4), ([(1, None)], -4), ([(2, None)], -4), ([(3, None)], -4),
+        ([(2, None), (9, 255)], -4), ([(3, None), (12, _BAD)], -4),                          # NULL before stride
+        ([(9, 255)], -3), ([(10, 127)], -3), ([(10, 127), (12, _BAD)], -3),                  # stride before dtype
+        ([(12, _BAD)], -1), ([(12, 3)], -1), ([(12, _BAD), (0, _ODD), (11, 1)], -1),
+    ]),
+    #          out input rows n in_stride dtype stream
+    "hx_silu": ([_P, _P, 2, 64, 64, 1, None], [
+        ([(2, -1)], -2), ([(3, -1)], -2), ([(2, -1), (3, 0)], -2), ([(3, -1), (1, None)], -2),
+        ([(2, 0)] + _nulls(0, 1) + [(5, _BAD)], 0), ([(3, 0)] + _nulls(0, 1) + [(4, -1), (5, _BAD)], 0),
+        ([(0, None)], -4), ([(1, None)], -4), ([(0, None), (4, 8)], -4), ([(1, None), (5, _BAD)], -4),
+        ([(4, 63)], -3), ([(4, 8), (5, _BAD)], -3),
+        ([(5, _BAD)], -1), ([(5, 3)], -1), ([(5, _BAD), (3, 63), (4, 63), (0, _ODD)], -1),   # the element kernel takes those
+    ]),
+    #                  out gate up rows n gate_stride up_stride dtype stream
+    "hx_silu_and_mul": ([_P, _P, _P, 2, 64, 64, 64, 1, None], [
+        ([(3, -1)], -2), ([(4, -1)], -2), ([(3, -1), (4, 0)], -2), ([(4, -1), (2, None)], -2),
+        ([(3, 0)] + _nulls(0, 1, 2) + [(7, _BAD)], 0), ([(4, 0)] + _nulls(0, 1, 2) + [(7, _BAD)], 0),
+        ([(0, None)], -4), ([(1, None)], -4), ([(2, None)], -4), ([(2, None), (6, 8)], -4), ([(1, None), (7, _BAD)], -4),
+        ([(5, 63)], -3), ([(6, 63)], -3), ([(6, 8), (7, _BAD)], -3),
+        ([(7, _BAD)], -1), ([(7, 3)], -1), ([(7, _BAD), (4, 63), (5, 63), (6, 63), (2, _ODD)], -1),
+    ]),
+    #                       q k v positions cos_sin slot_ids key_cache value_cache n_tokens n_heads n_kv_heads head_dim
+    #                       rotary_dim q_stride k_stride v_stride block_size kcache_block_stride vcache_block_stride dtype
+    "hx_rope_set_kv_cache": ([_P] * 8 + [2, 4, 2, 64, 64, 256, 128, 128, 16, 2048, 2048, 1, None], [
+        ([(8, -1)], -2), ([(9, -1)], -2), ([(10, 0)], -2), ([(11, 0)], -2), ([(16, 0)], -2),
+        ([(12, 0)], -2), ([(12, 66)], -2), ([(12, 63)], -2),
+        ([(12, 63), (8, 0)], -2), ([(16, 0), (0, None)], -2), ([(12, 63), (19, _BAD)], -2),
+        ([(8, 0)] + _nulls(*range(8)) + [(13, 1), (19, _BAD)], 0),
+    ] + [([(p, None)], -4) for p in range(8)] + [
+        ([(5, None), (19, _BAD)], -4), ([(7, None), (12, 8)], -4),                           # NULL before dtype
+        ([(19, _BAD)], -1), ([(19, 3)], -1),
+        ([(19, _BAD), (12, 8)], -1), ([(19, _BAD), (13, 260)], -1), ([(19, _BAD), (0, _ODD)], -1),   # dtype before the rest
+        ([(12, 8)], -2), ([(11, 68)], -2), ([(12, 4), (19, _F32)], -2),                      # whole vectors only
+        ([(12, 8), (13, 260)], -2), ([(12, 8), (0, _ODD)], -2), ([(11, 68), (13, 248)], -2), # ... before the strides
+        ([(13, 260)], -3), ([(14, 132)], -3), ([(15, 132)], -3), ([(17, 2052)], -3), ([(18, 2052)], -3),
+        ([(0, _ODD)], -3), ([(1, _ODD)], -3), ([(2, _ODD)], -3), ([(4, _ODD)], -3), ([(6, _ODD)], -3), ([(7, _ODD)], -3),
+        ([(13, 248)], -3), ([(14, 120)], -3), ([(15, 120)], -3),
+        ([(12, 8), (19, _F32), (6, _ODD)], -3),                                              # 4 floats are one vector
+    ]),
+    #                           out residual partial n_splits weight eps rows hidden dtype out_fragment_major stream
+    "hx_add_rms_norm_slabs_ex": ([_P, _P, _P, 2, _P, 1e-5, 4, 64, 1, 0, None], [
+        ([(6, -1)], -2), ([(7, 0)], -2), ([(3, 0)], -2), ([(6, -1), (0, None)], -2), ([(3, 0), (6, 0)], -2),
+        ([(9, 1), (7, 48)], -2), ([(9, 1), (7, 48), (6, 0)], -2),                            # ... before "no rows"
+        ([(6, 0)] + _nulls(0, 1, 2, 4) + [(7, 12), (8, _F32)], 0),
+        ([(0, None)], -4), ([(1, None)], -4), ([(2, None)], -4), ([(4, None)], -4),
+        ([(4, None), (7, 12)], -4), ([(0, None), (8, _F32)], -4),                            # NULL before width
+        ([(7, 12)], -2), ([(7, 16392)], -2), ([(7, 12), (0, _ODD)], -2), ([(7, 12), (8, _F32)], -2),
+        ([(0, _ODD)], -3), ([(1, _ODD)], -3), ([(2, _ODD)], -3), ([(4, _ODD)], -3),
+        ([(1, _ODD), (8, _F32)], -3),                                                        # dtype is reported last
+        ([(8, _F32)], -1), ([(8, _BAD)], -1), ([(8, _F32), (9, 1)], -1),
+    ]),
+    #                           out partial n_splits rows inter dtype out_fragment_major stream
+    "hx_silu_and_mul_slabs_ex": ([_P, _P, 2, 4, 64, 1, 0, None], [
+        ([(3, -1)], -2), ([(4, 0)], -2), ([(2, 0)], -2), ([(3, -1), (0, None)], -2), ([(2, 0), (3, 0)], -2),
+        ([(6, 1), (4, 48)], -2), ([(6, 1), (4, 48), (3, 0)], -2),
+        ([(3, 0)] + _nulls(0, 1) + [(4, 12), (5, _F32)], 0),
+        ([(0, None)], -4), ([(1, None)], -4), ([(1, None), (4, 12)], -4), ([(0, None), (5, _F32)], -4),
+        ([(4, 12)], -2), ([(3, 65536)], -2), ([(4, 12), (0, _ODD)], -2), ([(3, 65536), (5, _F32)], -2),
+        ([(0, _ODD)], -3), ([(1, _ODD)], -3), ([(1, _ODD), (5, _F32)], -3),
+        ([(5, _F32)], -1), ([(5, _BAD)], -1), ([(5, _F32), (6, 1)], -1),
+    ]),
+    #                    h_out x_out ids ids_are_int64 table weight eps rows hidden vocab dtype stream
+    "hx_embed_rms_norm": ([_P, _P, _P, 1, _P, _P, 1e-5, 2, 64, 100, 1, None], [
+        ([(7, -1)], -2), ([(8, 0)], -2), ([(9, 0)], -2), ([(9, 0), (0, None)], -2), ([(9, 0), (7, 0)], -2),
+        ([(7, 0)] + _nulls(0, 1, 2, 4, 5) + [(8, 12), (10, _F32)], 0),
+        ([(0, None)], -4), ([(1, None)], -4), ([(2, None)], -4), ([(4, None)], -4), ([(5, None)], -4),
+        ([(2, None), (10, _F32)], -4),                                                       # NULL before dtype
+        ([(10, _F32)], -1), ([(10, _BAD)], -1), ([(10, _F32), (8, 12)], -1), ([(10, _F32), (0, _ODD)], -1),
+        ([(8, 12)], -2), ([(8, 8200)], -2), ([(8, 12), (4, _ODD)], -2),                      # width before alignment
+        ([(0, _ODD)], -3), ([(1, _ODD)], -3), ([(4, _ODD)], -3), ([(5, _ODD)], -3),
+    ]),
+    #                 out logits rows n ld dtype stream
+    "hx_argmax_rows": ([_P, _P, 2, 64, 64, 1, None], [
+        ([(2, -1)], -2), ([(3, 0)], -2), ([(4, 63)], -2), ([(3, _BIG), (4, _BIG)], -2),
+        ([(3, 0), (2, 0)], -2), ([(4, 63), (0, None)], -2), ([(4, 63), (5, _F32)], -2),
+        ([(2, 0)] + _nulls(0, 1) + [(5, _F32)], 0),
+        ([(0, None)], -4), ([(1, None)], -4), ([(1, None), (5, _F32)], -4),
+        ([(5, _F32)], -1), ([(5, _BAD)], -1), ([(5, _F32), (1, _ODD)], -1),
+    ]),
+}
+
+# hx_decode_step_head takes its arguments in a struct: the fields of a call that would launch, and [(changes, status)]
+_STEP_HEAD_OK = dict(h_out=_P, x_out=_P, ids=_P, table=_P, weight=_P, rows=2, hidden=64, vocab=100, epsilon=1e-5,
+                     ids_are_int64=1, dtype=1)
+_STEP_META = ("positions", "kv_lens", "cu_seqlens_k", "new_cache_slots", "block_table", "cu_block_lens")
+_STEP_BATCH = dict({f: _P for f in _STEP_META}, batch=1, block_size=16, stride=1)
+_STEP_HEAD_CASES = [
+    (dict(rows=0), -2), (dict(rows=-1), -2), (dict(hidden=0), -2), (dict(vocab=0), -2), (dict(zero_bytes=-4), -2),
+    (dict(batch=-1), -2), (dict(rows=0, h_out=None), -2), (dict(rows=0, dtype=_F32), -2),    # no rows is a shape error here
+    (dict(h_out=None), -4), (dict(x_out=None), -4), (dict(ids=None), -4), (dict(table=None), -4), (dict(weight=None), -4),
+    (dict(ids=None, dtype=_F32), -4),                                                        # NULL before dtype
+    (dict(dtype=_F32), -1), (dict(dtype=_BAD), -1), (dict(dtype=_F32, hidden=12), -1), (dict(dtype=_F32, table=_ODD), -1),
+    (dict(hidden=12), -2), (dict(hidden=8200), -2), (dict(hidden=12, weight=_ODD), -2),
+    (dict(h_out=_ODD), -3), (dict(x_out=_ODD), -3), (dict(table=_ODD), -3), (dict(weight=_ODD), -3),
+    (dict(x_out=_ODD, feed_src=_P), -3),                                                     # alignment before the feed pair
+    (dict(feed_src=_P), -4), (dict(feed_prev=_P), -4), (dict(feed_src=_P, zero_bytes=6, zero_ptr=_P), -4),
+    (dict(zero_bytes=16), -4), (dict(zero_bytes=6), -4),                                     # no zero_ptr: NULL whatever the size
+    (dict(zero_bytes=6, zero_ptr=_P), -3), (dict(zero_bytes=16, zero_ptr=_P + 4), -3),
+    (dict(_STEP_BATCH, positions=None, zero_bytes=6, zero_ptr=_P), -3),                      # the zero area before the batch
+] + [(dict(_STEP_BATCH, **{f: None}), -4) for f in _STEP_META] + [
+    (dict(_STEP_BATCH, block_size=0), -2), (dict(_STEP_BATCH, stride=0), -2),
+    (dict(_STEP_BATCH, block_size=0, cu_block_lens=None), -4),                               # NULL before the block size
+    (dict(_STEP_BATCH, block_size=0, h_out=None), -4), (dict(_STEP_BATCH, stride=0, dtype=_F32), -1),
+]
+
+
+def test_rowwise_entries_keep_their_order_of_refusals():
+    lib = _lib.lib()
+    for name, (ok, cases) in _ROWWISE_ENTRIES.items():
+        assert len(cases) >= 14, name
+        for changes, status in cases:
+            assert changes, name                                   # the launching call itself is never made
+            args = list(ok)
+            for pos, v in changes:
+                args[pos] = v
+            assert getattr(lib, name)(*args) == status, (name, changes)
+    assert lib.hx_decode_step_head(None, None) == -4
+    for changes, status in _STEP_HEAD_CASES:
+        assert changes
+        a = _lib.hx_step_head_args(**dict(_STEP_HEAD_OK, **changes))
+        assert lib.hx_decode_step_head(ctypes.byref(a), None) == status, changes
