@@ -146,6 +146,74 @@ def dequant_fp8_block(wq: Tensor, scale: Tensor, dtype: torch.dtype, out: Option
     return out
 
 
+# ---- W8A8 (csrc/gemm_fp8a.hip): e4m3 activations, one fp32 scale per (row, 128-k group), on the FP8 matrix instructions ----
+def quant_fp8_group(x: Tensor, out=None):
+    """(xq, xs) of x [M, K] fp16 / bf16, K % 128 == 0: per (row, 128-k group) s = max(amax |x|, 1e-10) / 448 and
+    q = e4m3_rne(clamp(x / s, -448, 448)), bit for bit the torch expression (hx_quant_fp8_group).  xq: float8_e4m3fn [M, K];
+    xs: float32 of SHAPE [M, K / 128], kept k-major in memory (a transposed view: the GEMM reads a k-step's scales as one
+    run).  out: a (xq, xs) pair to write into — xq bytes with contiguous rows at a stride % 16 == 0, xs float32 of that
+    shape with any positive strides."""
+    from hydrainfer_amd._C.kernel.moe.experts import BLOCK, FP8
+    _lib.require_gpu(x, *(out or ()))
+    if x.dim() != 2 or x.dtype not in (torch.float16, torch.bfloat16) or x.shape[0] == 0 or x.shape[1] == 0 or x.shape[1] % BLOCK:
+        raise _lib.HydraHipError("quant_fp8_group: x must be fp16 / bf16 [M, K], M >= 1, K % 128 == 0")
+    if x.stride(1) != 1 or x.stride(0) % 8:
+        raise _lib.HydraHipError("quant_fp8_group: rows of x with contiguous elements at a stride that is a multiple of 8")
+    M, K = x.shape
+    if out is None:
+        xq = torch.empty((M, K), dtype=FP8, device=x.device)
+        xs = torch.empty((K // BLOCK, M), dtype=torch.float32, device=x.device).t()
+    else:
+        xq, xs = out
+        if (xq.dtype not in (FP8, torch.uint8) or tuple(xq.shape) != (M, K) or xq.stride(1) != 1 or xq.stride(0) % 16
+                or xs.dtype != torch.float32 or tuple(xs.shape) != (M, K // BLOCK) or min(xs.stride()) < 1):
+            raise _lib.HydraHipError("quant_fp8_group: out must be (float8_e4m3fn [M, K] with contiguous rows at a stride % 16 "
+                                     "== 0, float32 [M, K / 128] with positive strides)")
+    _lib.check(_lib.lib().hx_quant_fp8_group(xq.data_ptr(), xs.data_ptr(), x.data_ptr(), M, K, x.stride(0), xq.stride(0),
+                                             xs.stride(0), xs.stride(1), _lib.dtype_code(x), _lib.current_stream()),
+               "quant_fp8_group")
+    return xq, xs
+
+
+def fp8a_supported(x: Tensor, wq: Tensor, scale: Tensor) -> bool:
+    """Does quant_fp8_group + linear_fp8a take this batch?  x: the fp16 / bf16 activations or their e4m3 bytes.  Raises for a
+    (wq, scale) pair that is no FP8 block-scaled weight or an x that does not belong to it; False for rows the kernels
+    cannot stage (elements not contiguous, a row stride that is no multiple of 8 elements / 16 bytes)."""
+    from hydrainfer_amd._C.kernel.moe.experts import FP8
+    _fp8_weight(wq, scale, "linear_fp8a", 128)
+    quantised = x.dtype in (FP8, torch.uint8)
+    if x.dim() != 2 or x.shape[1] != wq.shape[1] or not (quantised or x.dtype in (torch.float16, torch.bfloat16)):
+        raise _lib.HydraHipError("linear_fp8a: x must be fp16 / bf16 / float8_e4m3fn [M, K] for a weight of [N, K] bytes")
+    return x.shape[0] >= 1 and x.stride(1) == 1 and x.stride(0) % (16 if quantised else 8) == 0
+
+
+def linear_fp8a(xq: Tensor, xs: Tensor, wq: Tensor, scale: Tensor, dtype: torch.dtype, out: Optional[Tensor] = None) -> Tensor:
+    """out[M, N] = T( sum_b (xs[m, b] * scale[n / 128, b]) * (xq[m, block b] . wq[n, block b]) ) on the FP8 MFMAs
+    (hx_linear_fp8a: a block's products into an fp32 sum from zero, one fma by the product of the two scales, blocks in
+    k order, one rounding).  (xq, xs) = quant_fp8_group(x); any M >= 1."""
+    from hydrainfer_amd._C.kernel.moe.experts import BLOCK, FP8
+    _lib.require_gpu(xq, xs, wq, scale, out)
+    if xq.dtype not in (FP8, torch.uint8):
+        raise _lib.HydraHipError(f"linear_fp8a: the activations must be float8_e4m3fn (or uint8) bytes, got {xq.dtype}")
+    if not fp8a_supported(xq, wq, scale):
+        raise _lib.HydraHipError("linear_fp8a: needs M >= 1 and rows of xq with contiguous bytes at a stride that is a multiple of 16")
+    M, K = xq.shape
+    N = wq.shape[0]
+    if xs.dtype != torch.float32 or tuple(xs.shape) != (M, K // BLOCK) or min(xs.stride()) < 1:
+        raise _lib.HydraHipError(f"linear_fp8a: the activation scales must be float32 [{M}, {K // BLOCK}] with positive strides")
+    if dtype not in (torch.float16, torch.bfloat16):
+        raise _lib.HydraHipError(f"linear_fp8a: fp16 / bf16 output, got {dtype}")
+    if out is None:
+        out = torch.empty((M, N), dtype=dtype, device=xq.device)
+    elif out.shape != (M, N) or out.dtype != dtype or out.stride(1) != 1 or out.stride(0) % 4:
+        raise _lib.HydraHipError("linear_fp8a: out must be [M, N] of `dtype`, contiguous rows, row stride % 4 == 0")
+    _lib.check(_lib.lib().hx_linear_fp8a(out.data_ptr(), xq.data_ptr(), xs.data_ptr(), wq.data_ptr(), scale.data_ptr(), M, N, K,
+                                         xq.stride(0), xs.stride(0), xs.stride(1), wq.stride(0), out.stride(0),
+                                         _lib.HX_F16 if dtype == torch.float16 else _lib.HX_BF16, _lib.current_stream()),
+               "linear_fp8a")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 def pack_weight(weight: Tensor) -> Tensor:
     """weight [N, K] -> flat [N*K] in MFMA-fragment order (hx_pack_decode_weight)."""

@@ -15,6 +15,7 @@ bool decode_supported(int head_dim);
 int decode_set_option(const char* name, int value);
 int gemm_set_option(const char* name, int value);
 int gemm_fp8_set_option(const char* name, int value);
+int gemm_fp8a_set_option(const char* name, int value);
 int fwd_set_option(const char* name, int value);
 int xreg_set_option(const char* name, int value);
 void fwd_set_stamps(void* buf);
@@ -52,6 +53,7 @@ extern "C" int hx_debug_set_option(const char* name, int value) {
   int rc = decode_set_option(name, value);
   if (rc == HX_ERR_UNSUPPORTED) rc = gemm_set_option(name, value);
   if (rc == HX_ERR_UNSUPPORTED) rc = gemm_fp8_set_option(name, value);
+  if (rc == HX_ERR_UNSUPPORTED) rc = gemm_fp8a_set_option(name, value);
   if (rc == HX_ERR_UNSUPPORTED) rc = fwd_set_option(name, value);
   if (rc == HX_ERR_UNSUPPORTED) rc = xreg_set_option(name, value);
 #if HX_EXPERIMENTS

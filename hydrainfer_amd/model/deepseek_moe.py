@@ -36,7 +36,9 @@ class DeepseekMoeForCausalLM(LlamaForCausalLM):
     of l{l}.wqkv / wo / wgu / wdown and l{l}.moe.sgu / sdown may be float8_e4m3fn [N, K] with an fp32 [N/128, K/128] scale
     under the same name + "_scale" (wqkv_scale: the q, k and v scales concatenated, so q_size and kv_size must be
     multiples of 128; wgu_scale: gate then up).  Embeddings, lm_head, norms and the router stay T.  Steps of <= 64 rows
-    never round a scaled weight; larger batches (prefill) multiply by T(q * s) (LlamaForCausalLM.linear)."""
+    never round a scaled weight; larger batches (prefill) multiply by T(q * s) (LlamaForCausalLM.linear) — or, after
+    enable_fp8_activations(), quantise their activations per (row, 128-k group) and run on the FP8 matrix instructions
+    (csrc/gemm_fp8a.hip); decode steps, the routed experts, lm_head and the router never see quantised activations."""
 
     fp8_dense = True
     DENSE_KEYS = ("wqkv", "wo", "wgu", "wdown")
@@ -125,9 +127,12 @@ class DeepseekMoeForCausalLM(LlamaForCausalLM):
     @classmethod
     def random_init(cls, shape: MoeShape, dtype: torch.dtype, device, seed: int = 0, std: float = 0.02,
                     router_std: float = 0.2, expert_std: float = None, expert_dtype: str = None,
-                    dense_dtype: str = None) -> "DeepseekMoeForCausalLM":
+                    dense_dtype: str = None, dense_activations: str = None) -> "DeepseekMoeForCausalLM":
         """N(0, std) linears and embeddings, N(0, router_std) routers, N(0, expert_std or std) routed and shared experts.
-        expert_dtype="fp8": the same draw, then quantize_experts(); dense_dtype="fp8": then quantize_dense()."""
+        expert_dtype="fp8": the same draw, then quantize_experts(); dense_dtype="fp8": then quantize_dense();
+        dense_activations="fp8": then enable_fp8_activations() (prefill of the FP8 dense linears on quantised activations)."""
+        if dense_activations not in (None, "fp8"):
+            raise ValueError(f"random_init: dense_activations {dense_activations!r} (None or 'fp8')")
         if expert_dtype not in (None, "fp8"):
             raise ValueError(f"random_init: expert_dtype {expert_dtype!r} (None or 'fp8')")
         if dense_dtype not in (None, "fp8"):
@@ -161,7 +166,9 @@ class DeepseekMoeForCausalLM(LlamaForCausalLM):
         model = cls(shape, dtype, device, st)
         if expert_dtype == "fp8":
             model.quantize_experts()
-        return model.quantize_dense() if dense_dtype == "fp8" else model
+        if dense_dtype == "fp8":
+            model.quantize_dense()
+        return model.enable_fp8_activations() if dense_activations == "fp8" else model
 
     @classmethod
     def from_reference_state_dict(cls, shape: MoeShape, sd: Dict[str, Tensor], dtype, device,

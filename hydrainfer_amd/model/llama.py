@@ -76,6 +76,9 @@ class LlamaForCausalLM:
     # FP8 block-scaled dense linears (state[key] float8_e4m3fn + state[key + "_scale"]): only a subclass whose decode
     # step runs on the general path offers them (model/deepseek_moe.py) — the in-register decode plan packs 16-bit weights
     fp8_dense = False
+    # W8A8 prefill (csrc/gemm_fp8a.hip): with FP8 dense weights, batches above 64 rows quantise their activations per
+    # (row, 128-k group) and multiply on the FP8 matrix instructions.  Off unless enable_fp8_activations() turns it on.
+    fp8_activations = False
 
     def __init__(self, shape: LlamaShape, dtype: torch.dtype, device, state: Dict[str, Tensor]):
         self.shape, self.dtype, self.device = shape, dtype, torch.device(device)
@@ -228,7 +231,9 @@ class LlamaForCausalLM:
         64 rows run on csrc/gemm_skinny_fp8.hip, which applies a block's scale to the block's fp32 partial sum and never
         rounds a scaled weight.  Larger batches (prefill) dequantise the weight into the model's scratch tensor
         (hx_dequant_fp8_block) and call the library GEMM: they multiply by T(q * s), a scaled weight ROUNDED to T — at
-        most half an ulp of T per weight away from what decode multiplies by."""
+        most half an ulp of T per weight away from what decode multiplies by.  With fp8_activations on, those larger
+        batches instead QUANTISE x per (row, 128-k group) to e4m3 and multiply bytes by bytes on the FP8 matrix
+        instructions (csrc/gemm_fp8a.hip): prefill then sees quantised activations, decode (<= 64 rows) never does."""
         if w.device.type == "meta":
             raise RuntimeError("decode-only model (prepare_decode(keep_row_major=False)): prefill / row-major GEMMs "
                                "are not available on this node")
@@ -237,10 +242,21 @@ class LlamaForCausalLM:
                 raise ValueError(f"{type(self).__name__}.linear: FP8 block-scaled weights are not supported by this model")
             if self.use_hip_gemm and hip_gemm.fp8_supported(x, w, scale):
                 return hip_gemm.linear_decode_fp8(x, w, scale)
+            if self.fp8_activations and self.use_hip_gemm and x.shape[0] > hip_gemm.FP8_MAX_ROWS and hip_gemm.fp8a_supported(x, w, scale):
+                return hip_gemm.linear_fp8a(*hip_gemm.quant_fp8_group(x), w, scale, x.dtype)
             return torch.matmul(x, self._dequantised(w, scale, x.dtype).t())
         if self.use_hip_gemm and x.shape[0] <= 64 and hip_gemm.supported(x, w):
             return hip_gemm.linear_decode(x, w)
         return torch.matmul(x, w.t())
+
+    def enable_fp8_activations(self, on: bool = True) -> "LlamaForCausalLM":
+        """Prefill linears over FP8 dense weights on quantised activations (linear()).  Only a model that runs FP8 dense
+        weights offers the switch; decode steps, routed experts, lm_head and the router are not affected by it."""
+        if on and not self.fp8_dense:
+            raise ValueError(f"{type(self).__name__}: FP8 activations need FP8 block-scaled dense weights, which this model's "
+                             "decode plan does not support; DeepseekMoeForCausalLM runs them")
+        self.fp8_activations = bool(on)
+        return self
 
     def _dequantised(self, w: Tensor, scale: Tensor, dtype: torch.dtype) -> Tensor:
         """T(q * s) of an FP8 weight as a [N, K] view of ONE scratch tensor: sized to the largest FP8 2-d weight of the

@@ -245,6 +245,35 @@ int hx_linear_decode_fp8w(void* out, const void* x, const void* wq, const float*
 int hx_debug_linear_fp8_plan(int64_t M, int64_t N, int64_t K, int32_t* out);
 int hx_dequant_fp8_block(void* out, const void* wq, const float* w_scale, int64_t N, int64_t K, int64_t ldo, int dtype,
                          hx_stream stream);
+/* W8A8: FP8 activations against the same FP8 block-scaled weights on the FP8 matrix instructions (csrc/gemm_fp8a.hip), for
+ * batches the decode kernel does not take (prefill).  Added WITHOUT raising HX_ABI_VERSION: nothing that existed changed.
+ * hx_quant_fp8_group: per-token-group quantisation of x [M, K] (T = `dtype`, HX_F16 / HX_BF16; contiguous elements, row
+ * stride ldx elements, a multiple of 8, 16-byte aligned; K % 128 == 0, any M >= 1).  For every (row m, 128-k group g), in
+ * fp32:  s = max(amax |x[m][g]|, 1e-10) / 448;  q = e4m3_rne(clamp(x / s, -448, 448))  — the IEEE division, no reciprocal;
+ * round to nearest even, subnormals included — bit for bit torch's (x.float() / s).clamp(-448, 448).to(float8_e4m3fn).
+ * xq [M, K] bytes (row stride ldq BYTES, a multiple of 16, 16-byte aligned); the scale of (m, g) is written to
+ * xs[m * xs_row_stride + g * xs_group_stride] (both strides in floats, > 0: row-major [M, K / 128] and k-major
+ * [K / 128, ld] are both expressible).  A non-finite x makes its group's scale non-finite (NaN -> NaN, inf -> inf).
+ * hx_linear_fp8a:
+ *   out[m][n] = T( sum over the 128-k blocks b, in order, of
+ *                  (xs[m][b] * w_scale[n / 128][b]) * ( sum_{k in b} float(xq[m][k]) * float(wq[n][k]) ) )
+ * — a block's 128 products go through matrix instructions into an fp32 sum that starts at zero (HX_BF16: the FP8 MFMA,
+ * which cuts the products of 8 consecutive k 13 binary places below the largest of them before adding; HX_F16: the bytes
+ * widened exactly to fp16 and the 16-bit MFMA, whose sums are fp32 — the FP8 instruction's cut exceeds the fp16 GEMM
+ * tolerance on outputs near zero); s = xs * w_scale is ONE fp32
+ * product and the block is folded in with ONE fp32 fma(block sum, s, running sum); ONE rounding to T at the store; no
+ * split-K, no atomics, deterministic.  xq / xs as written by hx_quant_fp8_group (same strides); wq / w_scale as for
+ * hx_linear_decode_fp8w (read in place: ldw BYTES, a multiple of 16; w_scale contiguous [N / 128, K / 128]); out [M, N]
+ * of T, row stride ldo elements (a multiple of 4), 8-byte aligned.  N % 128 == 0, K % 128 == 0, any M >= 1.  A row whose
+ * scale is non-finite is NaN; no other row is touched by it.  Nothing outside the operands (row gaps included) reaches
+ * a result, and nothing outside out [M, N] is written.
+ * Status as hx_linear_decode_fp8w.  "fp8a_tile_rows" (hx_debug_set_option; 0 = automatic, 64, 128) forces the rows of the
+ * output tile; results are identical for both. */
+int hx_quant_fp8_group(void* xq, float* xs, const void* x, int64_t M, int64_t K, int64_t ldx, int64_t ldq,
+                       int64_t xs_row_stride, int64_t xs_group_stride, int dtype, hx_stream stream);
+int hx_linear_fp8a(void* out, const void* xq, const float* xs, const void* wq, const float* w_scale, int64_t M, int64_t N,
+                   int64_t K, int64_t ldq, int64_t xs_row_stride, int64_t xs_group_stride, int64_t ldw, int64_t ldo, int dtype,
+                   hx_stream stream);
 /* Step-edge fusions of a decode loop (extensions, bit-identical to the ops they replace).
  * hx_embed_rms_norm: h_out[r] = table[ids[r]] (torch.nn.functional.embedding; ids int32 or int64, out-of-range
  * ids clamp) and x_out[r] = rms_norm(h_out[r]) * weight, one launch (hydrainfer/model/llama.py:80-83 + layer/norm.py).
