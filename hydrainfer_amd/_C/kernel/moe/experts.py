@@ -89,20 +89,78 @@ def dequantize_fp8_block(q: Tensor, scale: Tensor) -> Tensor:
     return (_blocks(q.float()) * scale.float()[..., :, None, :, None]).reshape(q.shape)
 
 
+MX_GROUP = 32            # consecutive k that share one E8M0 scale byte
+_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)      # the magnitudes of codes 0..7; bit 3 is the sign
+
+
+def _is_mxfp4_scale(scale: Optional[Tensor]) -> bool:
+    return scale is not None and scale.dtype == torch.uint8
+
+
+def quantize_mxfp4(w: Tensor) -> Tuple[Tensor, Tensor]:
+    """(q uint8 [..., N, K / 2], scale uint8 [..., N, K / 32]): OCP MXFP4.  Per group of 32 consecutive k the shared
+    exponent is floor(log2(amax)) - 2 (E2M1's largest exponent), stored as byte exponent + 127 (127 for an all-zero
+    group); the elements are rounded to nearest even onto the E2M1 grid and saturate at +-6.  Byte j of a row holds
+    element 2j in bits 0-3 and element 2j+1 in bits 4-7.  Load-time work in plain torch, any device."""
+    if w.dim() < 2 or w.shape[-1] % MX_GROUP:
+        raise _lib.HydraHipError("mxfp4: [..., N, K] with K a multiple of 32")
+    g = w.to(torch.float64).reshape(*w.shape[:-1], w.shape[-1] // MX_GROUP, MX_GROUP)
+    amax = g.abs().amax(dim=-1)
+    exp = torch.frexp(amax)[1].to(torch.int64) - 1 - 2            # frexp: amax = m * 2^e with m in [0.5, 1)
+    byte = torch.where(amax > 0, exp + 127, torch.full_like(exp, 127)).clamp_(0, 254)
+    a = (g.abs() * torch.exp2(-(byte - 127).to(torch.float64))[..., None]).clamp_(max=6.0)
+    # the grid's spacing is 0.5 below 2, 1 below 4 and 2 above: round to nearest even in units of that spacing
+    step = torch.where(a < 2, 0.5, torch.where(a < 4, 1.0, 2.0)).to(a.dtype)
+    a = torch.round(a / step) * step
+    code = torch.bucketize(a, torch.tensor(_E2M1, dtype=a.dtype, device=a.device)).to(torch.uint8)
+    code = (code | (torch.signbit(g).to(torch.uint8) << 3)).reshape(*w.shape[:-1], w.shape[-1] // 2, 2)
+    return (code[..., 0] | (code[..., 1] << 4)).contiguous(), byte.to(torch.uint8).contiguous()
+
+
+def dequantize_mxfp4(q: Tensor, scale: Tensor, dtype=torch.float32) -> Tensor:
+    """[..., N, K] of `dtype` (fp32 or float64): element * 2^(byte - 127) — exact in float64, and in fp32 up to 2 * 2^127 —
+    a group whose byte is 0xFF is NaN."""
+    if (q.dtype != torch.uint8 or scale.dtype != torch.uint8 or (q.shape[-1] * 2) % MX_GROUP
+            or scale.shape != q.shape[:-1] + (q.shape[-1] * 2 // MX_GROUP,)):
+        raise _lib.HydraHipError("mxfp4: q uint8 [..., N, K / 2] with scale uint8 [..., N, K / 32]")
+    if dtype not in (torch.float32, torch.float64):
+        raise _lib.HydraHipError("dequantize_mxfp4: fp32 or float64")
+    code = torch.stack([q & 0xF, q >> 4], dim=-1).reshape(*q.shape[:-1], q.shape[-1] * 2).long()
+    v = torch.tensor(_E2M1, dtype=dtype, device=q.device)[code & 7] * (1 - 2 * (code >> 3)).to(dtype)
+    s = torch.exp2(scale.to(torch.float64) - 127).to(dtype)      # 2^-127 is an fp32 denormal: exact
+    s = torch.where(scale == 0xFF, torch.full_like(s, float("nan")), s)
+    return (v.reshape(*scale.shape, MX_GROUP) * s[..., None]).reshape(code.shape)
+
+
 def _expert_weights(w_gate_up: Optional[Tensor], w_down: Optional[Tensor], dtype, scale: Optional[Tensor] = None
                     ) -> Tuple[int, int, int]:
-    """(E, h, I) of the one weight given.  With a scale the weight is e4m3 bytes (float8_e4m3fn or uint8) and the scale
-    fp32 [E, rows / 128, cols / 128] on its device; without one it is in the activations' dtype."""
+    """(E, h, I) of the one weight given.  With an fp32 scale the weight is e4m3 bytes (float8_e4m3fn or uint8) and the
+    scale [E, rows / 128, cols / 128] on its device; with a uint8 scale it is MXFP4: uint8 [E, rows, cols / 2] with the
+    scale [E, rows, cols / 32]; without one it is in the activations' dtype."""
     w, name, layout = (w_gate_up, "w_gate_up", "[E, 2I, h]") if w_gate_up is not None else (w_down, "w_down", "[E, h, I]")
+    mx = _is_mxfp4_scale(scale)
     if scale is None:
         if w.dtype in (FP8, torch.uint8):
-            raise _lib.HydraHipError(f"{name} holds fp8 bytes: it needs its block scales ({name}_scale)")
+            raise _lib.HydraHipError(f"{name} holds fp8 or mxfp4 bytes: it needs its scales ({name}_scale: fp32 "
+                                     "[E, rows / 128, cols / 128] for fp8, uint8 [E, rows, cols / 32] for mxfp4)")
         kind, ok = "in the activations' dtype", w.dtype == dtype
+    elif mx:
+        kind, ok = "of uint8 bytes, two columns per byte, when a uint8 scale is given", w.dtype == torch.uint8
+    elif scale.dtype == torch.float32:
+        kind, ok = "of float8_e4m3fn (or uint8) bytes when an fp32 scale is given", w.dtype in (FP8, torch.uint8)
     else:
-        kind, ok = "of float8_e4m3fn (or uint8) bytes when a scale is given", w.dtype in (FP8, torch.uint8)
+        raise _lib.HydraHipError(f"{name}_scale must be fp32 [E, rows / 128, cols / 128] (fp8 block scaling) or uint8 "
+                                 f"[E, rows, cols / 32] (mxfp4), not {scale.dtype}")
     if w.dim() != 3 or not w.is_contiguous() or not ok or (w_gate_up is not None and w.shape[1] % 2):
         raise _lib.HydraHipError(f"{name} must be contiguous {layout} {kind}")
-    if scale is not None:
+    cols = w.shape[2] * (2 if mx else 1)
+    if mx:
+        want = (w.shape[0], w.shape[1], cols // MX_GROUP)
+        if (w.shape[1] % BLOCK or cols % BLOCK or tuple(scale.shape) != want or not scale.is_contiguous()
+                or scale.device != w.device):
+            raise _lib.HydraHipError(f"{name}: mxfp4 is uint8 {layout[:-1]} / 2] with rows and columns multiples of 128 and "
+                                     f"{name}_scale contiguous uint8 {list(want)} on the weight's device")
+    elif scale is not None:
         if w.shape[1] % BLOCK or w.shape[2] % BLOCK:
             raise _lib.HydraHipError(f"{name}: fp8 block scaling needs rows and columns that are multiples of 128")
         want = (w.shape[0], w.shape[1] // BLOCK, w.shape[2] // BLOCK)
@@ -110,14 +168,15 @@ def _expert_weights(w_gate_up: Optional[Tensor], w_down: Optional[Tensor], dtype
                 or scale.device != w.device):
             raise _lib.HydraHipError(f"{name}_scale must be contiguous fp32 {list(want)} on the weight's device")
     if w_gate_up is not None:
-        return w.shape[0], w.shape[2], w.shape[1] // 2
-    return w.shape[0], w.shape[1], w.shape[2]
+        return w.shape[0], cols, w.shape[1] // 2
+    return w.shape[0], w.shape[1], cols
 
 
 def gate_up_silu(x: Tensor, w_gate_up: Tensor, seg: Tensor, topk: int, out: Optional[Tensor] = None,
                  w_gate_up_scale: Optional[Tensor] = None) -> Tensor:
     """act [n * topk, I] in slot order: silu(x_t Wg_e^T) * (x_t Wu_e^T) for every routed slot (t, k), e = its expert.
-    w_gate_up_scale given: w_gate_up is fp8 bytes with one scale per 128 x 128 block (hx_moe_gate_up_silu_fp8w)."""
+    w_gate_up_scale given: fp32 [E, 2I/128, h/128] — w_gate_up is fp8 bytes with one scale per 128 x 128 block
+    (hx_moe_gate_up_silu_fp8w); uint8 [E, 2I, h/32] — w_gate_up is MXFP4, uint8 [E, 2I, h/2] (hx_moe_gate_up_silu_mxfp4w)."""
     _lib.require_gpu(x, w_gate_up, seg, out, w_gate_up_scale)
     _rows(x, "x")
     E, h, inter = _expert_weights(w_gate_up, None, x.dtype, w_gate_up_scale)
@@ -129,9 +188,11 @@ def gate_up_silu(x: Tensor, w_gate_up: Tensor, seg: Tensor, topk: int, out: Opti
     elif out.shape != (n * topk, inter) or out.dtype != x.dtype or not out.is_contiguous():
         raise _lib.HydraHipError("gate_up_silu: out must be contiguous [n * topk, I]")
     if w_gate_up_scale is not None:
-        _lib.check(_lib.lib().hx_moe_gate_up_silu_fp8w(out.data_ptr(), x.data_ptr(), w_gate_up.data_ptr(),
-                                                       w_gate_up_scale.data_ptr(), seg.data_ptr(), n, int(topk), E, h, inter,
-                                                       _lib.dtype_code(x), _lib.current_stream()), "moe gate_up_silu_fp8w")
+        mx = _is_mxfp4_scale(w_gate_up_scale)
+        entry = _lib.lib().hx_moe_gate_up_silu_mxfp4w if mx else _lib.lib().hx_moe_gate_up_silu_fp8w
+        _lib.check(entry(out.data_ptr(), x.data_ptr(), w_gate_up.data_ptr(), w_gate_up_scale.data_ptr(), seg.data_ptr(), n,
+                         int(topk), E, h, inter, _lib.dtype_code(x), _lib.current_stream()),
+                   "moe gate_up_silu_mxfp4w" if mx else "moe gate_up_silu_fp8w")
         return out
     _lib.check(_lib.lib().hx_moe_gate_up_silu(out.data_ptr(), x.data_ptr(), w_gate_up.data_ptr(), seg.data_ptr(), n, int(topk),
                                               E, h, inter, _lib.dtype_code(x), _lib.current_stream()), "moe gate_up_silu")
@@ -140,7 +201,8 @@ def gate_up_silu(x: Tensor, w_gate_up: Tensor, seg: Tensor, topk: int, out: Opti
 
 def down(act: Tensor, w_down: Tensor, seg: Tensor, topk: int, out: Optional[Tensor] = None,
          w_down_scale: Optional[Tensor] = None) -> Tensor:
-    """y [n * topk, h] in slot order: act_s Wd_e^T.  w_down_scale given: fp8 bytes and block scales (hx_moe_down_fp8w)."""
+    """y [n * topk, h] in slot order: act_s Wd_e^T.  w_down_scale given: fp32 — fp8 bytes and block scales (hx_moe_down_fp8w); uint8
+    [E, h, I/32] — MXFP4 bytes [E, h, I/2] (hx_moe_down_mxfp4w)."""
     _lib.require_gpu(act, w_down, seg, out, w_down_scale)
     _rows(act, "act")
     E, h, inter = _expert_weights(None, w_down, act.dtype, w_down_scale)
@@ -152,9 +214,11 @@ def down(act: Tensor, w_down: Tensor, seg: Tensor, topk: int, out: Optional[Tens
     elif out.shape != (slots, h) or out.dtype != act.dtype or not out.is_contiguous():
         raise _lib.HydraHipError("down: out must be contiguous [n * topk, h]")
     if w_down_scale is not None:
-        _lib.check(_lib.lib().hx_moe_down_fp8w(out.data_ptr(), act.data_ptr(), w_down.data_ptr(), w_down_scale.data_ptr(),
-                                               seg.data_ptr(), slots // topk, int(topk), E, h, inter, _lib.dtype_code(act),
-                                               _lib.current_stream()), "moe down_fp8w")
+        mx = _is_mxfp4_scale(w_down_scale)
+        entry = _lib.lib().hx_moe_down_mxfp4w if mx else _lib.lib().hx_moe_down_fp8w
+        _lib.check(entry(out.data_ptr(), act.data_ptr(), w_down.data_ptr(), w_down_scale.data_ptr(), seg.data_ptr(),
+                         slots // topk, int(topk), E, h, inter, _lib.dtype_code(act), _lib.current_stream()),
+                   "moe down_mxfp4w" if mx else "moe down_fp8w")
         return out
     _lib.check(_lib.lib().hx_moe_down(out.data_ptr(), act.data_ptr(), w_down.data_ptr(), seg.data_ptr(), slots // topk, int(topk),
                                       E, h, inter, _lib.dtype_code(act), _lib.current_stream()), "moe down")
@@ -185,7 +249,7 @@ def experts_forward(x: Tensor, w_gate_up: Tensor, w_down: Tensor, topk_weights: 
                     shared: Optional[Tensor] = None, w_gate_up_scale: Optional[Tensor] = None,
                     w_down_scale: Optional[Tensor] = None) -> Tensor:
     """moe_infer (deepseek_v3.py:124-155) + the shared experts' term (:120): segments, gate|up + silu*mul, down, combine.
-    The scales select the fp8 block-scaled launches, each linear on its own."""
+    The scales select the fp8 block-scaled (fp32 scales) or the MXFP4 (uint8 scales) launches, each linear on its own."""
     topk = topk_ids.shape[1]
     seg = segments(topk_ids, w_gate_up.shape[0])
     act = gate_up_silu(x, w_gate_up, seg, topk, w_gate_up_scale=w_gate_up_scale)

@@ -9,7 +9,10 @@ MI355X-first differences (rounding-neutral with respect to the reference's ops, 
   * the routed experts may be held as FP8 block-scaled bytes (float8_e4m3fn + one fp32 scale per 128 x 128 block, the
     published DeepSeek-V3 format: csrc/moe_experts_fp8.hip) — opt-in, by quantize_experts() or by handing over such a state
     dict — and so may the shared experts (quantize_shared(); csrc/gemm_skinny_fp8.hip through the dense ops); the router
-    stays in T.
+    stays in T;
+  * or the routed experts may be held as MXFP4 (OCP microscaling: 4-bit E2M1 elements, two per byte, one E8M0 scale byte
+    per 32 consecutive k; csrc/moe_experts_mxfp4.hip) — opt-in, by quantize_experts("mxfp4") or by handing over such a
+    state dict; shared experts and router are not touched by it.
 HIP only: the router, the segments, both expert GEMMs and the combine are libhydra_hip launches; there is no fallback."""
 from typing import Callable, Dict, Optional
 
@@ -41,12 +44,22 @@ class SparseMoE:
                  w_gate_up_scale: Optional[Tensor] = None, w_down_scale: Optional[Tensor] = None,
                  shared_gate_up_scale: Optional[Tensor] = None, shared_down_scale: Optional[Tensor] = None):
         """linear(x, w, scale=None): the dense x @ w^T; it is handed a scale only for FP8 shared experts."""
-        E, two_i, h = w_gate_up.shape
-        if w_down.shape != (E, h, two_i // 2) or router_weight.shape != (E, h):
-            raise ValueError("SparseMoE: router_weight [E, h], w_gate_up [E, 2I, h], w_down [E, h, I]")
         if (w_gate_up_scale is None) != (w_down_scale is None):
-            raise ValueError("SparseMoE: fp8 experts need the scales of both weights")
-        if w_gate_up_scale is not None and (
+            raise ValueError("SparseMoE: fp8 / mxfp4 experts need the scales of both weights")
+        mx = w_gate_up_scale is not None and torch.uint8 in (w_gate_up_scale.dtype, w_down_scale.dtype)
+        E, two_i, h = w_gate_up.shape
+        if mx:                                           # two columns per byte
+            h *= 2
+            if (w_gate_up.dtype != torch.uint8 or w_down.dtype != torch.uint8 or w_gate_up_scale.dtype != torch.uint8
+                    or w_down_scale.dtype != torch.uint8 or w_down.shape != (E, h, two_i // 4)
+                    or w_gate_up_scale.shape != (E, two_i, h // 32) or w_down_scale.shape != (E, h, two_i // 64)):
+                raise ValueError("SparseMoE: mxfp4 experts are uint8 [E, 2I, h/2] and [E, h, I/2] with uint8 scales "
+                                 "[E, 2I, h/32] and [E, h, I/32]")
+        elif w_down.shape != (E, h, two_i // 2):
+            raise ValueError("SparseMoE: router_weight [E, h], w_gate_up [E, 2I, h], w_down [E, h, I]")
+        if router_weight.shape != (E, h):
+            raise ValueError("SparseMoE: router_weight [E, h], w_gate_up [E, 2I, h], w_down [E, h, I]")
+        if w_gate_up_scale is not None and not mx and (
                 w_gate_up.dtype != moe_experts.FP8 or w_down.dtype != moe_experts.FP8
                 or w_gate_up_scale.shape != (E, two_i // 128, h // 128) or w_down_scale.shape != (E, h // 128, two_i // 256)):
             raise ValueError("SparseMoE: fp8 experts are float8_e4m3fn with scales [E, 2I/128, h/128] and [E, h/128, I/128]")
@@ -80,13 +93,25 @@ class SparseMoE:
 
     @property
     def experts_fp8(self) -> bool:
-        return self.w_gate_up_scale is not None
+        return self.w_gate_up_scale is not None and self.w_gate_up_scale.dtype == torch.float32
 
-    def quantize_experts(self) -> "SparseMoE":
-        """The routed experts to FP8 block-scaled bytes, in place; the 16-bit tensors are dropped.  Idempotent."""
-        if not self.experts_fp8:
-            self.w_gate_up, self.w_gate_up_scale = moe_experts.quantize_fp8_block(self.w_gate_up)
-            self.w_down, self.w_down_scale = moe_experts.quantize_fp8_block(self.w_down)
+    @property
+    def experts_mxfp4(self) -> bool:
+        return self.w_gate_up_scale is not None and self.w_gate_up_scale.dtype == torch.uint8
+
+    def quantize_experts(self, fmt: str = "fp8") -> "SparseMoE":
+        """The routed experts to FP8 block-scaled bytes ("fp8") or to MXFP4 ("mxfp4": 4-bit E2M1 elements with one E8M0
+        scale byte per 32 k; csrc/moe_experts_mxfp4.hip), in place; the 16-bit tensors are dropped.  Idempotent; experts
+        already held in the other format are refused (quantising twice is not what either format means)."""
+        if fmt not in ("fp8", "mxfp4"):
+            raise ValueError(f"quantize_experts: format {fmt!r} ('fp8' or 'mxfp4')")
+        if self.w_gate_up_scale is not None:
+            if (fmt == "fp8") != self.experts_fp8:
+                raise ValueError(f"quantize_experts({fmt!r}): the experts are already held in the other format")
+            return self
+        quantize = moe_experts.quantize_fp8_block if fmt == "fp8" else moe_experts.quantize_mxfp4
+        self.w_gate_up, self.w_gate_up_scale = quantize(self.w_gate_up)
+        self.w_down, self.w_down_scale = quantize(self.w_down)
         return self
 
     @property
@@ -138,7 +163,9 @@ class SparseMoE:
         float8_e4m3fn come with {...}_proj.weight_scale_inv ([N / 128, K / 128] fp32): bytes and scales are stacked as they
         are (gate before up, the scales too), nothing is dequantised and `dtype` does not apply to them.  The same holds
         for shared experts published as float8_e4m3fn: a missing ...weight_scale_inv is a KeyError that names it, gate and
-        up projections of different dtypes are refused."""
+        up projections of different dtypes are refused.  Experts held as MXFP4 are uint8 [N, K / 2] weights (byte j: element
+        2j in bits 0-3, 2j+1 in bits 4-7) with {...}_proj.weight_scale (uint8 [N, K / 32], E8M0): stacked as they are; a
+        packed weight without its weight_scale is a KeyError that names it."""
         def t(name, cast=True):
             v = sd[prefix + name]
             return v.to(dtype=(dtype if cast else None) or v.dtype, device=device or v.device)
@@ -152,20 +179,33 @@ class SparseMoE:
         if len(fp8) != 1:
             raise ValueError(f"{prefix}experts: float8_e4m3fn and 16-bit expert weights in one layer")
         fp8 = fp8.pop()
+        mx = {sd[f"{prefix}experts.{e}.{p}_proj.weight"].dtype == torch.uint8
+              for e in range(n_e) for p in ("gate", "up", "down")}
+        if len(mx) != 1:
+            raise ValueError(f"{prefix}experts: mxfp4 (uint8) and other expert weights in one layer")
+        mx = mx.pop()
+        if mx:
+            for e in range(n_e):
+                for p in ("gate", "up", "down"):
+                    name = f"{prefix}experts.{e}.{p}_proj.weight_scale"
+                    if name not in sd:
+                        raise KeyError(f"{name}: the packed mxfp4 weight beside it needs its scale bytes")
         gus = downs = None
 
         def stack(suffix):
             # float8 tensors are stacked through their bytes (torch.cat / stack of float8 is not everywhere available)
             def b(name):
-                v = t(name, not fp8)
+                v = t(name, not (fp8 or mx))
                 return v.view(torch.uint8) if v.dtype == moe_experts.FP8 else v
             gu = torch.stack([torch.cat([b(f"experts.{e}.gate_proj.{suffix}"), b(f"experts.{e}.up_proj.{suffix}")], dim=0)
                               for e in range(n_e)]).contiguous()
             dn = torch.stack([b(f"experts.{e}.down_proj.{suffix}") for e in range(n_e)]).contiguous()
-            return (gu.view(moe_experts.FP8), dn.view(moe_experts.FP8)) if gu.dtype == torch.uint8 else (gu, dn)
+            return (gu.view(moe_experts.FP8), dn.view(moe_experts.FP8)) if fp8 and gu.dtype == torch.uint8 else (gu, dn)
         wgu, wdown = stack("weight")
         if fp8:
             gus, downs = stack("weight_scale_inv")
+        elif mx:
+            gus, downs = stack("weight_scale")
         sgu = sdown = sgus = sdowns = None
         if prefix + "shared_experts.gate_proj.weight" in sd:
             s_fp8 = {p: sd[f"{prefix}shared_experts.{p}_proj.weight"].dtype == moe_experts.FP8 for p in ("gate", "up", "down")}
@@ -204,6 +244,12 @@ class SparseMoE:
                 sd[f"{prefix}experts.{e}.gate_proj.weight_scale_inv"] = gus[e, :inter // 128]
                 sd[f"{prefix}experts.{e}.up_proj.weight_scale_inv"] = gus[e, inter // 128:]
                 sd[f"{prefix}experts.{e}.down_proj.weight_scale_inv"] = downs[e]
+        elif self.experts_mxfp4:
+            gus, downs = self.w_gate_up_scale.cpu(), self.w_down_scale.cpu()
+            for e in range(self.n_experts):
+                sd[f"{prefix}experts.{e}.gate_proj.weight_scale"] = gus[e, :inter]
+                sd[f"{prefix}experts.{e}.up_proj.weight_scale"] = gus[e, inter:]
+                sd[f"{prefix}experts.{e}.down_proj.weight_scale"] = downs[e]
         if self.shared_gate_up is not None:
             si = self.shared_gate_up.shape[0] // 2
             sgu = self.shared_gate_up.cpu()

@@ -32,6 +32,8 @@ class DeepseekMoeForCausalLM(LlamaForCausalLM):
     l{l}.moe.router [E, h], l{l}.moe.wgu [E, 2I, h], l{l}.moe.wdown [E, h, I], l{l}.moe.sgu [2 I_s, h], l{l}.moe.sdown.
     FP8 block-scaled routed experts (layer/moe.py): wgu / wdown are float8_e4m3fn and l{l}.moe.wgu_scale [E, 2I/128, h/128],
     l{l}.moe.wdown_scale [E, h/128, I/128] (fp32) stand beside them.
+    MXFP4 routed experts (csrc/moe_experts_mxfp4.hip): wgu / wdown are uint8 [E, 2I, h/2] / [E, h, I/2] (two E2M1 elements
+    per byte) and wgu_scale / wdown_scale uint8 [E, 2I, h/32] / [E, h, I/32] (E8M0).
     FP8 block-scaled dense linears (the published DeepSeek-V3 format of every other linear; csrc/gemm_skinny_fp8.hip): any
     of l{l}.wqkv / wo / wgu / wdown and l{l}.moe.sgu / sdown may be float8_e4m3fn [N, K] with an fp32 [N/128, K/128] scale
     under the same name + "_scale" (wqkv_scale: the q, k and v scales concatenated, so q_size and kv_size must be
@@ -95,11 +97,13 @@ class DeepseekMoeForCausalLM(LlamaForCausalLM):
         super().release()
         self.moe = {}
 
-    def quantize_experts(self) -> "DeepseekMoeForCausalLM":
-        """The routed experts of every sparse layer to FP8 block-scaled bytes (SparseMoE.quantize_experts); the state
-        holds the bytes and the scales afterwards, the 16-bit tensors are dropped.  Idempotent."""
+    def quantize_experts(self, fmt: str = "fp8") -> "DeepseekMoeForCausalLM":
+        """The routed experts of every sparse layer to FP8 block-scaled bytes, or with fmt="mxfp4" to MXFP4 (4-bit E2M1
+        elements, one E8M0 scale byte per 32 k: uint8 [E, N, K/2] with uint8 scales [E, N, K/32]) —
+        SparseMoE.quantize_experts; the state holds the bytes and the scales afterwards, the 16-bit tensors are dropped.
+        Idempotent."""
         for l, m in self.moe.items():
-            m.quantize_experts()
+            m.quantize_experts(fmt)
             self.state[f"l{l}.moe.wgu"], self.state[f"l{l}.moe.wdown"] = m.w_gate_up, m.w_down
             self.state[f"l{l}.moe.wgu_scale"], self.state[f"l{l}.moe.wdown_scale"] = m.w_gate_up_scale, m.w_down_scale
         return self
@@ -129,12 +133,12 @@ class DeepseekMoeForCausalLM(LlamaForCausalLM):
                     router_std: float = 0.2, expert_std: float = None, expert_dtype: str = None,
                     dense_dtype: str = None, dense_activations: str = None) -> "DeepseekMoeForCausalLM":
         """N(0, std) linears and embeddings, N(0, router_std) routers, N(0, expert_std or std) routed and shared experts.
-        expert_dtype="fp8": the same draw, then quantize_experts(); dense_dtype="fp8": then quantize_dense();
+        expert_dtype="fp8" / "mxfp4": the same draw, then quantize_experts(expert_dtype); dense_dtype="fp8": then quantize_dense();
         dense_activations="fp8": then enable_fp8_activations() (prefill of the FP8 dense linears on quantised activations)."""
         if dense_activations not in (None, "fp8"):
             raise ValueError(f"random_init: dense_activations {dense_activations!r} (None or 'fp8')")
-        if expert_dtype not in (None, "fp8"):
-            raise ValueError(f"random_init: expert_dtype {expert_dtype!r} (None or 'fp8')")
+        if expert_dtype not in (None, "fp8", "mxfp4"):
+            raise ValueError(f"random_init: expert_dtype {expert_dtype!r} (None, 'fp8' or 'mxfp4')")
         if dense_dtype not in (None, "fp8"):
             raise ValueError(f"random_init: dense_dtype {dense_dtype!r} (None or 'fp8')")
         g = torch.Generator(device=device).manual_seed(seed)
@@ -164,8 +168,8 @@ class DeepseekMoeForCausalLM(LlamaForCausalLM):
             st[f"l{l}.norm1"] = torch.ones(h, dtype=dtype, device=device)
             st[f"l{l}.norm2"] = torch.ones(h, dtype=dtype, device=device)
         model = cls(shape, dtype, device, st)
-        if expert_dtype == "fp8":
-            model.quantize_experts()
+        if expert_dtype is not None:
+            model.quantize_experts(expert_dtype)
         if dense_dtype == "fp8":
             model.quantize_dense()
         return model.enable_fp8_activations() if dense_activations == "fp8" else model
@@ -217,7 +221,7 @@ class DeepseekMoeForCausalLM(LlamaForCausalLM):
                 m = SparseMoE.from_reference_state_dict(prefix + p + "mlp.", sd, shape.num_experts_per_tok, dtype=dtype,
                                                         device=device)
                 st[f"l{l}.moe.router"], st[f"l{l}.moe.wgu"], st[f"l{l}.moe.wdown"] = m.router_weight, m.w_gate_up, m.w_down
-                if m.experts_fp8:
+                if m.experts_fp8 or m.experts_mxfp4:
                     st[f"l{l}.moe.wgu_scale"], st[f"l{l}.moe.wdown_scale"] = m.w_gate_up_scale, m.w_down_scale
                 if m.shared_gate_up is not None:
                     st[f"l{l}.moe.sgu"], st[f"l{l}.moe.sdown"] = m.shared_gate_up, m.shared_down
@@ -257,14 +261,16 @@ class DeepseekMoeForCausalLM(LlamaForCausalLM):
         """Bytes a decode step of n_tokens rows must stream at most: every dense linear, router and shared expert, the
         lm_head, and per sparse layer min(E, n_tokens * topk) routed experts (the distinct experts a step can hit) — at
         one byte per element plus 4 bytes per 128 x 128 block where the layer's experts are FP8 block-scaled, and the same
-        for every dense linear or shared expert that is."""
+        for every dense linear or shared expert that is; at half a byte per element plus one byte per 32 where the layer's
+        experts are MXFP4."""
         sh, es = self.shape, self.state["lm_head"].element_size()
         total = sum(v.numel() * (4 if k.endswith("_scale") else 1 if v.dtype == FP8 else es)
                     for k, v in self.state.items() if k != "embed" and v.dim() == 2)
         hit = min(sh.n_routed_experts, n_tokens * sh.num_experts_per_tok)
         per_expert = 3 * sh.hidden_size * sh.moe_intermediate_size
         for m in self.moe.values():
-            total += hit * (per_expert + 4 * per_expert // (128 * 128) if m.experts_fp8 else per_expert * es)
+            total += hit * (per_expert + 4 * per_expert // (128 * 128) if m.experts_fp8 else
+                            per_expert // 2 + per_expert // 32 if m.experts_mxfp4 else per_expert * es)
         return total
 
     def weight_bytes_resident(self) -> int:

@@ -1004,6 +1004,23 @@ int hx_moe_gate_up_silu_fp8w(void* act, const void* x, const void* wq_gate_up, c
 int hx_moe_down_fp8w(void* y, const void* act, const void* wq_down, const float* w_scale, const int32_t* seg,
                      int64_t n_tokens, int64_t topk, int64_t n_experts, int64_t hidden, int64_t inter, int dtype,
                      hx_stream stream);
+/* The same two GEMMs over MXFP4 expert weights (csrc/moe_experts_mxfp4.hip): the OCP microscaling format, E2M1 elements
+ * in groups of 32 consecutive k with one E8M0 scale byte per group.  wq_gate_up uint8 [E, 2I, h/2] / wq_down uint8
+ * [E, h, I/2]: byte j of a row holds element 2j in bits 0-3 and element 2j+1 in bits 4-7 (sign, 2 exponent bits of bias
+ * 1, 1 mantissa bit: 0, 0.5, 1, 1.5, 2, 3, 4, 6), contiguous, 16-byte aligned; w_scale uint8 [E, 2I, h/32] resp.
+ * [E, h, I/32], 4-byte aligned: byte b = 2^(b - 127) (b = 0 is 2^-127, not zero), b = 0xFF = NaN: every element of that
+ * group is a NaN weight.  Weight-only, as the FP8 entries.  With
+ *   lin(row n of expert e, token row v) = T( sum_g 2^(w_scale[e, n, g] - 127) * ( sum_{k in 32-group g} float(v[k]) * float(q[e, n, k]) ) )
+ * — a group's fp32 MFMA sum of exact products times its scale in one fp32 fma into the running sum, ONE rounding to T at
+ * the end, no weight ever rounded after scaling — act and y are what hx_moe_gate_up_silu / hx_moe_down define with lin
+ * in place of their dot products.  Shapes, status and refusal order as the FP8 entries (hidden and inter multiples of
+ * 128, the dtype before the alignment); an expert with no rows reads no weight bytes and no scales. */
+int hx_moe_gate_up_silu_mxfp4w(void* act, const void* x, const void* wq_gate_up, const uint8_t* w_scale,
+                               const int32_t* seg, int64_t n_tokens, int64_t topk, int64_t n_experts, int64_t hidden,
+                               int64_t inter, int dtype, hx_stream stream);
+int hx_moe_down_mxfp4w(void* y, const void* act, const void* wq_down, const uint8_t* w_scale, const int32_t* seg,
+                       int64_t n_tokens, int64_t topk, int64_t n_experts, int64_t hidden, int64_t inter, int dtype,
+                       hx_stream stream);
 
 /* ------------------------------------------------------------------------
  * Focal image-token pruning without a score tensor (csrc/focal_prune.hip).
